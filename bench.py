@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the hybrid SpMM hot path (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dim D] [--frontend ctypes|extension]
+                  [--dump-outputs DIR]
 
 A "step" is one pass of the hot path, Z = A*X, over one synthetic batch (graph + embedding matrix)
 already resident in HBM.  N = 1 runs BASELINE.json config 3, "Reddit-scale": 233 000 nodes /
@@ -27,6 +28,8 @@ Prints ONE JSON line on rank 0 (contract in the task description).  At N = 1 the
     RD-sized low-degree graph (the paper's Table II) and the all-dense MFMA-utilisation probe -- each
     with ITS counters from the same child passes (one rocprofv3 run per counter set covers every workload);
   * `cpu_baseline`: torch.sparse.mm on the box's host cores (threads stated), the oracle port nested beside it.
+`--dump-outputs DIR` also writes what the last timed step computed to DIR (dump_outputs); the graphs and features are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -405,9 +408,29 @@ def cpu_baseline(rp, col, X_host, D, n_cols, budget_s=20.0):
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much of Z (the whole directory must stay under 64 MB)
+
+
+def dump_outputs(out_dir, Z_pm):
+    """--dump-outputs: Z = A*X as the last timed step left it -- the persistent panel-major Z_pm [n_panels, rows, w] that
+    ShardedSpMM.step() returns -- row-major as float32 in out_dir/z.npy.  Beyond DUMP_BYTES, a fixed sample of its rows
+    (np.random.default_rng(0), ascending): the same rows for every build run with the same arguments."""
+    import torch
+    n_panels, n, w = Z_pm.shape
+    D = n_panels * w
+    k = min(n, DUMP_BYTES // (4 * D))
+    Z = Z_pm
+    if k < n:
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        Z = Z_pm.index_select(1, torch.from_numpy(rows).to(Z_pm.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "z.npy"), Z.permute(1, 0, 2).reshape(k, D).float().cpu().numpy())
+
+
 def run_case(fe, dev, workload, D, rp, col, n_local, world, rank, vworld, steps, warmup, dtype_name="f32", rule=0,
-             no_plan=False, n_gather_panels=0, dist=None, prep_runs=3, keep_op=False):
-    """Preprocess + `steps` timed steps of one workload on this rank; returns the measurements (no printing)."""
+             no_plan=False, n_gather_panels=0, dist=None, prep_runs=3, keep_op=False, dump_dir=None):
+    """Preprocess + `steps` timed steps of one workload on this rank; returns the measurements (no printing).
+    dump_dir: write what the last timed step computed there (dump_outputs)."""
     import torch
     from hcspmm.sharded import ShardedGraph, ShardedSpMM
     E = int(len(col))
@@ -468,6 +491,8 @@ def run_case(fe, dev, workload, D, rp, col, n_local, world, rank, vworld, steps,
         op.step()
     sync_all()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(dump_dir, op.Z_pm)
     kern_ms = float(np.sum([s.elapsed_time(e) for s, e in ev_pairs])) / steps if ev_pairs else float("nan")
     graph_ms = None
     if world == 1 and E <= 2_000_000:
@@ -649,7 +674,12 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cases", default="", help=argparse.SUPPRESS)
     ap.add_argument("--graph-cache", default="", help="directory holding (or receiving) the generated graphs as <workload>_rp.npy / _col.npy")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's Z = A*X, float32; a fixed seeded "
+                         "sample of its rows beyond %d MiB) to DIR/z.npy" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -780,7 +810,7 @@ def main():
             torch.cuda.empty_cache()
         return
     case = run_case(fe, dev, args.workload, D, rp, col, n_local, world, rank, vworld, args.steps, args.warmup, args.dtype,
-                    args.rule, args.no_plan, n_gather_panels, dist)
+                    args.rule, args.no_plan, n_gather_panels, dist, dump_dir=args.dump_outputs if rank == 0 else None)
     elapsed, E, header = case["elapsed"], case["E"], case["header"]
 
     red_dev = torch.device("cpu") if rehearsal else dev

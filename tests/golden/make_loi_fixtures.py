@@ -1,4 +1,4 @@
-"""Generates tests/golden/loi_*.npz -- run ONLY in the authoring container.
+"""Generates tests/golden/loi_*.npz and ref_loi_fuzz.npz -- run ONLY where the reference sources are present.
 
 Each fixture = a small seeded CSR graph + the vertex order and group sizes that the REFERENCE's
 own LOI.cpp (compiled from /root/reference by `make -C oracle ref`, driven by
@@ -93,6 +93,25 @@ def windowed_cases():
     yield "ties_400", graphs._to_csr(rows.astype(np.int64), cols.astype(np.int64), N)
 
 
+def fuzz_cases():
+    """Seeded random graphs of 100-4000 rows (tests/test_host_cpu.py::test_loi_reorder_matches_compiled_reference_on_random_graphs)
+    -> (row_pointers, column_index, variants).  Power-law and uniform graphs for the two unwindowed variants (reorder_plus_new
+    assumes a symmetric graph: uniform graphs get new_direct only), then graphs inside the windowed variants' domain."""
+    rng = np.random.default_rng(77)
+    for i in range(8):
+        N = int(rng.integers(100, 4000))
+        if i % 2 == 0:
+            rp, col = graphs.powerlaw_graph(N, N * int(rng.integers(3, 25)), seed=100 + i,
+                                            max_degree_frac=float(rng.choice([0.02, 0.3])))
+            yield rp, col, ("new_direct", "new")
+        else:
+            yield graphs.uniform_graph(N, N * int(rng.integers(1, 10)), seed=100 + i) + (("new_direct",),)
+    for i in range(12):
+        N = int(rng.choice([50, 51, 64, 299, 300, 301, 650, 1500]))
+        gen = (graphs.uniform_graph, graphs.powerlaw_graph)[i % 2]
+        yield _fill_empty_rows(*gen(N, N * int(rng.integers(2, 9)), seed=200 + i), seed=i) + (("plus_direct", "plus"),)
+
+
 if __name__ == "__main__":
     if not os.path.exists(REF_BIN):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
@@ -114,3 +133,13 @@ if __name__ == "__main__":
                             group_sizes_plus_direct=sizes_d, group_members_plus_direct=members_d, order_plus_direct=order_d,
                             group_sizes_plus=sizes_p, group_members_plus=members_p, order_plus=order_p)
         print("windowed", name, "N", len(rp) - 1, "E", len(col), "groups", len(sizes_d), len(sizes_p), "full", int((sizes_d == 16).sum()))
+    fuzz = {}
+    for i, (rp, col, variants) in enumerate(fuzz_cases()):
+        fuzz["row_pointers_%d" % i], fuzz["column_index_%d" % i] = rp, col
+        fuzz["variants_%d" % i] = np.array(variants)
+        for variant in variants:
+            sizes, _, order = run_ref(rp, col, variant)
+            assert sorted(order.tolist()) == list(range(len(rp) - 1)), (i, variant)
+            fuzz["group_sizes_%d_%s" % (i, variant)], fuzz["order_%d_%s" % (i, variant)] = sizes, order
+    np.savez_compressed(os.path.join(out_dir, "ref_loi_fuzz.npz"), n_cases=i + 1, **fuzz)
+    print("fuzz", i + 1, "graphs")

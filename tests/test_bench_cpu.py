@@ -185,3 +185,25 @@ def test_loi_block_host_side_and_oracle_sample_check():
     Zbad = Z.copy()
     Zbad[np.argsort(np.diff(rpr))[-1]] += 1.0  # the longest row is always in the sample
     assert not bench.oracle_sample_check(rpr, colr, torch.from_numpy(X), torch.from_numpy(Zbad), n_rows=500)["ok"]
+
+
+def test_dumped_outputs_are_row_major_float32_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the panel-major Z_pm a step returns, written row-major as float32; beyond DUMP_BYTES a seeded, ascending
+    sample of rows -- the same rows on every call -- and never more than DUMP_BYTES."""
+    import numpy as np
+    import torch
+    n, D = 1000, 64
+    Z = torch.arange(n * D, dtype=torch.float32).reshape(n, D)
+    Z_pm = Z.reshape(n, 2, D // 2).permute(1, 0, 2).contiguous()
+    bench.dump_outputs(str(tmp_path / "bf16"), Z_pm.to(torch.bfloat16))
+    assert np.array_equal(np.load(tmp_path / "bf16" / "z.npy"), Z.to(torch.bfloat16).float().numpy())
+    bench.dump_outputs(str(tmp_path / "full"), Z_pm)
+    full = np.load(tmp_path / "full" / "z.npy")
+    assert full.dtype == np.float32 and np.array_equal(full, Z.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 300 * D * 4 + 17)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Z_pm)
+    a, b = np.load(tmp_path / "a" / "z.npy"), np.load(tmp_path / "b" / "z.npy")
+    assert a.shape == (300, D) and a.nbytes <= bench.DUMP_BYTES and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // D
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, full[rows])

@@ -50,3 +50,22 @@ def test_more_ranks_than_gpus_is_refused_with_the_count():
     r, out = _bench(["--gpus", str(n + 1), "--steps", "2"])
     assert r.returncode == 3 and out is None
     assert "needs %d visible GPUs, found %d" % (n + 1, n) in r.stderr
+
+
+def test_dumped_outputs_are_the_product_of_the_seeded_inputs(tmp_path):
+    """--dump-outputs on the Cora-scale workload (Z = 10 000 x 32, written whole): z.npy is A*X within the oracle's bar, A the
+    seeded graph bench.py generates and X its seeded features (torch.manual_seed(1234), normal_ over the [1, rows, 32] buffer)."""
+    import numpy as np
+    import bench
+    import oracle
+    r, out = _bench(["--workload", "cora", "--steps", "3", "--warmup", "1", "--no-pmc", "--no-sweep", "--no-cpu-baseline",
+                     "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0 and out is not None and out["steps"] == 3, r.stderr[-2000:]
+    n, e, D = bench.WORKLOADS["cora"][:3]
+    rp, col = bench.make_local_block("cora", n, e, 1, 0)
+    torch.manual_seed(1234)
+    X = torch.zeros((1, n, D), device="cuda").normal_()[0].cpu().numpy()
+    Z = np.load(tmp_path / "z.npy")
+    assert Z.dtype == np.float32 and Z.shape == (n, D)
+    ok, ratio = oracle.check_spmm(Z, rp, col, X)
+    assert ok, "A*X off by %.3g x the 1e-5 bar" % ratio

@@ -5,7 +5,6 @@ import ctypes
 import glob
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -500,37 +499,20 @@ def test_loi_reorder_matches_reference_golden(path):
 
 
 def test_loi_reorder_matches_compiled_reference_on_random_graphs():
-    """Fuzz against the reference's own LOI.cpp, compiled where it lies into oracle/_ref/ (authoring container only:
-    skipped wherever that binary does not exist, e.g. on the GPU box)."""
-    ref_bin = os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "loi_ref")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/loi_ref not built (no /root/reference here)")
-    sys.path.insert(0, GOLD)
-    from make_loi_fixtures import run_ref
-    rng = np.random.default_rng(77)
-    for i in range(8):
-        N = int(rng.integers(100, 4000))
-        if i % 2 == 0:
-            rp, col = graphs.powerlaw_graph(N, N * int(rng.integers(3, 25)), seed=100 + i,
-                                            max_degree_frac=float(rng.choice([0.02, 0.3])))
-            variants = ("new_direct", "new")
-        else:
-            rp, col = graphs.uniform_graph(N, N * int(rng.integers(1, 10)), seed=100 + i)
-            variants = ("new_direct",)  # the other variant assumes a symmetric graph
-        for variant in variants:
-            sizes, _, order = run_ref(rp, col, variant)
+    """Fuzz against the reference's own LOI.cpp: 20 seeded random graphs (8 power-law / uniform for the unwindowed variants,
+    12 inside the windowed variants' domain) and the permutations the compiled reference produced for them, recorded by
+    tests/golden/make_loi_fixtures.py (fuzz_cases)."""
+    g = np.load(os.path.join(GOLD, "ref_loi_fuzz.npz"))
+    assert int(g["n_cases"]) == 20
+    checked = []
+    for i in range(int(g["n_cases"])):
+        rp, col = g["row_pointers_%d" % i], g["column_index_%d" % i]
+        for variant in g["variants_%d" % i].tolist():
             perm, gs = hcspmm.loi_reorder(_t(rp), _t(col), variant=variant)
-            assert np.array_equal(perm.numpy(), order) and np.array_equal(gs.numpy(), sizes), (i, variant)
-    # the windowed variants, on graphs inside the reference's defined domain (no row without entries)
-    from make_loi_fixtures import _fill_empty_rows
-    for i in range(12):
-        N = int(rng.choice([50, 51, 64, 299, 300, 301, 650, 1500]))
-        gen = (graphs.uniform_graph, graphs.powerlaw_graph)[i % 2]
-        rp, col = _fill_empty_rows(*gen(N, N * int(rng.integers(2, 9)), seed=200 + i), seed=i)
-        for variant in ("plus_direct", "plus"):
-            sizes, _, order = run_ref(rp, col, variant)
-            perm, gs = hcspmm.loi_reorder(_t(rp), _t(col), variant=variant)
-            assert np.array_equal(perm.numpy(), order) and np.array_equal(gs.numpy(), sizes), (i, N, variant)
+            assert np.array_equal(perm.numpy(), g["order_%d_%s" % (i, variant)]), (i, variant)
+            assert np.array_equal(gs.numpy(), g["group_sizes_%d_%s" % (i, variant)]), (i, variant)
+            checked.append(variant)
+    assert {v: checked.count(v) for v in set(checked)} == {"new_direct": 8, "new": 4, "plus_direct": 12, "plus": 12}
 
 
 def test_loi_reorder_matches_oracle_on_larger_graph():
