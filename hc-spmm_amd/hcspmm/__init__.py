@@ -462,7 +462,7 @@ def update(X, W):
     library's streaming MFMA update kernel (hcspmm_dense_update) -- the layers' torch.mm(X, weights), which for N in the
     millions and D, H of a few dozen is a stream over X.  Returns None when the operands are not of that kind (caller: torch.mm)."""
     if not (X.is_cuda and W.is_cuda and X.dtype == W.dtype == torch.float32 and X.dim() == W.dim() == 2
-            and X.size(1) == W.size(0) and X.is_contiguous() and X.size(0) > 0 and W.size(1) > 0):
+            and X.size(1) == W.size(0) and X.is_contiguous() and X.size(0) > 0 and X.size(1) > 0 and W.size(1) > 0):
         return None
     out = torch.empty((X.size(0), W.size(1)), dtype=torch.float32, device=X.device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
@@ -477,7 +477,8 @@ def weight_grad(A, B):
     kernel of hcspmm_weight_grad.  Returns None when the shape is outside the kernel's range (caller: library GEMM)."""
     L = lib()
     if not (A.is_cuda and B.is_cuda and A.dtype == B.dtype == torch.float32 and A.dim() == B.dim() == 2
-            and A.size(0) == B.size(0) and A.stride(1) == 1 and B.stride(1) == 1):
+            and A.size(0) == B.size(0) and A.stride(1) == 1 and B.stride(1) == 1
+            and A.stride(0) >= A.size(1) and B.stride(0) >= B.size(1)):  # (rows that overlap, e.g. an expanded row: not taken)
         return None
     N, D, H = A.size(0), A.size(1), B.size(1)
     ws_bytes = int(L.hcspmm_weight_grad_workspace(N, D, H))

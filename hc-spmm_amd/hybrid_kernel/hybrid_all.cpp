@@ -504,7 +504,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // X * W through the library's streaming update kernel (hcspmm.h hcspmm_dense_update); an undefined tensor (None) when
     // the operands are not fp32 device matrices of that kind, so that the caller can use torch.mm
     if (!(X.is_cuda() && W.is_cuda() && X.scalar_type() == torch::kFloat && W.scalar_type() == torch::kFloat && X.dim() == 2 &&
-          W.dim() == 2 && X.size(1) == W.size(0) && X.is_contiguous() && X.size(0) > 0 && W.size(1) > 0))
+          W.dim() == 2 && X.size(1) == W.size(0) && X.is_contiguous() && X.size(0) > 0 && X.size(1) > 0 && W.size(1) > 0))
       return torch::Tensor();
     auto out = torch::empty({X.size(0), W.size(1)}, X.options());
     const c10::DeviceGuard guard(X.device());
@@ -517,7 +517,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // dW = A^T B with K = number of nodes (hcspmm.h hcspmm_weight_grad); an undefined tensor (None) when the
     // shape is outside the kernel's range, so that the caller can use a library GEMM
     if (!(A.is_cuda() && B.is_cuda() && A.scalar_type() == torch::kFloat && B.scalar_type() == torch::kFloat &&
-          A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0) && A.stride(1) == 1 && B.stride(1) == 1))
+          A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0) && A.stride(1) == 1 && B.stride(1) == 1 &&
+          A.stride(0) >= A.size(1) && B.stride(0) >= B.size(1)))  // (rows that overlap, e.g. an expanded row: not taken)
       return torch::Tensor();
     const int64_t N = A.size(0);
     const int D = (int)A.size(1), H = (int)B.size(1);

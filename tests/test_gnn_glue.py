@@ -106,6 +106,73 @@ def test_layer_forward_backward_vs_dense_autograd(family, fixed, nodes):
     assert torch.equal(Y2, Y) and close(conv.weights.grad, Wr.grad)
 
 
+_LAYERS = [  # (class, family, input width, output width): the driver's default widths (96 -> 32 -> 32 -> 22) and the old test's
+    ("HCSPMMFunctionFirst", "gcn", 96, 32), ("HCSPMMFunctionFirst", "gcn", 32, 32), ("HCSPMMFunctionFixed32", "gcn", 32, 32),
+    ("HCSPMMFunctionFinal", "gcn", 32, 22), ("HCSPMMFunction_GINFirst", "gin", 96, 32),
+    ("HCSPMMFunction_GINFirst", "gin", 32, 32), ("HCSPMMFunction_GINFixed32", "gin", 32, 32),
+    ("HCSPMMFunction_GINFinal", "gin", 32, 22), ("HCSPMMFunction", "gcn", 96, 32), ("HCSPMMFunction", "gcn", 32, 22),
+    ("HCSPMMFunction_SAG", "sag", 96, 96), ("HCSPMMFunction_SAG", "sag", 32, 32),
+]
+
+
+def _fp64_layer(family, A, X, W, dY):
+    """The formula table of GNN_model.py's docstring in fp64 (A a scipy.sparse matrix): Y, dX, dW (None for SAG)."""
+    if family == "gcn":  # Y = A (X W), dX = (A dY) W^T, dW = X^T (A dY)
+        AdY = A @ dY
+        return A @ (X @ W), AdY @ W.T, X.T @ AdY
+    if family == "gin":  # Y = (A X) W, dX = A (dY W^T), dW = (A X)^T dY
+        AX = A @ X
+        return AX @ W, A @ (dY @ W.T), AX.T @ dY
+    return A @ X, A @ dY, None  # SAG: Y = A X, dX = A dY
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nodes", [400, 5000])
+@pytest.mark.parametrize("cls,family,din,dout", _LAYERS)
+def test_layer_autograd_vs_fp64_on_directed_graph(cls, family, din, dout, nodes):
+    """Every layer Function behind GCNConv / GINConv, plus HCSPMMFunction and HCSPMMFunction_SAG, against the formula table of
+    GNN_model.py evaluated in fp64 on the CPU, on a NON-symmetric graph: the backward pass must aggregate with A (as the
+    reference does), and the graph is asymmetric enough that the A^T gradient misses the bar.  400 nodes: the layers' X*W and
+    weight gradients go through torch.mm; 5 000: through HCSPMM.update / HCSPMM.weight_grad.  Componentwise bar: 1e-5 x the
+    same expression on absolute values."""
+    _pkg_imports()
+    import scipy.sparse as sp
+    import HCSPMM
+    import GNN_model
+    from hcspmm import graphs
+    dev = torch.device("cuda:0")
+    rp, col = graphs.powerlaw_graph(nodes, 7 * nodes + 200, seed=13, symmetric=False)
+    N = len(rp) - 1
+    A = sp.csr_matrix((np.ones(len(col)), col, rp), shape=(N, N))
+    assert (A != A.T).nnz > 0
+    rp_d, col_d = torch.from_numpy(rp).to(dev), torch.from_numpy(col).to(dev)
+    graph = (rp_d, col_d, *HCSPMM.preprocess(col_d, rp_d, N, len(col), (N + 15) // 16))
+    fn = getattr(GNN_model, cls)
+    g = torch.Generator(device=dev).manual_seed(nodes + din + dout)
+    X = torch.randn(N, din, device=dev, generator=g).requires_grad_(True)
+    W = torch.randn(din, dout, device=dev, generator=g).requires_grad_(True)
+    dY = torch.randn(N, dout, device=dev, generator=g)
+    if family == "sag":
+        Y = fn.apply(X, *graph)
+    else:
+        extra = (torch.zeros(N, din, device=dev),) if cls == "HCSPMMFunctionFinal" else ()  # HC-SpMM_main.py:45
+        Y = fn.apply(X, W, *graph, *extra)
+    Y.backward(dY)
+    Xh, Wh, dYh = (t.detach().cpu().double().numpy() for t in (X, W, dY))
+    want = _fp64_layer(family, A, Xh, Wh, dYh)
+    scale = _fp64_layer(family, A, np.abs(Xh), np.abs(Wh), np.abs(dYh))
+    got = (Y.detach(), X.grad, None if family == "sag" else W.grad)
+
+    def within(g_, w_, s_):
+        return bool(np.all(np.abs(g_.cpu().double().numpy() - w_) <= 1e-5 * s_ + 1e-30))
+    for name, g_, w_, s_ in zip(("Y", "dX", "dW"), got, want, scale):
+        if w_ is not None:
+            assert g_.shape == w_.shape and within(g_, w_, s_), name
+    # the graph tells A from A^T: the gradient a backward pass aggregating with A^T would give misses the bar
+    want_t, scale_t = _fp64_layer(family, A.T.tocsr(), Xh, Wh, dYh), _fp64_layer(family, A.T.tocsr(), np.abs(Xh), np.abs(Wh), np.abs(dYh))
+    assert not within(got[1], want_t[1], scale_t[1])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,D,H", [(5000, 32, 32), (70001, 96, 32), (4097, 32, 22), (9000, 22, 32), (6000, 32, 96), (5000, 7, 5), (4100, 128, 64)])
 def test_update_op_matches_torch_mm(N, D, H):
