@@ -170,6 +170,74 @@ class SAG(torch.nn.Module):
         return dur * 1e3 / num_rounds
 
 
+class HCSPMMFunction_Weighted(torch.autograd.Function):
+    """Edge-weighted aggregation A_w X (HCSPMM.forward_weighted).  Backward: dX = A_w^T dY, which for a pattern-symmetric
+    graph is forward_weighted on the same graph and plan with values_t = values[perm] (HCSPMM.transpose_permutation).  The
+    gradient with respect to the values is an SDDMM this library does not have yet."""
+
+    @staticmethod
+    def forward(ctx, X, values, values_t, *graph):
+        if values.requires_grad:
+            raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented; "
+                                      "pass values that do not require grad")
+        ctx.save_for_backward(values_t, *graph)
+        return HCSPMM.forward_weighted(X.contiguous(), values, *graph)[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        values_t, *graph = ctx.saved_tensors
+        d_x = HCSPMM.forward_weighted(d_out.contiguous(), values_t, *graph)[0] if ctx.needs_input_grad[0] else None
+        return (d_x, None, None) + (None,) * N_GRAPH
+
+
+class _Update(torch.autograd.Function):
+    """X W with the library's update and weight-gradient kernels (_mm / _weight_grad) on both passes."""
+
+    @staticmethod
+    def forward(ctx, X, W):
+        X = X.contiguous()
+        ctx.save_for_backward(X, W)
+        return _mm(X, W)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, W = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_x = _mm(d_out, W.transpose(0, 1)) if ctx.needs_input_grad[0] else None
+        d_w = _weight_grad(X, d_out) if ctx.needs_input_grad[1] else None
+        return d_x, d_w
+
+
+_TRANSPOSED = {}  # (row_pointers, column_index) pointers and sizes -> (weak refs, perm): the host pass runs once per graph
+
+
+def transpose_permutation(row_pointers, column_index):
+    """HCSPMM.transpose_permutation, cached per graph tensor pair."""
+    import weakref
+    key = (row_pointers.data_ptr(), column_index.data_ptr(), row_pointers.numel(), column_index.numel())
+    hit = _TRANSPOSED.get(key)
+    if hit is not None and hit[0]() is row_pointers and hit[1]() is column_index:
+        return hit[2]
+    try:
+        perm = HCSPMM.transpose_permutation(row_pointers, column_index)
+    except RuntimeError as e:
+        raise RuntimeError("HCSPMM: the edge-weighted backward needs a graph whose sparsity pattern is symmetric (A_w^T is "
+                           "then A's pattern with permuted values); this one is not") from e
+    for k in [k for k, v in _TRANSPOSED.items() if v[0]() is None or v[1]() is None]:
+        del _TRANSPOSED[k]
+    _TRANSPOSED[key] = (weakref.ref(row_pointers), weakref.ref(column_index), perm)
+    return perm
+
+
+def weighted_aggregate(X, edge_weight, graph):
+    """A_w X with autograd for X (graph = the eight graph tensors)."""
+    if edge_weight.requires_grad:
+        raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented; "
+                                  "pass values that do not require grad")
+    values_t = edge_weight.detach()[transpose_permutation(graph[0], graph[1])].contiguous()
+    return HCSPMMFunction_Weighted.apply(X, edge_weight, values_t, *graph)
+
+
 class _Conv(torch.nn.Module):
     """fixed: 1 = first layer, 0 = hidden layer, 2 = last layer (reference GNN_model.py:264-302)."""
     first_fn = hidden_fn = last_fn = None
@@ -184,9 +252,17 @@ class _Conv(torch.nn.Module):
         stdv = 1.0 / math.sqrt(self.weights.size(1))
         self.weights.data.uniform_(-stdv, stdv)
 
+    aggregate_first = False
+
     def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
-                col_nzr, output):
+                col_nzr, output, edge_weight=None):
+        """edge_weight (float32 [E], aligned with column_index): aggregate with A_w (e.g. HCSPMM.edge_norm's "sym" / "mean"
+        values) -- weighted aggregation + the update, no fused operators; None: the binary layer functions."""
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if edge_weight is not None:
+            if self.aggregate_first:
+                return _Update.apply(weighted_aggregate(X, edge_weight, graph), self.weights)
+            return weighted_aggregate(_Update.apply(X, self.weights), edge_weight, graph)
         if self.fixed == 0:
             return self.hidden_fn.apply(X, self.weights, *graph)
         if self.fixed == 2:
@@ -202,3 +278,4 @@ class GCNConv(_Conv):
 
 class GINConv(_Conv):
     first_fn, hidden_fn, last_fn = HCSPMMFunction_GINFirst, HCSPMMFunction_GINFixed32, HCSPMMFunction_GINFinal
+    aggregate_first = True

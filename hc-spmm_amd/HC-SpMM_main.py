@@ -52,6 +52,9 @@ def parse_args(argv=None):
     # memory before preprocess, features and labels move with their vertices.  "fast": the relaxed parallel variant
     # (hcspmm_loi_reorder_fast); "exact": reorder_plus_new_direct bit for bit (seconds on large graphs).
     p.add_argument("--loi", type=str, default="none", choices=["none", "fast", "exact"], help="reorder the graph (LOI) before preprocessing")
+    # aggregation with edge values: "sym" = D^-1/2 A D^-1/2 (GCN), "mean" = D^-1 A (GraphSAGE-mean), deg = row length
+    # (HCSPMM.edge_norm); "none" = the binary A of the reference
+    p.add_argument("--norm", type=str, default="none", choices=["none", "sym", "mean"], help="edge normalisation of A")
     return p.parse_args(argv)
 
 
@@ -66,20 +69,21 @@ class Net(nn.Module):
     """conv1 (first) -> ReLU -> dropout -> (num_layers - 2) x [hidden conv -> ReLU] -> conv2 (last)
     -> log_softmax   (reference HC-SpMM_main.py:66-110)."""
 
-    def __init__(self, conv_cls, dataset, graph, output, hidden, num_layers):
+    def __init__(self, conv_cls, dataset, graph, output, hidden, num_layers, edge_weight=None):
         super().__init__()
         self.dataset, self.graph, self.output = dataset, graph, output
+        self.ew = {} if edge_weight is None else {"edge_weight": edge_weight}
         self.conv1 = conv_cls(dataset.num_features, hidden, 1)
         self.hidden_layers = nn.ModuleList(conv_cls(hidden, hidden, 0) for _ in range(num_layers - 2))
         self.conv2 = conv_cls(hidden, dataset.num_classes, 2)
         self.relu = nn.ReLU()
 
     def forward(self):
-        x = self.relu(self.conv1(self.dataset.x, *self.graph, self.output))
+        x = self.relu(self.conv1(self.dataset.x, *self.graph, self.output, **self.ew))
         x = F.dropout(x, training=self.training)
         for conv in self.hidden_layers:
-            x = self.relu(conv(x, *self.graph, self.output))
-        x = self.conv2(x, *self.graph, self.output)
+            x = self.relu(conv(x, *self.graph, self.output, **self.ew))
+        x = self.conv2(x, *self.graph, self.output, **self.ew)
         return F.log_softmax(x, dim=1)
 
 
@@ -122,12 +126,15 @@ def main(argv=None):
             (time.perf_counter() - start) * 1e3, {k: v for k, v in report[0].items() if k != "ms"}, report[0]["ms"],
             next(r["ms"] for r in report if not r.get("slice_threshold") and not r.get("panel_cols"))))
     graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+    edge_weight = None
+    if args.norm != "none":  # once, on the (reordered) graph; every layer aggregates with it
+        edge_weight = HCSPMM.edge_norm(row_pointers, column_index, args.norm)
 
     if args.single_kernel:
         return SAG(*graph).profile(dataset.x)
 
     conv_cls = GCNConv if args.model == "gcn" else GINConv
-    model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers).to(device)
+    model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 
     def train():

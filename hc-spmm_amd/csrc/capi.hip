@@ -210,7 +210,7 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
                  const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
                  const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
-                 size_t workspace_bytes, void* stream_v, const FusedOperands* fused) {
+                 size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr) {
   if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
   if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
   if (N == 0) return HCSPMM_OK;
@@ -276,9 +276,17 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
       e = hcspmm::launch_fused_tiles(a, stream);
       if (e != hipSuccess) return fail_hip(e);
     }
-    e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_f32(a, vec, stream)
-        : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_f16(a, vec, stream)
-                                    : hcspmm::launch_plan_bf16(a, vec, stream);
+    if (values) {
+      if (fused) return HCSPMM_EINVAL;
+      const hcspmm::WPlanArgs wa{a, values, rowptr, ph->segment_len};
+      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
+          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_w_f16(wa, vec, stream)
+                                      : hcspmm::launch_plan_w_bf16(wa, vec, stream);
+    } else {
+      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_f32(a, vec, stream)
+          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_f16(a, vec, stream)
+                                      : hcspmm::launch_plan_bf16(a, vec, stream);
+    }
   } else {
     if (fused) return HCSPMM_EINVAL;
     if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
@@ -297,9 +305,16 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     a.N = (int)N;
     a.D = D;
     const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, nullptr);
-    e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_f32(a, vec, stream)
-        : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_f16(a, vec, stream)
-                                    : hcspmm::launch_window_bf16(a, vec, stream);
+    if (values) {
+      const hcspmm::WWindowArgs wa{a, values};
+      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
+          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_w_f16(wa, vec, stream)
+                                      : hcspmm::launch_window_w_bf16(wa, vec, stream);
+    } else {
+      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_f32(a, vec, stream)
+          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_f16(a, vec, stream)
+                                      : hcspmm::launch_window_bf16(a, vec, stream);
+    }
   }
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
@@ -312,6 +327,27 @@ extern "C" int hcspmm_forward_typed(const void* X, int64_t x_rows, int64_t ldx, 
                                     size_t workspace_bytes, void* stream_v) {
   return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
                       plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr);
+}
+
+// Edge-weighted product (spmm_weighted*.hip): the plan and launch decisions of hcspmm_forward_typed, values read on every call.
+extern "C" int hcspmm_forward_weighted(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                       const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                       const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                       const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                       void* workspace, size_t workspace_bytes, void* stream_v, const float* values) {
+  if (!values) return HCSPMM_EINVAL;  // never a silent binary product
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                      plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values);
+}
+
+extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int kind,
+                                       float* values_out, void* stream_v) {
+  if (N < 0 || E < 0 || (kind != HCSPMM_NORM_SYM && kind != HCSPMM_NORM_MEAN)) return HCSPMM_EINVAL;
+  if (E > 0 && (!rowptr || !col || !values_out || N == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  const hipError_t e = hcspmm::launch_edge_norm(rowptr, col, (int)N, (long long)E, kind == HCSPMM_NORM_SYM ? 0 : 1, values_out,
+                                                reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,

@@ -65,6 +65,21 @@ struct WindowArgs {
   int N, D;
 };
 
+// Arguments of the weighted launches (spmm_weighted*.hip, hcspmm_forward_weighted): Z = A_w * X with A_w's values aligned with
+// column_index.  The plan is the binary one, unchanged; the kernels find each entry's position from the task descriptors (ordinary,
+// wide and sliced tasks carry their first entry), from rowptr (tiny tasks, dense-tile windows: a lane's entry is its row's first
+// entry plus a running popcount of the row's mask bits) and from the fix-up list (tiny row segments).
+struct WPlanArgs {
+  PlanArgs p;
+  const float* values;  // [E]
+  const int* rowptr;    // [N + 1]
+  int segment_len;      // plan header: entries per segment of a split row
+};
+struct WWindowArgs {
+  WindowArgs w;
+  const float* values;  // [E]
+};
+
 // vec = elements per lane access.  fp32: 4 for every D >= 4 (element-aligned vectors: any stride, any base address), 2 / 1 for
 // D = 2, 3 / 1.  16-bit: 8 (D >= 32) or 4 when D and the strides are even and the bases 4-byte aligned (dword-aligned vectors), else 1.
 hipError_t launch_plan_f32(const PlanArgs& a, int vec, hipStream_t stream);
@@ -73,6 +88,15 @@ hipError_t launch_plan_f16(const PlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_f16(const WindowArgs& a, int vec, hipStream_t stream);
 hipError_t launch_plan_bf16(const PlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_bf16(const WindowArgs& a, int vec, hipStream_t stream);
+// the weighted forms (same vec contract)
+hipError_t launch_plan_w_f32(const WPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_w_f32(const WWindowArgs& a, int vec, hipStream_t stream);
+hipError_t launch_plan_w_f16(const WPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_w_f16(const WWindowArgs& a, int vec, hipStream_t stream);
+hipError_t launch_plan_w_bf16(const WPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_w_bf16(const WWindowArgs& a, int vec, hipStream_t stream);
+// values[e] = 1/sqrt(deg(row e) * deg(col e)) (kind 0) or 1/deg(row e) (kind 1), deg = row length
+hipError_t launch_edge_norm(const int* rowptr, const int* col, int N, long long E, int kind, float* values, hipStream_t stream);
 
 // dW[D x H] = A^T * B (A: N x D rows lda apart, B: N x H rows ldb apart); `partial` holds
 // weight_grad_groups(N) * D * H floats.  Shapes: weight_grad_supported(D, H).

@@ -457,6 +457,72 @@ def forward_into(X, Z, row_pointers, column_index, blockPartition, edgeToColumn,
     return Z
 
 
+def _check_values(values, E, device):
+    # the reference-style CHECK_INPUT messages (hybrid_all.cpp:185-187), then the weighted operand's own contract
+    _check_input(values, "values")
+    if values.dtype != torch.float32:
+        raise RuntimeError("values must be a float32 tensor")
+    if values.dim() != 1 or values.numel() != E:
+        raise RuntimeError("values must hold one float32 per stored entry: %d, got %s" % (E, tuple(values.shape)))
+    if values.device != device:
+        raise RuntimeError("values must be on the device of the input")
+
+
+def forward_weighted(X, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                     col_nzr):
+    """Edge-weighted aggregation -> [A_w * X]: values[e] (float32, one per entry of column_index) weights entry e.  Same
+    plan, registry, fingerprint check and workspace handling as forward; X may be float32 / float16 / bfloat16 (Z has its
+    dtype, values stay float32).  values == 1 gives forward's bits.  The values are read on every call (hcspmm.h
+    hcspmm_forward_weighted)."""
+    L = lib()
+    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                             row_nzr, False, dtypes=tuple(_DTYPES))
+    _check_values(values, E, X.device)
+    Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(L.hcspmm_forward_weighted(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
+                                        _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                        _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                        ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
+                                        _ptr(values if E else torch.zeros(1, device=X.device))))  # (NULL values: EINVAL)
+    return [Z]
+
+
+_NORMS = {"sym": 0, "mean": 1}
+
+
+def edge_norm(row_pointers, column_index, kind):
+    """Edge values of a normalised aggregation, computed on the device -> float32 [E]:
+    "sym" = 1/sqrt(deg_r * deg_c) (GCN), "mean" = 1/deg_r (GraphSAGE-mean); deg = row length."""
+    if kind not in _NORMS:
+        raise ValueError("kind must be 'sym' or 'mean', got %r" % (kind,))
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    N, E = row_pointers.numel() - 1, column_index.numel()
+    out = torch.empty(E, dtype=torch.float32, device=row_pointers.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(row_pointers.device).cuda_stream)
+    with _on_device(row_pointers.device):
+        check(lib().hcspmm_edge_norm_device(_ptr(row_pointers), _ptr(column_index), N, E, _NORMS[kind], _ptr(out), stream))
+    return out
+
+
+def transpose_permutation(row_pointers, column_index):
+    """perm (int64, on the graph's device) with values[perm] = the values of A_w^T in A's own CSR order, for a
+    pattern-symmetric graph (hcspmm_transpose_permutation; an asymmetric pattern raises)."""
+    rp = _i32_host(row_pointers)
+    col = _i32_host(column_index)
+    N, E = rp.numel() - 1, col.numel()
+    perm = torch.empty(E, dtype=torch.int32)
+    check(lib().hcspmm_transpose_permutation(_ptr(rp), _ptr(col), N, E, _ptr(perm)))
+    return perm.to(device=row_pointers.device, dtype=torch.int64)
+
+
 def update(X, W):
     """X @ W for X [N, D] (fp32, contiguous) and W [D, H] (any strides: a transposed view needs no copy) through the
     library's streaming MFMA update kernel (hcspmm_dense_update) -- the layers' torch.mm(X, weights), which for N in the

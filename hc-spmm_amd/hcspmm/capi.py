@@ -65,6 +65,10 @@ SYMBOLS = {
     "hcspmm_wide_threshold_typed": (ctypes.c_int32, [_hp, _int, _int]),
     "hcspmm_forward_typed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp,
                                     _sz, _vp]),
+    "hcspmm_forward_weighted": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
+                                       _vp, _sz, _vp, _vp]),
+    "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
+    "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "hcspmm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_forward_strided": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz,
                                       _vp]),

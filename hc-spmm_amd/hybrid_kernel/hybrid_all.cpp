@@ -206,6 +206,29 @@ torch::Tensor run_spmm(const torch::Tensor& input, const torch::Tensor& nodePoin
   return output;
 }
 
+// Edge-weighted aggregation (hcspmm_forward_weighted): the call of run_spmm plus one float32 value per stored entry
+std::vector<torch::Tensor> spmm_forward_weighted(torch::Tensor input, torch::Tensor values, torch::Tensor nodePointer,
+                                                 torch::Tensor edgeList, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                                 torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                                                 torch::Tensor col_nzr) {
+  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  CHECK_INPUT(values);
+  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
+  TORCH_CHECK(values.dim() == 1 && values.numel() == c.E, "values must hold one float32 per stored entry: ", c.E, ", got ",
+              values.sizes());
+  TORCH_CHECK(values.device() == input.device(), "values must be on the device of the input");
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
+  auto vals = c.E > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_forward_weighted(
+      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
+      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
+      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>());
+  check_rc(rc, "forward_weighted");
+  return {output};
+}
+
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
                                      const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
@@ -458,6 +481,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return h.magic == HCSPMM_PLAN_MAGIC ? hcspmm_fused_in_launch(&h, embedding_dim, hidden_dim) : 0;
   }, "form forward_*_fused takes with this plan and shape: 0 = two launches, 1 = dense-tile windows update inside the hybrid "
      "launch, 2 = the sparse-row path as well (row-tile form)");
+  m.def("forward_weighted", &spmm_forward_weighted, "edge-weighted aggregation [A_w * X] (gfx950)");
+  m.def("edge_norm", [](torch::Tensor row_pointers, torch::Tensor column_index, std::string kind) {
+    TORCH_CHECK(kind == "sym" || kind == "mean", "kind must be 'sym' or 'mean', got '", kind, "'");
+    CHECK_INPUT(row_pointers);
+    CHECK_INPUT(column_index);
+    TORCH_CHECK(row_pointers.scalar_type() == torch::kInt && column_index.scalar_type() == torch::kInt,
+                "nodePointer / edgeList must be int32");
+    const int64_t N = row_pointers.numel() - 1, E = column_index.numel();
+    auto out = torch::empty({E}, row_pointers.options().dtype(torch::kFloat));
+    const c10::DeviceGuard guard(row_pointers.device());
+    check_rc(hcspmm_edge_norm_device(iptr(row_pointers), iptr(column_index), N, E, kind == "sym" ? HCSPMM_NORM_SYM : HCSPMM_NORM_MEAN,
+                                     E ? out.data_ptr<float>() : nullptr,
+                                     (void*)c10::hip::getCurrentHIPStream(row_pointers.device().index()).stream()),
+             "edge_norm");
+    return out;
+  }, "edge values of the 'sym' (1/sqrt(deg_r deg_c)) or 'mean' (1/deg_r) normalisation, on the device");
+  m.def("transpose_permutation", [](torch::Tensor row_pointers, torch::Tensor column_index) {
+    auto rp = row_pointers.to(torch::kCPU, torch::kInt).contiguous();
+    auto col = column_index.to(torch::kCPU, torch::kInt).contiguous();
+    const int64_t N = rp.numel() - 1, E = col.numel();
+    auto perm = torch::empty({E}, rp.options());
+    check_rc(hcspmm_transpose_permutation(rp.data_ptr<int>(), E ? col.data_ptr<int>() : nullptr, N, E,
+                                          E ? perm.data_ptr<int>() : nullptr),
+             "transpose_permutation");
+    return perm.to(row_pointers.device(), torch::kLong);
+  }, "perm with values[perm] = the values of A_w^T in A's CSR order (pattern-symmetric graphs)");
   m.def("abi_version", []() { return hcspmm_abi_version(); });
   // LOI layout reorder on the host (the reference ships it as a separate file-to-file program, LOI.cpp)
   m.def("loi_reorder", [](torch::Tensor row_pointers, torch::Tensor column_index, int variant) {

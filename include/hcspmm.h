@@ -11,8 +11,10 @@
  *
  * Pointer naming: *_h = host memory, *_d = device (HBM) memory.
  * Index arrays are int32 (reference: dataset.py:102-103, K.cu:439-443); features
- * are fp32 row-major (hcspmm_forward_typed also takes fp16 / bf16).  A is binary: edge
- * values are never read.
+ * are fp32 row-major (hcspmm_forward_typed also takes fp16 / bf16).  A is binary in every entry point
+ * the reference has: their edge values are never read.  hcspmm_forward_weighted is
+ * the edge-weighted product Z = A_w * X on the same graph tensors and plans, with an fp32 value per
+ * stored entry (normalised GCN / GraphSAGE-mean aggregation, edge-weighted graphs).
  */
 #ifndef HCSPMM_H
 #define HCSPMM_H
@@ -25,7 +27,8 @@ extern "C" {
 #endif
 
 /* 3 = the signatures below.  Entry points ADDED since 3 was introduced leave it unchanged (a consumer built against an older header keeps
- * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
+ * hcspmm_transpose_permutation (round 5).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -293,6 +296,42 @@ int hcspmm_forward_typed(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d
                          const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
                          int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d,
                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Edge-weighted forward: Z = A_w * X.  Arguments of hcspmm_forward_typed (strided X / Z, x_rows, rectangular blocks, all
+ * three dtypes, with a plan or plan-free) plus
+ *   values_d[E]  fp32, aligned with column_index: values_d[e] belongs to CSR entry e.  NULL is HCSPMM_EINVAL.
+ *   Z[r][:] = sum over e in [row_pointers[r], row_pointers[r+1])  values[e] * X[column_index[e]][:]
+ * Every step is acc = fmaf(values[e], x, acc), in the order hcspmm_forward_typed adds that row: CSR order on ordinary and
+ * tiny tasks, ascending window columns on the dense-tile path (v_mfma_f32_16x16x4_f32 is a k-ordered fma chain; non-edges
+ * contribute fmaf(0, x, acc)), the same fixed shuffle tree on wide tasks, the same slice / segment order through the fix-up
+ * pass.  Hence values == 1 gives hcspmm_forward_typed's bits on every path, and exactly representable products give the
+ * bits of a sequential fp32 sum.  16-bit features are widened, accumulated in fp32 and rounded once (RNE); values stay fp32.
+ * The values are read on every call and never enter the plan: a caller may change them between calls (learned or attention
+ * weights) without preprocessing again.  Separate kernels (spmm_weighted*.hip); the binary ones are untouched.
+ * ---------------------------------------------------------------------------------------- */
+int hcspmm_forward_weighted(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype,
+                            const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                            const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                            const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                            int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
+                            const float* values_d);
+
+/* Edge normalisations of a square graph, on the device (asynchronous on `stream`); deg(r) = stored entries of row r, so
+ * self-loops count only when the graph stores them.  Rows of degree 0 own no entries.
+ *   HCSPMM_NORM_SYM  : values[e] = 1 / sqrt(deg(r) * deg(c))  (GCN: D^-1/2 A D^-1/2)
+ *   HCSPMM_NORM_MEAN : values[e] = 1 / deg(r)                 (GraphSAGE-mean: D^-1 A) */
+#define HCSPMM_NORM_SYM 0
+#define HCSPMM_NORM_MEAN 1
+int hcspmm_edge_norm_device(const int32_t* row_pointers_d, const int32_t* column_index_d, int64_t num_nodes,
+                            int64_t num_edges, int kind, float* values_out_d, void* stream);
+
+/* Transpose of a pattern-symmetric weighted graph in A's own CSR order (host): perm_out_h[E] such that values[perm] are the
+ * values of A_w^T entry by entry, so the backward dX = A_w^T * G is hcspmm_forward_weighted on the same graph and plan with
+ * values[perm] -- also for asymmetric values such as the mean normalisation.  HCSPMM_EINVAL when the pattern is not
+ * symmetric (or a row's columns are not strictly ascending). */
+int hcspmm_transpose_permutation(const int32_t* row_pointers_h, const int32_t* column_index_h, int64_t num_nodes,
+                                 int64_t num_edges, int32_t* perm_out_h);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
