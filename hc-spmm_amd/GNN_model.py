@@ -238,6 +238,67 @@ def weighted_aggregate(X, edge_weight, graph):
     return HCSPMMFunction_Weighted.apply(X, edge_weight, values_t, *graph)
 
 
+class EdgeWeightedAggregate(torch.autograd.Function):
+    """A_w X with the gradient for both operands: dX = A_w^T dY = forward_weighted(dY, w[perm]) as in
+    HCSPMMFunction_Weighted, and dw[e] = <dY[row(e)], X[col(e)]> = HCSPMM.sddmm(dY, X)."""
+
+    @staticmethod
+    def forward(ctx, X, edge_weight, perm, *graph):
+        X = X.contiguous()
+        edge_weight = edge_weight.contiguous()
+        ctx.save_for_backward(X, edge_weight, perm, *graph)
+        return HCSPMM.forward_weighted(X, edge_weight, *graph)[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, edge_weight, perm, *graph = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_x = HCSPMM.forward_weighted(d_out, edge_weight[perm].contiguous(), *graph)[0] if ctx.needs_input_grad[0] else None
+        d_w = HCSPMM.sddmm(d_out, X, *graph) if ctx.needs_input_grad[1] else None
+        return (d_x, d_w, None) + (None,) * N_GRAPH
+
+
+def edge_weighted_aggregate(X, edge_weight, graph):
+    """A_w X with autograd for X and edge_weight (float32 [E], aligned with column_index), e.g. learned or attention
+    weights; graph = the eight graph tensors, whose pattern must be symmetric (the backward's A_w^T)."""
+    perm = transpose_permutation(graph[0], graph[1])
+    return EdgeWeightedAggregate.apply(X, edge_weight, perm, *graph)
+
+
+class EdgeSoftmax(torch.autograd.Function):
+    """Softmax of logits ([E] or [heads, E], float32) over each row's stored entries (HCSPMM.edge_softmax), with its
+    backward (HCSPMM.edge_softmax_backward)."""
+
+    @staticmethod
+    def forward(ctx, logits, row_pointers):
+        alpha = HCSPMM.edge_softmax(logits.contiguous(), row_pointers)
+        ctx.save_for_backward(alpha, row_pointers)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, d_alpha):
+        alpha, row_pointers = ctx.saved_tensors
+        return HCSPMM.edge_softmax_backward(alpha, d_alpha.contiguous(), row_pointers), None
+
+
+_EDGE_ROWS = {}  # (row_pointers pointer and size) -> (weak ref, row of every stored entry as int64)
+
+
+def edge_rows(row_pointers):
+    """row(e) for every stored entry (int64, on the graph's device), cached per row_pointers tensor."""
+    import weakref
+    key = (row_pointers.data_ptr(), row_pointers.numel())
+    hit = _EDGE_ROWS.get(key)
+    if hit is not None and hit[0]() is row_pointers:
+        return hit[1]
+    n = row_pointers.numel() - 1
+    rows = torch.repeat_interleave(torch.arange(n, device=row_pointers.device), (row_pointers[1:] - row_pointers[:-1]).long())
+    for k in [k for k, v in _EDGE_ROWS.items() if v[0]() is None]:
+        del _EDGE_ROWS[k]
+    _EDGE_ROWS[key] = (weakref.ref(row_pointers), rows)
+    return rows
+
+
 class _Conv(torch.nn.Module):
     """fixed: 1 = first layer, 0 = hidden layer, 2 = last layer (reference GNN_model.py:264-302)."""
     first_fn = hidden_fn = last_fn = None
@@ -279,3 +340,43 @@ class GCNConv(_Conv):
 class GINConv(_Conv):
     first_fn, hidden_fn, last_fn = HCSPMMFunction_GINFirst, HCSPMMFunction_GINFixed32, HCSPMMFunction_GINFinal
     aggregate_first = True
+
+
+class GATConv(torch.nn.Module):
+    """Graph attention layer (GAT), `heads` heads averaged: per head k
+        h_k = X W_k                                                       (the library's update, _Update)
+        l_e = LeakyReLU(<a_dst_k, h_k[row(e)]> + <a_src_k, h_k[col(e)]>)  (row = destination, col = source)
+        alpha_k = EdgeSoftmax(l) over each row's entries;   out_k = A_alpha_k h_k   (edge_weighted_aggregate)
+    -> mean_k out_k  [N, output_dim].  The backward is autograd over these pieces.  _Conv's call signature, so that Net
+    builds it; the attention weights are the edge values, so edge_weight is refused."""
+
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2):
+        super().__init__()
+        self.fixed, self.heads, self.negative_slope = fixed, int(heads), float(negative_slope)
+        self.weights = torch.nn.Parameter(torch.empty(self.heads, input_dim, output_dim))  # W_k = weights[k], contiguous
+        self.a_src = torch.nn.Parameter(torch.empty(self.heads, output_dim))
+        self.a_dst = torch.nn.Parameter(torch.empty(self.heads, output_dim))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.weights.size(2))
+        for p in (self.weights, self.a_src, self.a_dst):
+            p.data.uniform_(-stdv, stdv)
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("GATConv computes its edge values from the features: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        rows, cols = edge_rows(row_pointers), column_index.long()
+        hs, logits = [], []
+        for k in range(self.heads):
+            h = _Update.apply(X, self.weights[k])
+            hs.append(h)
+            logits.append(torch.nn.functional.leaky_relu((h @ self.a_dst[k])[rows] + (h @ self.a_src[k])[cols],
+                                                         self.negative_slope))
+        alpha = EdgeSoftmax.apply(torch.stack(logits), row_pointers)
+        out = edge_weighted_aggregate(hs[0], alpha[0], graph)
+        for k in range(1, self.heads):
+            out = out + edge_weighted_aggregate(hs[k], alpha[k], graph)
+        return out / self.heads if self.heads > 1 else out

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GCN / GIN training driver and single-kernel profiler over the HCSPMM operators -- counterpart
+"""GCN / GIN / GAT training driver and single-kernel profiler over the HCSPMM operators -- counterpart
 of the reference's HC-SpMM_main.py (same eight flags, HC-SpMM_main.py:18-27, same printed lines
 "Prep. (ms)" :54 and "=> SAG profiling avg (ms)" GNN_model.py:261, same model shape :66-110, same
 schedule: 9 untimed warm-up epochs then --epochs timed ones, Adam lr 0.01, nll_loss :114-158).
@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GCNConv, GINConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GCNConv, GINConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -55,7 +55,14 @@ def parse_args(argv=None):
     # aggregation with edge values: "sym" = D^-1/2 A D^-1/2 (GCN), "mean" = D^-1 A (GraphSAGE-mean), deg = row length
     # (HCSPMM.edge_norm); "none" = the binary A of the reference
     p.add_argument("--norm", type=str, default="none", choices=["none", "sym", "mean"], help="edge normalisation of A")
-    return p.parse_args(argv)
+    # addition: attention heads of --model gat (GNN_model.GATConv: the heads' outputs are averaged)
+    p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat)")
+    args = p.parse_args(argv)
+    if args.model == "gat" and args.norm != "none":
+        p.error("--norm does not apply to --model gat: its edge values are the attention weights")
+    if args.heads < 1:
+        p.error("--heads must be at least 1")
+    return args
 
 
 def nll_loss(log_probs, target):
@@ -133,7 +140,10 @@ def main(argv=None):
     if args.single_kernel:
         return SAG(*graph).profile(dataset.x)
 
-    conv_cls = GCNConv if args.model == "gcn" else GINConv
+    conv_cls = {"gcn": GCNConv, "gin": GINConv}.get(args.model)
+    if args.model == "gat":
+        def conv_cls(input_dim, output_dim, fixed):
+            return GATConv(input_dim, output_dim, fixed, heads=args.heads)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 

@@ -350,6 +350,53 @@ extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// SDDMM (sddmm.hip): out[e] = <A[row(e)], B[col(e)]>.  With a plan its header vouches for the column range, as in
+// hcspmm_forward_typed; plan-free, column_index is trusted.
+extern "C" int hcspmm_sddmm(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
+                            const int32_t* rowptr, const int32_t* col, const int32_t* plan_d, const hcspmm_plan_header* ph,
+                            int64_t N, int64_t E, int D, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || b_rows < 0 || D <= 0 || lda < D || ldb < D) return HCSPMM_EINVAL;
+  if (!rowptr || (E > 0 && (!A || !B || !out || !col || N == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if ((plan_d == nullptr) != (ph == nullptr)) return HCSPMM_EINVAL;  // both or neither
+  if (ph) {
+    const int rc = hcspmm_plan_check(ph, N, E, 0);
+    if (rc != HCSPMM_OK) return rc;
+    if (b_rows < ph->num_columns) return HCSPMM_EINVAL;  // the graph gathers rows B does not have
+  }
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::SddmmArgs a{A, B, (size_t)lda, (size_t)ldb, rowptr, col, out, (int)N, D, (long long)E};
+  const int vec = pick_vec(dtype, D, lda, ldb, A, B, nullptr);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+  const hipError_t e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_sddmm_f32(a, vec, stream)
+                       : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_sddmm_f16(a, vec, stream)
+                                                   : hcspmm::launch_sddmm_bf16(a, vec, stream);
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+namespace {
+int edge_softmax_impl(const float* x, const float* y, float* out, const int32_t* rowptr, int64_t N, int64_t E, int heads,
+                      void* stream_v, bool backward) {
+  if (N < 0 || E < 0 || heads <= 0 || !rowptr) return HCSPMM_EINVAL;
+  if (E > 0 && (!x || !out || (backward && !y) || N == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || (long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
+  const hcspmm::SoftmaxArgs a{x, y, out, rowptr, (int)N, heads, (long long)E};
+  const hipError_t e = hcspmm::launch_edge_softmax(a, backward, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+}  // namespace
+
+extern "C" int hcspmm_edge_softmax(const float* logits, float* alpha, const int32_t* rowptr, int64_t N, int64_t E, int heads,
+                                   void* stream_v) {
+  return edge_softmax_impl(logits, nullptr, alpha, rowptr, N, E, heads, stream_v, false);
+}
+
+extern "C" int hcspmm_edge_softmax_backward(const float* alpha, const float* grad_alpha, float* grad_logits, const int32_t* rowptr,
+                                            int64_t N, int64_t E, int heads, void* stream_v) {
+  return edge_softmax_impl(alpha, grad_alpha, grad_logits, rowptr, N, E, heads, stream_v, true);
+}
+
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,
                                       const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                                       const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,

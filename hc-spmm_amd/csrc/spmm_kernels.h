@@ -126,5 +126,33 @@ hipError_t launch_dense_update_leftover(const float* in, const float* W, long lo
 // fused dense-tile epilogue is built for as well)
 bool dense_update_streams(const float* in, const float* out, int D, int H);
 
+// SDDMM and edge softmax (sddmm.hip; include/hcspmm.h hcspmm_sddmm, hcspmm_edge_softmax*): the kernels that produce and
+// differentiate edge values.  out[e] = <A[row(e)], B[col(e)]> in fp32 for e in [0, E), A and B of one element type.
+struct SddmmArgs {
+  const void* A;  // [N][lda]: row r of A pairs with the entries of CSR row r
+  const void* B;  // [b_rows][ldb]: indexed by column ids
+  size_t lda, ldb;
+  const int* rowptr;  // [N + 1]
+  const int* col;     // [E]
+  float* out;         // [E]
+  int N, D;
+  long long E;
+};
+// vec: as for launch_plan_* (pick_vec with A and B in the places of X and Z)
+hipError_t launch_sddmm_f32(const SddmmArgs& a, int vec, hipStream_t stream);
+hipError_t launch_sddmm_f16(const SddmmArgs& a, int vec, hipStream_t stream);
+hipError_t launch_sddmm_bf16(const SddmmArgs& a, int vec, hipStream_t stream);
+// per row r and head h, over the head-major [heads][E] arrays:
+//   forward  out = softmax(x) over the row's entries;  backward  out = x * (y - sum_row x * y)  (x = alpha, y = grad_alpha)
+struct SoftmaxArgs {
+  const float* x;  // forward: logits; backward: alpha
+  const float* y;  // backward: grad_alpha (forward: unused)
+  float* out;      // forward: alpha; backward: grad_logits
+  const int* rowptr;
+  int N, heads;
+  long long E;
+};
+hipError_t launch_edge_softmax(const SoftmaxArgs& a, bool backward, hipStream_t stream);
+
 
 }  // namespace hcspmm

@@ -24,7 +24,8 @@ __all__ = [
     "forward_fixed64_fused", "forward_final_fused", "forward_final_fused_64", "forward_GIN_final_fused", "backward",
     "backward_fixed32", "backward_fixed32_fused", "backward_final_fused", "backward_fixed64",
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
-    "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
+    "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
+    "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
 
@@ -521,6 +522,85 @@ def transpose_permutation(row_pointers, column_index):
     perm = torch.empty(E, dtype=torch.int32)
     check(lib().hcspmm_transpose_permutation(_ptr(rp), _ptr(col), N, E, _ptr(perm)))
     return perm.to(device=row_pointers.device, dtype=torch.int64)
+
+
+def _check_view(t, name, dtype=None):
+    # a 2-D row-major view: unit inner stride, any row stride (column slices of wider matrices need no copy)
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+    if t.dtype not in _DTYPES or (dtype is not None and t.dtype != dtype) or t.dim() != 2 or t.stride(1) != 1 or \
+            t.stride(0) < t.size(1):
+        raise RuntimeError("%s must be a 2-D float32 / float16 / bfloat16 view with unit inner stride%s"
+                           % (name, "" if dtype is None else ", of the dtype of A"))
+
+
+def sddmm(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr):
+    """Sampled dense-dense product on the stored entries -> float32 [E]: out[e] = <A[row(e)], B[column_index[e]]>
+    (include/hcspmm.h hcspmm_sddmm).  A [N, D] and B [b_rows, D] are float32 / float16 / bfloat16 of one dtype, 2-D views
+    with unit inner stride (column slices need no copy); 16-bit inputs are summed in fp32.  The graph tensors are those of
+    forward_weighted: with a plan in row_nzr it is checked against this graph and B must have every row it gathers.  The
+    gradient of forward_weighted with respect to its values is sddmm(dZ, X)."""
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    _check_view(A, "A")
+    _check_view(B, "B", A.dtype)
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), A.size(1)
+    if A.size(0) != N:
+        raise RuntimeError("A has %d rows but the graph has %d nodes" % (A.size(0), N))
+    if B.size(1) != D:
+        raise RuntimeError("B has %d columns but A has %d" % (B.size(1), D))
+    if B.device != A.device:
+        raise RuntimeError("B must be on the device of A")
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, B.size(0))
+    out = torch.empty(E, dtype=torch.float32, device=A.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+    with _on_device(A.device):
+        check(lib().hcspmm_sddmm(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
+                                 _ptr(row_pointers), _ptr(column_index), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                 ctypes.byref(h) if h is not None else None, N, E, D, stream))
+    return out
+
+
+def _softmax_operand(t, name, E, device):
+    _check_input(t, name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be a float32 tensor" % name)
+    if t.dim() not in (1, 2) or t.size(-1) != E or t.numel() == 0 and E > 0:
+        raise RuntimeError("%s must be [E] or [heads, E] with E = %d, got %s" % (name, E, tuple(t.shape)))
+    if t.device != device:
+        raise RuntimeError("%s must be on the device of row_pointers" % name)
+    return 1 if t.dim() == 1 else t.size(0)
+
+
+def edge_softmax(logits, row_pointers):
+    """Softmax of float32 logits over each row's stored entries -> alpha of the same shape: [E] or [heads, E] (head-major:
+    alpha[h] is a values vector forward_weighted takes as is).  Logits must be finite (hcspmm.h hcspmm_edge_softmax)."""
+    _check_input(row_pointers, "nodePointer")
+    N = row_pointers.numel() - 1
+    E = logits.size(-1) if logits.dim() else -1
+    heads = _softmax_operand(logits, "logits", E, row_pointers.device)
+    alpha = torch.empty_like(logits)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+    with _on_device(logits.device):
+        check(lib().hcspmm_edge_softmax(_ptr(logits), _ptr(alpha), _ptr(row_pointers), N, E, heads, stream))
+    return alpha
+
+
+def edge_softmax_backward(alpha, grad_alpha, row_pointers):
+    """grad_logits = alpha * (grad_alpha - sum over the row of alpha * grad_alpha), shapes as edge_softmax."""
+    _check_input(row_pointers, "nodePointer")
+    N = row_pointers.numel() - 1
+    E = alpha.size(-1) if alpha.dim() else -1
+    heads = _softmax_operand(alpha, "alpha", E, row_pointers.device)
+    if grad_alpha.shape != alpha.shape:
+        raise RuntimeError("grad_alpha must have the shape of alpha")
+    _softmax_operand(grad_alpha, "grad_alpha", E, row_pointers.device)
+    grad = torch.empty_like(alpha)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream)
+    with _on_device(alpha.device):
+        check(lib().hcspmm_edge_softmax_backward(_ptr(alpha), _ptr(grad_alpha), _ptr(grad), _ptr(row_pointers), N, E, heads,
+                                                 stream))
+    return grad
 
 
 def update(X, W):

@@ -229,6 +229,79 @@ std::vector<torch::Tensor> spmm_forward_weighted(torch::Tensor input, torch::Ten
   return {output};
 }
 
+// SDDMM (hcspmm_sddmm): out[e] = <A[row(e)], B[col(e)]>, A and B 2-D views with unit inner stride (column slices need no copy)
+torch::Tensor spmm_sddmm(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
+                         torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
+                         torch::Tensor row_nzr, torch::Tensor col_nzr) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  CHECK_CUDA(A);
+  CHECK_CUDA(B);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  for (const torch::Tensor* t : {&A, &B})
+    TORCH_CHECK(feature_dtype(*t) >= 0 && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
+                t == &A ? "A" : "B", " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
+  TORCH_CHECK(B.scalar_type() == A.scalar_type(), "B must be a 2-D float32 / float16 / bfloat16 view with unit inner stride, of the "
+              "dtype of A");
+  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0);
+  TORCH_CHECK(A.size(0) == N, "A has ", A.size(0), " rows but the graph has ", N, " nodes");
+  TORCH_CHECK(B.size(1) == A.size(1), "B has ", B.size(1), " columns but A has ", A.size(1));
+  TORCH_CHECK(B.device() == A.device(), "B must be on the device of A");
+  hcspmm_plan_header h;
+  const bool has_plan = lookup(row_nzr, nodePointer, edgeList, N, E, &h);
+  if (has_plan)
+    TORCH_CHECK(B.size(0) >= h.num_columns, "B has ", B.size(0), " rows but the plan gathers from ", h.num_columns);
+  auto out = torch::empty({E}, A.options().dtype(torch::kFloat));
+  const c10::DeviceGuard guard(A.device());
+  check_rc(hcspmm_sddmm(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
+                        E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList), has_plan ? iptr(row_nzr) : nullptr,
+                        has_plan ? &h : nullptr, N, E, (int)A.size(1),
+                        (void*)c10::hip::getCurrentHIPStream(A.device().index()).stream()),
+           "sddmm");
+  return out;
+}
+
+// the [E] or [heads, E] fp32 operands of the edge softmax -> heads
+int64_t softmax_heads(const torch::Tensor& t, const char* name, int64_t E, const torch::Tensor& nodePointer) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, name, " must be a float32 tensor");
+  TORCH_CHECK((t.dim() == 1 || t.dim() == 2) && t.size(-1) == E, name, " must be [E] or [heads, E] with E = ", E, ", got ", t.sizes());
+  TORCH_CHECK(t.device() == nodePointer.device(), name, " must be on the device of row_pointers");
+  return t.dim() == 1 ? 1 : t.size(0);
+}
+
+torch::Tensor edge_softmax(torch::Tensor logits, torch::Tensor nodePointer) {
+  CHECK_INPUT(nodePointer);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt, "nodePointer must be int32");
+  const int64_t E = logits.dim() ? logits.size(-1) : -1;
+  const int64_t heads = softmax_heads(logits, "logits", E, nodePointer);
+  auto alpha = torch::empty_like(logits);
+  const c10::DeviceGuard guard(logits.device());
+  check_rc(hcspmm_edge_softmax(logits.numel() ? logits.data_ptr<float>() : nullptr, alpha.numel() ? alpha.data_ptr<float>() : nullptr,
+                               iptr(nodePointer), nodePointer.numel() - 1, E, (int)heads,
+                               (void*)c10::hip::getCurrentHIPStream(logits.device().index()).stream()),
+           "edge_softmax");
+  return alpha;
+}
+
+torch::Tensor edge_softmax_backward(torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor nodePointer) {
+  CHECK_INPUT(nodePointer);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt, "nodePointer must be int32");
+  const int64_t E = alpha.dim() ? alpha.size(-1) : -1;
+  const int64_t heads = softmax_heads(alpha, "alpha", E, nodePointer);
+  TORCH_CHECK(grad_alpha.sizes() == alpha.sizes(), "grad_alpha must have the shape of alpha");
+  softmax_heads(grad_alpha, "grad_alpha", E, nodePointer);
+  auto grad = torch::empty_like(alpha);
+  const c10::DeviceGuard guard(alpha.device());
+  const bool any = alpha.numel() > 0;
+  check_rc(hcspmm_edge_softmax_backward(any ? alpha.data_ptr<float>() : nullptr, any ? grad_alpha.data_ptr<float>() : nullptr,
+                                        any ? grad.data_ptr<float>() : nullptr, iptr(nodePointer), nodePointer.numel() - 1, E,
+                                        (int)heads, (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
+           "edge_softmax_backward");
+  return grad;
+}
+
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
                                      const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
@@ -507,6 +580,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              "transpose_permutation");
     return perm.to(row_pointers.device(), torch::kLong);
   }, "perm with values[perm] = the values of A_w^T in A's CSR order (pattern-symmetric graphs)");
+  m.def("sddmm", &spmm_sddmm, "sampled dense-dense product on the stored entries: float32 [E], out[e] = <A[row(e)], B[col(e)]> (gfx950)");
+  m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
+  m.def("edge_softmax_backward", &edge_softmax_backward,
+        "grad_logits = alpha * (grad_alpha - row sum of alpha * grad_alpha), shapes as edge_softmax (gfx950)");
   m.def("abi_version", []() { return hcspmm_abi_version(); });
   // LOI layout reorder on the host (the reference ships it as a separate file-to-file program, LOI.cpp)
   m.def("loi_reorder", [](torch::Tensor row_pointers, torch::Tensor column_index, int variant) {

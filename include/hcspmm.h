@@ -28,7 +28,7 @@ extern "C" {
 
 /* 3 = the signatures below.  Entry points ADDED since 3 was introduced leave it unchanged (a consumer built against an older header keeps
  * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
- * hcspmm_transpose_permutation (round 5).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -332,6 +332,39 @@ int hcspmm_edge_norm_device(const int32_t* row_pointers_d, const int32_t* column
  * symmetric (or a row's columns are not strictly ascending). */
 int hcspmm_transpose_permutation(const int32_t* row_pointers_h, const int32_t* column_index_h, int64_t num_nodes,
                                  int64_t num_edges, int32_t* perm_out_h);
+
+/* ------------------------------------------------------------------------------------------
+ * SDDMM (sampled dense-dense product) on the stored entries -- with the two edge softmax entry points below, the kernels
+ * that produce and differentiate edge values (the gradient of hcspmm_forward_weighted with respect to its values is
+ * hcspmm_sddmm(dZ, X); attention layers compute their values from the features):
+ *   out_d[e] = sum_k A[row(e)][k] * B[column_index[e]][k]      for every e in [0, E), fp32, in CSR order
+ *   A_d  [num_nodes][lda]  one row per CSR row;  B_d [b_rows][ldb]  indexed by column ids (may be rectangular: a row block)
+ *   dtype HCSPMM_DTYPE_*: A and B of that type, 16-bit elements widened; the sum is accumulated in fp32 either way.
+ * Every entry is written exactly once (rows without entries own nothing); no atomics.  The order is fixed -- each of L
+ * lanes sums its own columns with fmaf in column order, then a fixed xor-butterfly over the L lanes -- so two calls give
+ * the same bits, and the result is within (D + 1) * 2^-24 * sum_k |a_k b_k| of the exact product of the widened inputs.
+ * plan_d / plan_header_h (both or neither): the header vouches for the column range -- HCSPMM_EINVAL when its num_columns
+ * exceeds b_rows, HCSPMM_EPLAN when it does not match num_nodes / num_edges; plan-free, column_index is trusted, as in
+ * hcspmm_forward_typed.  Argument errors (NULL pointers, D <= 0, lda / ldb < D, a bad dtype, negative sizes) are
+ * HCSPMM_EINVAL before any device call; E = 0 launches nothing.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------- */
+int hcspmm_sddmm(const void* A_d, int64_t lda, const void* B_d, int64_t b_rows, int64_t ldb, int dtype, float* out_d,
+                 const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* plan_d,
+                 const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim, void* stream);
+
+/* Edge softmax over each row's stored entries, per head, on head-major fp32 arrays [heads][E] (head h is the contiguous
+ * slice [h * E, (h + 1) * E), which hcspmm_forward_weighted takes as its values as is):
+ *   alpha[e] = exp(logits[e] - m_r) / sum_{j in row r} exp(logits[j] - m_r),   m_r = max_{j in row r} logits[j]
+ * Logits must be finite.  Rows of up to 16 entries are taken by one thread, up to 2048 by one wave, longer ones by a
+ * workgroup of 256 threads; each row's sums run in an order fixed by its length alone: deterministic.  Argument errors
+ * (NULL pointers, heads <= 0, negative sizes) are HCSPMM_EINVAL before any device call.  Asynchronous on `stream`. */
+int hcspmm_edge_softmax(const float* logits_d, float* alpha_out_d, const int32_t* row_pointers_d, int64_t num_nodes,
+                        int64_t num_edges, int heads, void* stream);
+
+/* Backward of hcspmm_edge_softmax, same layout and contract:
+ *   grad_logits[e] = alpha[e] * (grad_alpha[e] - sum_{j in row r} alpha[j] * grad_alpha[j]) */
+int hcspmm_edge_softmax_backward(const float* alpha_d, const float* grad_alpha_d, float* grad_logits_out_d,
+                                 const int32_t* row_pointers_d, int64_t num_nodes, int64_t num_edges, int heads, void* stream);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
