@@ -281,6 +281,51 @@ class EdgeSoftmax(torch.autograd.Function):
         return HCSPMM.edge_softmax_backward(alpha, d_alpha.contiguous(), row_pointers), None
 
 
+_PERM_I32 = {}  # id of a cached int64 perm -> (weak ref, int32 copy): the attention backward's kernel reads int32
+
+
+def transpose_permutation_i32(row_pointers, column_index):
+    """transpose_permutation as an int32 device tensor, cached per graph tensor pair (raises for an asymmetric pattern)."""
+    import weakref
+    perm = transpose_permutation(row_pointers, column_index)
+    hit = _PERM_I32.get(id(perm))
+    if hit is not None and hit[0]() is perm:
+        return hit[1]
+    for k in [k for k, v in _PERM_I32.items() if v[0]() is None]:
+        del _PERM_I32[k]
+    perm32 = perm.to(torch.int32)
+    _PERM_I32[id(perm)] = (weakref.ref(perm), perm32)
+    return perm32
+
+
+class GATAttention(torch.autograd.Function):
+    """GAT attention weights alpha [heads, E] = softmax over each row of LeakyReLU(s_dst[row] + s_src[col]) from node-major
+    scores s_dst, s_src [N, heads] (HCSPMM.gat_attention, one launch), with the gradients of both scores
+    (HCSPMM.gat_attention_backward, two launches; perm32 = transpose_permutation_i32 of the graph)."""
+
+    @staticmethod
+    def forward(ctx, s_dst, s_src, negative_slope, perm32, row_pointers, column_index):
+        s_dst, s_src = s_dst.contiguous(), s_src.contiguous()
+        alpha = HCSPMM.gat_attention(s_dst, s_src, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(alpha, s_dst, s_src, perm32, row_pointers, column_index)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, d_alpha):
+        alpha, s_dst, s_src, perm32, row_pointers, column_index = ctx.saved_tensors
+        d_dst, d_src, _ = HCSPMM.gat_attention_backward(alpha, d_alpha.contiguous(), s_dst, s_src, row_pointers, column_index,
+                                                        perm32, ctx.negative_slope)
+        return d_dst, d_src, None, None, None, None
+
+
+def gat_attention(s_dst, s_src, graph, negative_slope=0.2):
+    """GAT attention weights [heads, E] ([E] for 1-D scores) with autograd for both node-major scores; graph = the eight
+    graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over A^T)."""
+    perm32 = transpose_permutation_i32(graph[0], graph[1])
+    return GATAttention.apply(s_dst, s_src, float(negative_slope), perm32, graph[0], graph[1])
+
+
 _EDGE_ROWS = {}  # (row_pointers pointer and size) -> (weak ref, row of every stored entry as int64)
 
 
@@ -346,9 +391,11 @@ class GATConv(torch.nn.Module):
     """Graph attention layer (GAT), `heads` heads averaged: per head k
         h_k = X W_k                                                       (the library's update, _Update)
         l_e = LeakyReLU(<a_dst_k, h_k[row(e)]> + <a_src_k, h_k[col(e)]>)  (row = destination, col = source)
-        alpha_k = EdgeSoftmax(l) over each row's entries;   out_k = A_alpha_k h_k   (edge_weighted_aggregate)
-    -> mean_k out_k  [N, output_dim].  The backward is autograd over these pieces.  _Conv's call signature, so that Net
-    builds it; the attention weights are the edge values, so edge_weight is refused."""
+        alpha_k = softmax of l over each row's entries;   out_k = A_alpha_k h_k   (edge_weighted_aggregate)
+    -> mean_k out_k  [N, output_dim].  The per-node scores <a_dst_k, h_k> and <a_src_k, h_k> go node-major [N, heads] into
+    gat_attention, which computes every head's logits and softmax in one launch and their backward in two (no per-entry
+    torch op); the backward is autograd over these pieces.  _Conv's call signature, so that Net builds it; the attention
+    weights are the edge values, so edge_weight is refused.  The pattern must be symmetric."""
 
     def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2):
         super().__init__()
@@ -368,14 +415,11 @@ class GATConv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("GATConv computes its edge values from the features: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
-        rows, cols = edge_rows(row_pointers), column_index.long()
-        hs, logits = [], []
-        for k in range(self.heads):
-            h = _Update.apply(X, self.weights[k])
-            hs.append(h)
-            logits.append(torch.nn.functional.leaky_relu((h @ self.a_dst[k])[rows] + (h @ self.a_src[k])[cols],
-                                                         self.negative_slope))
-        alpha = EdgeSoftmax.apply(torch.stack(logits), row_pointers)
+        transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        hs = [_Update.apply(X, self.weights[k]) for k in range(self.heads)]
+        s_dst = torch.stack([h @ self.a_dst[k] for k, h in enumerate(hs)], 1)  # [N, heads]
+        s_src = torch.stack([h @ self.a_src[k] for k, h in enumerate(hs)], 1)
+        alpha = gat_attention(s_dst, s_src, graph, self.negative_slope)  # [heads, E]
         out = edge_weighted_aggregate(hs[0], alpha[0], graph)
         for k in range(1, self.heads):
             out = out + edge_weighted_aggregate(hs[k], alpha[k], graph)

@@ -397,6 +397,36 @@ extern "C" int hcspmm_edge_softmax_backward(const float* alpha, const float* gra
   return edge_softmax_impl(alpha, grad_alpha, grad_logits, rowptr, N, E, heads, stream_v, true);
 }
 
+// GAT attention (gat_attention.hip).  Every array with at least one element needs a pointer; column ids (and perm) are
+// trusted, as on the plan-free paths.
+extern "C" int hcspmm_gat_attention(const float* s_dst, const float* s_src, int64_t src_rows, float slope, float* alpha,
+                                    const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int heads, void* stream_v) {
+  if (N < 0 || E < 0 || src_rows < 0 || heads <= 0 || !rowptr || !__builtin_isfinite(slope)) return HCSPMM_EINVAL;
+  if ((N > 0 && !s_dst) || (src_rows > 0 && !s_src)) return HCSPMM_EINVAL;
+  if (E > 0 && (!alpha || !col || N == 0 || src_rows == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || E * heads > INT64_MAX / 4 || N * heads > INT64_MAX / 4 ||
+      src_rows > INT64_MAX / 4 / heads)
+    return HCSPMM_ERANGE;
+  const hcspmm::GatArgs a{s_dst, s_src, nullptr, nullptr, rowptr, col, nullptr, alpha, nullptr, nullptr, slope, (int)N, heads,
+                          (long long)E};
+  const hipError_t e = hcspmm::launch_gat_attention(a, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" int hcspmm_gat_attention_backward(const float* alpha, const float* grad_alpha, const float* s_dst, const float* s_src,
+                                             float slope, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t N,
+                                             int64_t E, int heads, float* grad_scores, float* grad_s_dst, float* grad_s_src,
+                                             void* stream_v) {
+  if (N < 0 || E < 0 || heads <= 0 || !rowptr || !__builtin_isfinite(slope)) return HCSPMM_EINVAL;
+  if (N > 0 && (!s_dst || !s_src || !grad_s_dst || !grad_s_src)) return HCSPMM_EINVAL;
+  if (E > 0 && (!alpha || !grad_alpha || !col || !perm || !grad_scores || N == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || E * heads > INT64_MAX / 4 || N * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
+  const hcspmm::GatArgs a{s_dst, s_src, alpha, grad_alpha, rowptr, col, perm, grad_scores, grad_s_dst, grad_s_src, slope, (int)N,
+                          heads, (long long)E};
+  const hipError_t e = hcspmm::launch_gat_attention_backward(a, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,
                                       const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                                       const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,

@@ -154,5 +154,27 @@ struct SoftmaxArgs {
 };
 hipError_t launch_edge_softmax(const SoftmaxArgs& a, bool backward, hipStream_t stream);
 
+// GAT attention (gat_attention.hip; include/hcspmm.h hcspmm_gat_attention*): scores node-major [rows][heads], per-entry
+// arrays head-major [heads][E].
+//   forward   out = softmax over the row of LeakyReLU(s_dst[r] + s_src[col[e]])  (alpha)
+//   backward  out = g (the gradient of the scores' sum z), grad_s_dst = row sums of g, grad_s_src = row sums of g[perm]
+struct GatArgs {
+  const float* s_dst;       // [N][heads]
+  const float* s_src;       // [src_rows][heads] (backward: src_rows = N)
+  const float* alpha;       // backward: [heads][E]
+  const float* grad_alpha;  // backward: [heads][E]
+  const int* rowptr;        // [N + 1]
+  const int* col;           // [E]
+  const int* perm;          // backward: [E], hcspmm_transpose_permutation's
+  float* out;               // forward: alpha; backward: g
+  float* grad_s_dst;        // backward: [N][heads]
+  float* grad_s_src;        // backward: [N][heads]
+  float slope;
+  int N, heads;
+  long long E;
+};
+hipError_t launch_gat_attention(const GatArgs& a, hipStream_t stream);
+hipError_t launch_gat_attention_backward(const GatArgs& a, hipStream_t stream);
+
 
 }  // namespace hcspmm

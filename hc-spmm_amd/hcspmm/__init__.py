@@ -25,6 +25,7 @@ __all__ = [
     "backward_fixed32", "backward_fixed32_fused", "backward_final_fused", "backward_fixed64",
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
+    "gat_attention", "gat_attention_backward",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
@@ -601,6 +602,82 @@ def edge_softmax_backward(alpha, grad_alpha, row_pointers):
         check(lib().hcspmm_edge_softmax_backward(_ptr(alpha), _ptr(grad_alpha), _ptr(grad), _ptr(row_pointers), N, E, heads,
                                                  stream))
     return grad
+
+
+def _scores_operand(t, name, device):
+    """GAT scores: float32 [rows] (one head) or [rows, heads], contiguous, on `device` -> (rows, heads)"""
+    _check_input(t, name)
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s must be a float32 tensor" % name)
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.size(1) == 0):
+        raise RuntimeError("%s must be [rows] or [rows, heads], got %s" % (name, tuple(t.shape)))
+    if t.device != device:
+        raise RuntimeError("%s must be on the device of row_pointers" % name)
+    return t.size(0), 1 if t.dim() == 1 else t.size(1)
+
+
+def _gat_graph(row_pointers, column_index, s_dst, s_src):
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    if row_pointers.dtype != torch.int32 or column_index.dtype != torch.int32:
+        raise RuntimeError("nodePointer / edgeList must be int32")
+    N, E = row_pointers.numel() - 1, column_index.numel()
+    n_dst, heads = _scores_operand(s_dst, "s_dst", row_pointers.device)
+    src_rows, heads_src = _scores_operand(s_src, "s_src", row_pointers.device)
+    if s_dst.dim() != s_src.dim() or heads != heads_src:
+        raise RuntimeError("s_dst and s_src must have the same number of heads, got %s and %s"
+                           % (tuple(s_dst.shape), tuple(s_src.shape)))
+    if n_dst != N:
+        raise RuntimeError("s_dst has %d rows but the graph has %d nodes" % (n_dst, N))
+    return N, E, src_rows, heads
+
+
+def gat_attention(s_dst, s_src, row_pointers, column_index, negative_slope=0.2):
+    """GAT attention weights -> alpha float32 [E] (one head: s_* of shape [rows]) or [heads, E] (s_* [rows, heads]):
+    alpha[h] = softmax over each row's entries of LeakyReLU(s_dst[row(e), h] + s_src[column_index[e], h]), bit for bit
+    edge_softmax of those logits, in one launch for all heads (include/hcspmm.h hcspmm_gat_attention).  s_src may have
+    any number of rows (a row block); column ids are trusted to be below it."""
+    N, E, src_rows, heads = _gat_graph(row_pointers, column_index, s_dst, s_src)
+    alpha = torch.empty((E,) if s_dst.dim() == 1 else (heads, E), dtype=torch.float32, device=s_dst.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(s_dst.device).cuda_stream)
+    with _on_device(s_dst.device):
+        check(lib().hcspmm_gat_attention(_ptr(s_dst), _ptr(s_src), src_rows, float(negative_slope), _ptr(alpha),
+                                         _ptr(row_pointers), _ptr(column_index), N, E, heads, stream))
+    return alpha
+
+
+def _perm_i32(perm, E, device):
+    _check_input(perm, "perm")
+    if perm.dtype not in (torch.int32, torch.int64) or perm.dim() != 1 or perm.numel() != E:
+        raise RuntimeError("perm must be an int32 / int64 [E] tensor with E = %d, got %s %s" % (E, perm.dtype, tuple(perm.shape)))
+    if perm.device != device:
+        raise RuntimeError("perm must be on the device of row_pointers")
+    return perm if perm.dtype == torch.int32 else perm.to(torch.int32)
+
+
+def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, perm, negative_slope=0.2):
+    """Backward of gat_attention on a square, pattern-symmetric graph -> (grad_s_dst, grad_s_src, grad_scores), shaped as
+    s_dst, s_src and alpha; grad_scores is the gradient of z = s_dst[row] + s_src[col].  perm is transpose_permutation's
+    (int64 as it returns it, or an int32 copy; the kernel reads int32).  Two launches (hcspmm_gat_attention_backward)."""
+    N, E, src_rows, heads = _gat_graph(row_pointers, column_index, s_dst, s_src)
+    if src_rows != N:
+        raise RuntimeError("s_src has %d rows but the backward needs one per node (%d)" % (src_rows, N))
+    shape = (E,) if s_dst.dim() == 1 else (heads, E)
+    for t, n in ((alpha, "alpha"), (grad_alpha, "grad_alpha")):
+        _check_input(t, n)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise RuntimeError("%s must be float32 of shape %s, got %s %s" % (n, shape, t.dtype, tuple(t.shape)))
+        if t.device != row_pointers.device:
+            raise RuntimeError("%s must be on the device of row_pointers" % n)
+    perm = _perm_i32(perm, E, row_pointers.device)
+    grad_s_dst, grad_s_src = torch.empty_like(s_dst), torch.empty_like(s_src)
+    grad_scores = torch.empty(shape, dtype=torch.float32, device=alpha.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream)
+    with _on_device(alpha.device):
+        check(lib().hcspmm_gat_attention_backward(_ptr(alpha), _ptr(grad_alpha), _ptr(s_dst), _ptr(s_src), float(negative_slope),
+                                                  _ptr(row_pointers), _ptr(column_index), _ptr(perm), N, E, heads,
+                                                  _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src), stream))
+    return grad_s_dst, grad_s_src, grad_scores
 
 
 def update(X, W):

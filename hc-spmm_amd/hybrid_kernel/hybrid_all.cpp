@@ -302,6 +302,75 @@ torch::Tensor edge_softmax_backward(torch::Tensor alpha, torch::Tensor grad_alph
   return grad;
 }
 
+// GAT scores: float32 [rows] (one head) or [rows, heads], contiguous -> heads
+int64_t gat_scores(const torch::Tensor& t, const char* name, const torch::Tensor& nodePointer) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, name, " must be a float32 tensor");
+  TORCH_CHECK(t.dim() == 1 || (t.dim() == 2 && t.size(1) > 0), name, " must be [rows] or [rows, heads], got ", t.sizes());
+  TORCH_CHECK(t.device() == nodePointer.device(), name, " must be on the device of row_pointers");
+  return t.dim() == 1 ? 1 : t.size(1);
+}
+
+int64_t gat_graph(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& s_dst, const torch::Tensor& s_src) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  const int64_t heads = gat_scores(s_dst, "s_dst", nodePointer);
+  TORCH_CHECK(s_dst.dim() == s_src.dim() && gat_scores(s_src, "s_src", nodePointer) == heads,
+              "s_dst and s_src must have the same number of heads, got ", s_dst.sizes(), " and ", s_src.sizes());
+  TORCH_CHECK(s_dst.size(0) == nodePointer.numel() - 1, "s_dst has ", s_dst.size(0), " rows but the graph has ",
+              nodePointer.numel() - 1, " nodes");
+  return heads;
+}
+
+const float* fptr(const torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
+float* mfptr(torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
+
+torch::Tensor gat_attention(torch::Tensor s_dst, torch::Tensor s_src, torch::Tensor nodePointer, torch::Tensor edgeList,
+                            double negative_slope) {
+  const int64_t heads = gat_graph(nodePointer, edgeList, s_dst, s_src);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel();
+  auto alpha = s_dst.dim() == 1 ? torch::empty({E}, s_dst.options()) : torch::empty({heads, E}, s_dst.options());
+  const c10::DeviceGuard guard(s_dst.device());
+  check_rc(hcspmm_gat_attention(fptr(s_dst), fptr(s_src), s_src.size(0), (float)negative_slope, mfptr(alpha), iptr(nodePointer),
+                                E ? iptr(edgeList) : nullptr, N, E, (int)heads,
+                                (void*)c10::hip::getCurrentHIPStream(s_dst.device().index()).stream()),
+           "gat_attention");
+  return alpha;
+}
+
+std::vector<torch::Tensor> gat_attention_backward(torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor s_dst, torch::Tensor s_src,
+                                                  torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor perm,
+                                                  double negative_slope) {
+  const int64_t heads = gat_graph(nodePointer, edgeList, s_dst, s_src);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel();
+  TORCH_CHECK(s_src.size(0) == N, "s_src has ", s_src.size(0), " rows but the backward needs one per node (", N, ")");
+  const std::vector<int64_t> shape = s_dst.dim() == 1 ? std::vector<int64_t>{E} : std::vector<int64_t>{heads, E};
+  for (const torch::Tensor* t : {&alpha, &grad_alpha}) {
+    const char* name = t == &alpha ? "alpha" : "grad_alpha";
+    TORCH_CHECK(t->is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t->is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat && t->sizes() == c10::IntArrayRef(shape), name, " must be float32 of shape ",
+                c10::IntArrayRef(shape), ", got ", t->scalar_type(), " ", t->sizes());
+    TORCH_CHECK(t->device() == nodePointer.device(), name, " must be on the device of row_pointers");
+  }
+  CHECK_INPUT(perm);
+  TORCH_CHECK((perm.scalar_type() == torch::kInt || perm.scalar_type() == torch::kLong) && perm.dim() == 1 && perm.numel() == E,
+              "perm must be an int32 / int64 [E] tensor with E = ", E, ", got ", perm.scalar_type(), " ", perm.sizes());
+  TORCH_CHECK(perm.device() == nodePointer.device(), "perm must be on the device of row_pointers");
+  auto perm32 = perm.scalar_type() == torch::kInt ? perm : perm.to(torch::kInt);
+  auto grad_s_dst = torch::empty_like(s_dst), grad_s_src = torch::empty_like(s_src);
+  auto grad_scores = torch::empty(shape, alpha.options());
+  const c10::DeviceGuard guard(alpha.device());
+  check_rc(hcspmm_gat_attention_backward(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
+                                         iptr(nodePointer), E ? iptr(edgeList) : nullptr, E ? iptr(perm32) : nullptr, N, E, (int)heads,
+                                         mfptr(grad_scores), mfptr(grad_s_dst), mfptr(grad_s_src),
+                                         (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
+           "gat_attention_backward");
+  return {grad_s_dst, grad_s_src, grad_scores};
+}
+
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
                                      const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
@@ -584,6 +653,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
   m.def("edge_softmax_backward", &edge_softmax_backward,
         "grad_logits = alpha * (grad_alpha - row sum of alpha * grad_alpha), shapes as edge_softmax (gfx950)");
+  m.def("gat_attention", &gat_attention,
+        "GAT attention weights: softmax over each row of LeakyReLU(s_dst[row] + s_src[col]), s_* float32 [rows] / [rows, heads] "
+        "-> [E] / [heads, E] (gfx950)",
+        pybind11::arg("s_dst"), pybind11::arg("s_src"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("negative_slope") = 0.2);
+  m.def("gat_attention_backward", &gat_attention_backward,
+        "backward of gat_attention (square, pattern-symmetric graph; perm = transpose_permutation) -> [grad_s_dst, grad_s_src, "
+        "grad_scores] (gfx950)",
+        pybind11::arg("alpha"), pybind11::arg("grad_alpha"), pybind11::arg("s_dst"), pybind11::arg("s_src"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("perm"), pybind11::arg("negative_slope") = 0.2);
   m.def("abi_version", []() { return hcspmm_abi_version(); });
   // LOI layout reorder on the host (the reference ships it as a separate file-to-file program, LOI.cpp)
   m.def("loi_reorder", [](torch::Tensor row_pointers, torch::Tensor column_index, int variant) {

@@ -28,7 +28,8 @@ extern "C" {
 
 /* 3 = the signatures below.  Entry points ADDED since 3 was introduced leave it unchanged (a consumer built against an older header keeps
  * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
- * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6); hcspmm_gat_attention,
+ * hcspmm_gat_attention_backward (round 7).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -365,6 +366,34 @@ int hcspmm_edge_softmax(const float* logits_d, float* alpha_out_d, const int32_t
  *   grad_logits[e] = alpha[e] * (grad_alpha[e] - sum_{j in row r} alpha[j] * grad_alpha[j]) */
 int hcspmm_edge_softmax_backward(const float* alpha_d, const float* grad_alpha_d, float* grad_logits_out_d,
                                  const int32_t* row_pointers_d, int64_t num_nodes, int64_t num_edges, int heads, void* stream);
+
+/* GAT attention: the per-entry logits of a graph attention layer and their edge softmax in one launch for all heads, from
+ * node-major fp32 scores s_dst [num_nodes][heads] and s_src [src_rows][heads]:
+ *   z[h][e] = s_dst[r][h] + s_src[c][h],  l = z > 0 ? z : z * negative_slope,  alpha[h][e] = softmax of l[h] over row r
+ * for entry e of row r with column c; alpha_out_d is head-major [heads][E], the layout of hcspmm_edge_softmax, and is bit
+ * for bit hcspmm_edge_softmax applied to l (same row scheme and fold order; l is rounded as a separate product).  z and l
+ * are never stored.  s_src may be rectangular (a row block): column ids are trusted to be below src_rows, as on the
+ * plan-free paths.  Argument errors (NULL pointers, heads <= 0, negative sizes, a non-finite negative_slope) are
+ * HCSPMM_EINVAL before any device call; E = 0 launches nothing.  Asynchronous on `stream`. */
+int hcspmm_gat_attention(const float* s_dst_d, const float* s_src_d, int64_t src_rows, float negative_slope,
+                         float* alpha_out_d, const int32_t* row_pointers_d, const int32_t* column_index_d,
+                         int64_t num_nodes, int64_t num_edges, int heads, void* stream);
+
+/* Backward of hcspmm_gat_attention on a square, pattern-symmetric graph (s_src has num_nodes rows), given grad_alpha
+ * [heads][E]:
+ *   g[h][e]          = alpha (grad_alpha - sum_{j in row r} alpha[h][j] grad_alpha[h][j]) * (z > 0 ? 1 : negative_slope)
+ *   grad_s_dst[r][h] = sum_{e in row r} g[h][e];   grad_s_src[c][h] = sum_{e' in row c} g[h][transpose_perm[e']]
+ * with transpose_perm_d [E] from hcspmm_transpose_permutation and z recomputed with the forward's bits (the derivative at
+ * z == 0 is negative_slope).  grad_scores_out_d [heads][E] receives g.  Two launches, rows walked as in the forward, fixed
+ * orders and no atomics: two calls give the same bits.  Rows without entries get zeros, so with E = 0 both grad_s_*
+ * arrays are zeroed.  Argument errors as hcspmm_gat_attention.  Asynchronous on `stream`. */
+int hcspmm_gat_attention_backward(const float* alpha_d, const float* grad_alpha_d, const float* s_dst_d,
+                                  const float* s_src_d, float negative_slope, const int32_t* row_pointers_d,
+                                  const int32_t* column_index_d, const int32_t* transpose_perm_d,
+                                  int64_t num_nodes, int64_t num_edges, int heads,
+                                  float* grad_scores_out_d /* g, [heads][E] */,
+                                  float* grad_s_dst_out_d /* [N][heads] */, float* grad_s_src_out_d /* [N][heads] */,
+                                  void* stream);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
