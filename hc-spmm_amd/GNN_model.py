@@ -265,6 +265,37 @@ def edge_weighted_aggregate(X, edge_weight, graph):
     return EdgeWeightedAggregate.apply(X, edge_weight, perm, *graph)
 
 
+class EdgeWeightedAggregateHeads(torch.autograd.Function):
+    """Multi-head A_w X: columns [h*Dh, (h+1)*Dh) of the result are A_{w[h]} X[:, h*Dh:(h+1)*Dh] for w [heads, E]
+    (HCSPMM.forward_weighted_heads, one launch), with the gradient for both operands:
+    dX = forward_weighted_heads(dY, w[:, perm]) and dw = HCSPMM.sddmm_heads(dY, X)."""
+
+    @staticmethod
+    def forward(ctx, X, edge_weight, perm, *graph):
+        X = X.contiguous()
+        edge_weight = edge_weight.contiguous()
+        ctx.save_for_backward(X, edge_weight, perm, *graph)
+        return HCSPMM.forward_weighted_heads(X, edge_weight, *graph)[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, edge_weight, perm, *graph = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_x = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_x = HCSPMM.forward_weighted_heads(d_out, edge_weight[:, perm].contiguous(), *graph)[0]
+        if ctx.needs_input_grad[1]:
+            d_w = HCSPMM.sddmm_heads(d_out, X, *graph, edge_weight.size(0))
+        return (d_x, d_w, None) + (None,) * N_GRAPH
+
+
+def edge_weighted_aggregate_heads(X, edge_weight, graph):
+    """Multi-head A_w X with autograd for X [N, heads*Dh] and edge_weight [heads, E] (float32, Dh % 4 == 0); graph = the
+    eight graph tensors, whose pattern must be symmetric (the backward's A_w^T)."""
+    perm = transpose_permutation(graph[0], graph[1])
+    return EdgeWeightedAggregateHeads.apply(X, edge_weight, perm, *graph)
+
+
 class EdgeSoftmax(torch.autograd.Function):
     """Softmax of logits ([E] or [heads, E], float32) over each row's stored entries (HCSPMM.edge_softmax), with its
     backward (HCSPMM.edge_softmax_backward)."""
@@ -395,11 +426,20 @@ class GATConv(torch.nn.Module):
     -> mean_k out_k  [N, output_dim].  The per-node scores <a_dst_k, h_k> and <a_src_k, h_k> go node-major [N, heads] into
     gat_attention, which computes every head's logits and softmax in one launch and their backward in two (no per-entry
     torch op); the backward is autograd over these pieces.  _Conv's call signature, so that Net builds it; the attention
-    weights are the edge values, so edge_weight is refused.  The pattern must be symmetric."""
+    weights are the edge values, so edge_weight is refused.  The pattern must be symmetric.
 
-    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2):
+    concat=True concatenates the heads instead -> [N, heads * output_dim] (the hidden layers of the GAT paper): one
+    update X W_cat for all heads, both scores as one product H A_blk (A_blk block-diagonal [heads * output_dim, 2 heads]
+    from a_dst / a_src; both products run on the library's update and weight-gradient kernels in both passes),
+    gat_attention, and one multi-head aggregation (edge_weighted_aggregate_heads).  The kernels need output_dim % 4 == 0.
+    The parameters are the same in both modes, so a state dict loads into either."""
+
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False):
         super().__init__()
-        self.fixed, self.heads, self.negative_slope = fixed, int(heads), float(negative_slope)
+        self.fixed, self.heads, self.negative_slope, self.concat = fixed, int(heads), float(negative_slope), bool(concat)
+        if self.concat and output_dim % 4 != 0:
+            raise ValueError("GATConv(concat=True) needs output_dim (the width of one head) to be a multiple of 4, got %d"
+                             % output_dim)
         self.weights = torch.nn.Parameter(torch.empty(self.heads, input_dim, output_dim))  # W_k = weights[k], contiguous
         self.a_src = torch.nn.Parameter(torch.empty(self.heads, output_dim))
         self.a_dst = torch.nn.Parameter(torch.empty(self.heads, output_dim))
@@ -416,6 +456,8 @@ class GATConv(torch.nn.Module):
             raise ValueError("GATConv computes its edge values from the features: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        if self.concat:
+            return self._forward_concat(X, graph)
         hs = [_Update.apply(X, self.weights[k]) for k in range(self.heads)]
         s_dst = torch.stack([h @ self.a_dst[k] for k, h in enumerate(hs)], 1)  # [N, heads]
         s_src = torch.stack([h @ self.a_src[k] for k, h in enumerate(hs)], 1)
@@ -424,3 +466,12 @@ class GATConv(torch.nn.Module):
         for k in range(1, self.heads):
             out = out + edge_weighted_aggregate(hs[k], alpha[k], graph)
         return out / self.heads if self.heads > 1 else out
+
+    def _forward_concat(self, X, graph):
+        heads, din, dout = self.weights.shape
+        w_cat = self.weights.permute(1, 0, 2).reshape(din, heads * dout)  # column block k = W_k
+        h = _Update.apply(X, w_cat)  # [N, heads * dout]
+        a_blk = torch.cat([torch.block_diag(*self.a_dst.unsqueeze(2)), torch.block_diag(*self.a_src.unsqueeze(2))], 1)
+        s = _Update.apply(h, a_blk)  # [N, 2 heads]: s_dst | s_src
+        alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope)  # [heads, E]
+        return edge_weighted_aggregate_heads(h, alpha, graph)

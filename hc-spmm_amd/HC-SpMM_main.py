@@ -57,11 +57,19 @@ def parse_args(argv=None):
     p.add_argument("--norm", type=str, default="none", choices=["none", "sym", "mean"], help="edge normalisation of A")
     # addition: attention heads of --model gat (GNN_model.GATConv: the heads' outputs are averaged)
     p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat)")
+    # addition: the first and hidden GAT layers concatenate their heads (hidden / heads features each), the last averages
+    p.add_argument("--gat-concat", action="store_true",
+                   help="--model gat: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
     args = p.parse_args(argv)
     if args.model == "gat" and args.norm != "none":
         p.error("--norm does not apply to --model gat: its edge values are the attention weights")
     if args.heads < 1:
         p.error("--heads must be at least 1")
+    if args.gat_concat and args.model != "gat":
+        p.error("--gat-concat applies to --model gat only")
+    if args.gat_concat and args.hidden % (4 * args.heads) != 0:
+        p.error("--gat-concat needs --hidden to be a multiple of 4 * heads (= %d): each head's width must be a multiple of 4"
+                % (4 * args.heads))
     return args
 
 
@@ -143,6 +151,8 @@ def main(argv=None):
     conv_cls = {"gcn": GCNConv, "gin": GINConv}.get(args.model)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
+            if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated
+                return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True)
             return GATConv(input_dim, output_dim, fixed, heads=args.heads)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)

@@ -210,9 +210,12 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
                  const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
                  const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
-                 size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr) {
+                 size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr,
+                 int heads = 0) {
   if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
   if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
+  // heads > 0: the multi-head weighted product (fp32, Dh = D / heads columns per head, Dh % 4 == 0)
+  if (heads > 0 && (dtype != HCSPMM_DTYPE_F32 || !values || fused || D % heads != 0 || (D / heads) % 4 != 0)) return HCSPMM_EINVAL;
   if (N == 0) return HCSPMM_OK;
   if (!X || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
   if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
@@ -279,7 +282,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     if (values) {
       if (fused) return HCSPMM_EINVAL;
       const hcspmm::WPlanArgs wa{a, values, rowptr, ph->segment_len};
-      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
+      if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads}, vec, stream);
+      else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_w_f16(wa, vec, stream)
                                       : hcspmm::launch_plan_w_bf16(wa, vec, stream);
     } else {
@@ -307,7 +311,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, nullptr);
     if (values) {
       const hcspmm::WWindowArgs wa{a, values};
-      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
+      if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads}, vec, stream);
+      else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_w_f16(wa, vec, stream)
                                       : hcspmm::launch_window_w_bf16(wa, vec, stream);
     } else {
@@ -340,6 +345,20 @@ extern "C" int hcspmm_forward_weighted(const void* X, int64_t x_rows, int64_t ld
                       plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values);
 }
 
+// Multi-head edge-weighted product (spmm_weighted_heads.hip): hcspmm_forward_weighted's checks and launch decisions, values
+// [heads][E], fp32 only.
+extern "C" int hcspmm_forward_weighted_heads(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                             const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                             const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                             const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                             void* workspace, size_t workspace_bytes, void* stream_v, const float* values,
+                                             int heads) {
+  if (!values || heads <= 0) return HCSPMM_EINVAL;
+  if ((long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                      plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads);
+}
+
 extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int kind,
                                        float* values_out, void* stream_v) {
   if (N < 0 || E < 0 || (kind != HCSPMM_NORM_SYM && kind != HCSPMM_NORM_MEAN)) return HCSPMM_EINVAL;
@@ -350,12 +369,14 @@ extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
-// SDDMM (sddmm.hip): out[e] = <A[row(e)], B[col(e)]>.  With a plan its header vouches for the column range, as in
-// hcspmm_forward_typed; plan-free, column_index is trusted.
-extern "C" int hcspmm_sddmm(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
-                            const int32_t* rowptr, const int32_t* col, const int32_t* plan_d, const hcspmm_plan_header* ph,
-                            int64_t N, int64_t E, int D, void* stream_v) {
+namespace {
+// heads > 0: the multi-head form (fp32, Dh = D / heads columns per head, Dh % 4 == 0); 0: hcspmm_sddmm
+int sddmm_impl(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
+               const int32_t* rowptr, const int32_t* col, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N,
+               int64_t E, int D, void* stream_v, int heads) {
   if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (heads > 0 && (dtype != HCSPMM_DTYPE_F32 || D <= 0 || D % heads != 0 || (D / heads) % 4 != 0)) return HCSPMM_EINVAL;
+  if (heads > 0 && (long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
   if (N < 0 || E < 0 || b_rows < 0 || D <= 0 || lda < D || ldb < D) return HCSPMM_EINVAL;
   if (!rowptr || (E > 0 && (!A || !B || !out || !col || N == 0))) return HCSPMM_EINVAL;
   if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
@@ -366,13 +387,32 @@ extern "C" int hcspmm_sddmm(const void* A, int64_t lda, const void* B, int64_t b
     if (b_rows < ph->num_columns) return HCSPMM_EINVAL;  // the graph gathers rows B does not have
   }
   if (E == 0) return HCSPMM_OK;
-  hcspmm::SddmmArgs a{A, B, (size_t)lda, (size_t)ldb, rowptr, col, out, (int)N, D, (long long)E};
-  const int vec = pick_vec(dtype, D, lda, ldb, A, B, nullptr);
+  const int dh = heads > 0 ? D / heads : D;
+  hcspmm::SddmmArgs a{A, B, (size_t)lda, (size_t)ldb, rowptr, col, out, (int)N, dh, (long long)E};
+  const int vec = pick_vec(dtype, dh, lda, ldb, A, B, nullptr);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
-  const hipError_t e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_sddmm_f32(a, vec, stream)
+  const hipError_t e = heads > 0 ? hcspmm::launch_sddmm_heads_f32(a, heads, vec, stream)
+                       : dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_sddmm_f32(a, vec, stream)
                        : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_sddmm_f16(a, vec, stream)
                                                    : hcspmm::launch_sddmm_bf16(a, vec, stream);
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+}  // namespace
+
+// SDDMM (sddmm.hip): out[e] = <A[row(e)], B[col(e)]>.  With a plan its header vouches for the column range, as in
+// hcspmm_forward_typed; plan-free, column_index is trusted.
+extern "C" int hcspmm_sddmm(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
+                            const int32_t* rowptr, const int32_t* col, const int32_t* plan_d, const hcspmm_plan_header* ph,
+                            int64_t N, int64_t E, int D, void* stream_v) {
+  return sddmm_impl(A, lda, B, b_rows, ldb, dtype, out, rowptr, col, plan_d, ph, N, E, D, stream_v, 0);
+}
+
+// Multi-head SDDMM (sddmm_heads.hip): hcspmm_sddmm's checks, then heads column slices of D / heads in one launch; fp32 only.
+extern "C" int hcspmm_sddmm_heads(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
+                                  const int32_t* rowptr, const int32_t* col, const int32_t* plan_d, const hcspmm_plan_header* ph,
+                                  int64_t N, int64_t E, int D, void* stream_v, int heads) {
+  if (heads <= 0) return HCSPMM_EINVAL;
+  return sddmm_impl(A, lda, B, b_rows, ldb, dtype, out, rowptr, col, plan_d, ph, N, E, D, stream_v, heads);
 }
 
 namespace {

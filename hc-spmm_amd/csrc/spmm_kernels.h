@@ -95,6 +95,20 @@ hipError_t launch_plan_w_f16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_f16(const WWindowArgs& a, int vec, hipStream_t stream);
 hipError_t launch_plan_w_bf16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_bf16(const WWindowArgs& a, int vec, hipStream_t stream);
+// the multi-head weighted forms (spmm_weighted_heads.hip, hcspmm_forward_weighted_heads): values [heads][E], column c takes
+// head c / dh's; fp32 with vec 4 only, dh % 4 == 0, D % dh == 0
+struct WHPlanArgs {
+  WPlanArgs w;
+  long long E;  // entries per head slice of w.values
+  int dh;       // columns per head
+};
+struct WHWindowArgs {
+  WWindowArgs w;
+  long long E;
+  int dh;
+};
+hipError_t launch_plan_wh_f32(const WHPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_wh_f32(const WHWindowArgs& a, int vec, hipStream_t stream);
 // values[e] = 1/sqrt(deg(row e) * deg(col e)) (kind 0) or 1/deg(row e) (kind 1), deg = row length
 hipError_t launch_edge_norm(const int* rowptr, const int* col, int N, long long E, int kind, float* values, hipStream_t stream);
 
@@ -142,6 +156,9 @@ struct SddmmArgs {
 hipError_t launch_sddmm_f32(const SddmmArgs& a, int vec, hipStream_t stream);
 hipError_t launch_sddmm_f16(const SddmmArgs& a, int vec, hipStream_t stream);
 hipError_t launch_sddmm_bf16(const SddmmArgs& a, int vec, hipStream_t stream);
+// multi-head SDDMM (sddmm_heads.hip, hcspmm_sddmm_heads): out[h*E + e] = <A[row(e)][h*D : (h+1)*D], B[col(e)][h*D : (h+1)*D]>
+// for h < heads, a.D = columns per head; fp32, vec as pick_vec gives for one head's column slice
+hipError_t launch_sddmm_heads_f32(const SddmmArgs& a, int heads, int vec, hipStream_t stream);
 // per row r and head h, over the head-major [heads][E] arrays:
 //   forward  out = softmax(x) over the row's entries;  backward  out = x * (y - sum_row x * y)  (x = alpha, y = grad_alpha)
 struct SoftmaxArgs {

@@ -25,7 +25,7 @@ __all__ = [
     "backward_fixed32", "backward_fixed32_fused", "backward_final_fused", "backward_fixed64",
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
-    "gat_attention", "gat_attention_backward",
+    "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
@@ -496,6 +496,48 @@ def forward_weighted(X, values, row_pointers, column_index, blockPartition, edge
     return [Z]
 
 
+def _check_heads_width(D, heads, dtype):
+    # the multi-head kernels' limits (hcspmm.h hcspmm_forward_weighted_heads / hcspmm_sddmm_heads)
+    if dtype != torch.float32:
+        raise RuntimeError("the multi-head kernels take float32 features only, got %s" % (dtype,))
+    if heads < 1 or D % heads != 0 or (D // heads) % 4 != 0:
+        raise RuntimeError("the multi-head kernels need heads >= 1 and D = heads * Dh with Dh a multiple of 4: D = %d, heads = %d"
+                           % (D, heads))
+
+
+def forward_weighted_heads(X, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                           row_nzr, col_nzr):
+    """Multi-head edge-weighted aggregation -> [Z]: values [heads, E] (float32, head-major), X [rows, D] float32 with
+    D = heads * Dh, Dh % 4 == 0; Z[:, h*Dh:(h+1)*Dh] = A_{values[h]} X[:, h*Dh:(h+1)*Dh], all heads in one launch.  Each
+    head's columns are bit for bit forward_weighted(X, values[h]) at full width (hcspmm.h hcspmm_forward_weighted_heads)."""
+    L = lib()
+    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                             row_nzr, False, dtypes=tuple(_DTYPES))
+    _check_input(values, "values")
+    if values.dtype != torch.float32:
+        raise RuntimeError("values must be a float32 tensor")
+    if values.dim() != 2 or values.size(1) != E or values.size(0) < 1:
+        raise RuntimeError("values must be [heads, E] with E = %d, got %s" % (E, tuple(values.shape)))
+    if values.device != X.device:
+        raise RuntimeError("values must be on the device of the input")
+    heads = values.size(0)
+    _check_heads_width(D, heads, X.dtype)
+    Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(L.hcspmm_forward_weighted_heads(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
+                                              _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                              _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                              ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
+                                              _ptr(values if E else torch.zeros(1, device=X.device)), heads))
+    return [Z]
+
+
 _NORMS = {"sym": 0, "mean": 1}
 
 
@@ -559,6 +601,36 @@ def sddmm(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeTo
         check(lib().hcspmm_sddmm(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
                                  _ptr(row_pointers), _ptr(column_index), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
                                  ctypes.byref(h) if h is not None else None, N, E, D, stream))
+    return out
+
+
+def sddmm_heads(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                heads):
+    """Multi-head SDDMM -> float32 [heads, E]: out[h, e] = <A[row(e), h*Dh:(h+1)*Dh], B[column_index[e], h*Dh:(h+1)*Dh]>,
+    all heads in one launch (hcspmm.h hcspmm_sddmm_heads).  A [N, D] and B [b_rows, D] float32 views with unit inner stride,
+    D = heads * Dh, Dh % 4 == 0.  Each head is bit for bit sddmm on the column slices.  The gradient of
+    forward_weighted_heads with respect to its values is sddmm_heads(dZ, X)."""
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    _check_view(A, "A")
+    _check_view(B, "B", A.dtype)
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), A.size(1)
+    if A.size(0) != N:
+        raise RuntimeError("A has %d rows but the graph has %d nodes" % (A.size(0), N))
+    if B.size(1) != D:
+        raise RuntimeError("B has %d columns but A has %d" % (B.size(1), D))
+    if B.device != A.device:
+        raise RuntimeError("B must be on the device of A")
+    heads = int(heads)
+    _check_heads_width(D, heads, A.dtype)
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, B.size(0))
+    out = torch.empty((heads, E), dtype=torch.float32, device=A.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+    with _on_device(A.device):
+        check(lib().hcspmm_sddmm_heads(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
+                                       _ptr(row_pointers), _ptr(column_index),
+                                       _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                       ctypes.byref(h) if h is not None else None, N, E, D, stream, heads))
     return out
 
 

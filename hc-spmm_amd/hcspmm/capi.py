@@ -67,9 +67,12 @@ SYMBOLS = {
                                     _sz, _vp]),
     "hcspmm_forward_weighted": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
                                        _vp, _sz, _vp, _vp]),
+    "hcspmm_forward_weighted_heads": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
+                                             _int, _vp, _sz, _vp, _vp, _int]),
     "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "hcspmm_sddmm": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp]),
+    "hcspmm_sddmm_heads": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _int]),
     "hcspmm_edge_softmax": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_edge_softmax_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_gat_attention": (_int, [_vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp]),

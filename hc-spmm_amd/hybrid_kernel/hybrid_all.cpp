@@ -229,6 +229,71 @@ std::vector<torch::Tensor> spmm_forward_weighted(torch::Tensor input, torch::Ten
   return {output};
 }
 
+// multi-head limits of hcspmm_forward_weighted_heads / hcspmm_sddmm_heads
+void check_heads_width(int64_t D, int64_t heads, const torch::Tensor& t) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, "the multi-head kernels take float32 features only, got ", t.scalar_type());
+  TORCH_CHECK(heads >= 1 && D % heads == 0 && (D / heads) % 4 == 0,
+              "the multi-head kernels need heads >= 1 and D = heads * Dh with Dh a multiple of 4: D = ", D, ", heads = ", heads);
+}
+
+// Multi-head edge-weighted aggregation (hcspmm_forward_weighted_heads): values [heads, E], D = heads * Dh
+std::vector<torch::Tensor> spmm_forward_weighted_heads(torch::Tensor input, torch::Tensor values, torch::Tensor nodePointer,
+                                                       torch::Tensor edgeList, torch::Tensor blockPartition,
+                                                       torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                                       torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr) {
+  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  CHECK_INPUT(values);
+  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
+  TORCH_CHECK(values.dim() == 2 && values.size(1) == c.E && values.size(0) >= 1, "values must be [heads, E] with E = ", c.E,
+              ", got ", values.sizes());
+  TORCH_CHECK(values.device() == input.device(), "values must be on the device of the input");
+  const int64_t heads = values.size(0);
+  check_heads_width(c.D, heads, input);
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
+  auto vals = c.E > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_forward_weighted_heads(
+      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
+      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
+      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>(), (int)heads);
+  check_rc(rc, "forward_weighted_heads");
+  return {output};
+}
+
+// Multi-head SDDMM (hcspmm_sddmm_heads): float32 [heads, E], out[h][e] = <A[row(e)][h-th Dh slice], B[col(e)][same slice]>
+torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
+                               torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                               torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr, int64_t heads) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  CHECK_CUDA(A);
+  CHECK_CUDA(B);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  for (const torch::Tensor* t : {&A, &B})
+    TORCH_CHECK(feature_dtype(*t) >= 0 && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
+                t == &A ? "A" : "B", " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
+  TORCH_CHECK(B.scalar_type() == A.scalar_type(), "B must be a 2-D float32 / float16 / bfloat16 view with unit inner stride, of the "
+              "dtype of A");
+  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0);
+  TORCH_CHECK(A.size(0) == N, "A has ", A.size(0), " rows but the graph has ", N, " nodes");
+  TORCH_CHECK(B.size(1) == A.size(1), "B has ", B.size(1), " columns but A has ", A.size(1));
+  TORCH_CHECK(B.device() == A.device(), "B must be on the device of A");
+  check_heads_width(A.size(1), heads, A);
+  hcspmm_plan_header h;
+  const bool has_plan = lookup(row_nzr, nodePointer, edgeList, N, E, &h);
+  if (has_plan)
+    TORCH_CHECK(B.size(0) >= h.num_columns, "B has ", B.size(0), " rows but the plan gathers from ", h.num_columns);
+  auto out = torch::empty({heads, E}, A.options().dtype(torch::kFloat));
+  const c10::DeviceGuard guard(A.device());
+  check_rc(hcspmm_sddmm_heads(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
+                              E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList),
+                              has_plan ? iptr(row_nzr) : nullptr, has_plan ? &h : nullptr, N, E, (int)A.size(1),
+                              (void*)c10::hip::getCurrentHIPStream(A.device().index()).stream(), (int)heads),
+           "sddmm_heads");
+  return out;
+}
+
 // SDDMM (hcspmm_sddmm): out[e] = <A[row(e)], B[col(e)]>, A and B 2-D views with unit inner stride (column slices need no copy)
 torch::Tensor spmm_sddmm(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
                          torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
@@ -649,6 +714,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              "transpose_permutation");
     return perm.to(row_pointers.device(), torch::kLong);
   }, "perm with values[perm] = the values of A_w^T in A's CSR order (pattern-symmetric graphs)");
+  m.def("forward_weighted_heads", &spmm_forward_weighted_heads,
+        "multi-head edge-weighted aggregation [Z]: values [heads, E], head h weights columns h*Dh ... (h+1)*Dh - 1 (gfx950)");
+  m.def("sddmm_heads", &spmm_sddmm_heads,
+        "multi-head sampled dense-dense product: float32 [heads, E], one Dh-column slice per head (gfx950)");
   m.def("sddmm", &spmm_sddmm, "sampled dense-dense product on the stored entries: float32 [E], out[e] = <A[row(e)], B[col(e)]> (gfx950)");
   m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
   m.def("edge_softmax_backward", &edge_softmax_backward,

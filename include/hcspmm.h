@@ -29,7 +29,7 @@ extern "C" {
 /* 3 = the signatures below.  Entry points ADDED since 3 was introduced leave it unchanged (a consumer built against an older header keeps
  * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
  * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6); hcspmm_gat_attention,
- * hcspmm_gat_attention_backward (round 7).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -318,6 +318,23 @@ int hcspmm_forward_weighted(const void* X_d, int64_t x_rows, int64_t ldx, void* 
                             int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                             const float* values_d);
 
+/* Multi-head edge-weighted forward: hcspmm_forward_weighted for `heads` heads of Dh = embedding_dim / heads columns each,
+ * in one launch.  values_d is head-major fp32 [heads][E] (head h's values are the slice [h * E, (h + 1) * E)):
+ *   Z[r][h * Dh + j] = sum over e in row r  values[h * E + e] * X[column_index[e]][h * Dh + j]
+ * Columns [h * Dh, (h + 1) * Dh) of Z are bit for bit hcspmm_forward_weighted(X, values + h * E) on the same graph, plan and
+ * full width embedding_dim, restricted to those columns (equal up to the sign of a zero; values must be finite: a dense-tile
+ * window covering several heads adds the other heads' finite products with zero to each column).  So heads = 1 is
+ * hcspmm_forward_weighted, and values of 1 give hcspmm_forward_typed's bits.  One column-index load per entry serves every
+ * head.  fp32 features only: HCSPMM_DTYPE_F16 / BF16 are HCSPMM_EINVAL.  heads >= 1, embedding_dim % heads == 0 and
+ * Dh % 4 == 0, else HCSPMM_EINVAL; every other argument as for hcspmm_forward_weighted (NULL values is HCSPMM_EINVAL);
+ * all argument errors are reported before any device call.  Plan and preprocessing are those of the binary product. */
+int hcspmm_forward_weighted_heads(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype,
+                                  const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                                  const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                                  const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                                  int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
+                                  const float* values_d, int heads);
+
 /* Edge normalisations of a square graph, on the device (asynchronous on `stream`); deg(r) = stored entries of row r, so
  * self-loops count only when the graph stores them.  Rows of degree 0 own no entries.
  *   HCSPMM_NORM_SYM  : values[e] = 1 / sqrt(deg(r) * deg(c))  (GCN: D^-1/2 A D^-1/2)
@@ -352,6 +369,17 @@ int hcspmm_transpose_permutation(const int32_t* row_pointers_h, const int32_t* c
 int hcspmm_sddmm(const void* A_d, int64_t lda, const void* B_d, int64_t b_rows, int64_t ldb, int dtype, float* out_d,
                  const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* plan_d,
                  const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim, void* stream);
+
+/* Multi-head SDDMM: hcspmm_sddmm per head on the column slices of Dh = embedding_dim / heads columns, in one launch:
+ *   out_d[h * E + e] = <A[row(e)][h * Dh : (h + 1) * Dh], B[column_index[e]][h * Dh : (h + 1) * Dh]>
+ * head-major [heads][E].  Each head's result is bit for bit hcspmm_sddmm on the slice views A_d + h * Dh, B_d + h * Dh (same
+ * lda / ldb) at width Dh: same lanes, vector width, column order and butterfly.  One column-index load per entry serves
+ * every head; deterministic, no atomics.  fp32 only (F16 / BF16 are HCSPMM_EINVAL); heads >= 1, embedding_dim % heads == 0
+ * and Dh % 4 == 0; the plan / b_rows checks and the other argument checks of hcspmm_sddmm, all before any device call. */
+int hcspmm_sddmm_heads(const void* A_d, int64_t lda, const void* B_d, int64_t b_rows, int64_t ldb, int dtype, float* out_d,
+                       const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* plan_d,
+                       const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                       void* stream, int heads);
 
 /* Edge softmax over each row's stored entries, per head, on head-major fp32 arrays [heads][E] (head h is the contiguous
  * slice [h * E, (h + 1) * E), which hcspmm_forward_weighted takes as its values as is):
