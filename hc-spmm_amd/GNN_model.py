@@ -357,6 +357,35 @@ def gat_attention(s_dst, s_src, graph, negative_slope=0.2):
     return GATAttention.apply(s_dst, s_src, float(negative_slope), perm32, graph[0], graph[1])
 
 
+class ExtremumAggregate(torch.autograd.Function):
+    """Max or min of each row's neighbour features (HCSPMM.forward_max / forward_min, with the argmax) and its gradient
+    dX[j][d] = sum of dY[i][d] over the entries (i, j) that won (i, d) (HCSPMM.forward_extremum_backward: A^T walked on
+    the same plan, deterministic; perm32 = transpose_permutation_i32 of the graph)."""
+
+    @staticmethod
+    def forward(ctx, X, reduce, perm32, *graph):
+        fn = HCSPMM.forward_max if reduce == "max" else HCSPMM.forward_min
+        Z, arg = fn(X.contiguous(), *graph, True)
+        ctx.save_for_backward(arg, perm32, *graph)
+        ctx.mark_non_differentiable(arg)
+        return Z
+
+    @staticmethod
+    def backward(ctx, d_out):
+        arg, perm32, *graph = ctx.saved_tensors
+        d_x = HCSPMM.forward_extremum_backward(d_out.contiguous(), arg, perm32, *graph) if ctx.needs_input_grad[0] else None
+        return (d_x, None, None) + (None,) * N_GRAPH
+
+
+def extremum_aggregate(X, graph, reduce="max"):
+    """max / min over each row's neighbours with autograd for X (float32 [N, D]); graph = the eight graph tensors, whose
+    pattern must be symmetric (checked before any launch: the backward walks A^T).  Rows without entries give 0."""
+    if reduce not in ("max", "min"):
+        raise ValueError("reduce must be 'max' or 'min', got %r" % (reduce,))
+    perm32 = transpose_permutation_i32(graph[0], graph[1])
+    return ExtremumAggregate.apply(X, reduce, perm32, *graph)
+
+
 _EDGE_ROWS = {}  # (row_pointers pointer and size) -> (weak ref, row of every stored entry as int64)
 
 
@@ -475,3 +504,43 @@ class GATConv(torch.nn.Module):
         s = _Update.apply(h, a_blk)  # [N, 2 heads]: s_dst | s_src
         alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope)  # [heads, E]
         return edge_weighted_aggregate_heads(h, alpha, graph)
+
+
+class SAGEConv(torch.nn.Module):
+    """GraphSAGE layer:  out = X W_root + AGG(X) W_neigh, AGG over each row's neighbours:
+      "max" / "min"  extremum_aggregate (GraphSAGE-pool without the pre-MLP, PyG aggr="max" / "min");
+      "mean"         edge_weighted_aggregate with HCSPMM.edge_norm(..., "mean") values, computed once per graph.
+    Both products run on _Update (the library's update and weight-gradient kernels).  _Conv's call signature, so that Net
+    builds it; the aggregation is fixed by `aggr`, so edge_weight is refused.  The pattern must be symmetric."""
+
+    def __init__(self, input_dim, output_dim, fixed=0, aggr="max"):
+        super().__init__()
+        if aggr not in ("max", "min", "mean"):
+            raise ValueError("SAGEConv aggr must be 'max', 'min' or 'mean', got %r" % (aggr,))
+        self.fixed, self.aggr = fixed, aggr
+        self.weights_root = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self.weights_neigh = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self._mean = None  # (row_pointers, column_index, values) of the last graph
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.weights_root.size(1))
+        for p in (self.weights_root, self.weights_neigh):
+            p.data.uniform_(-stdv, stdv)
+
+    def _mean_values(self, row_pointers, column_index):
+        m = self._mean
+        if m is None or m[0] is not row_pointers or m[1] is not column_index:
+            self._mean = m = (row_pointers, column_index, HCSPMM.edge_norm(row_pointers, column_index, "mean"))
+        return m[2]
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("SAGEConv aggregates with its own `aggr`: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if self.aggr == "mean":
+            agg = edge_weighted_aggregate(X, self._mean_values(row_pointers, column_index), graph)
+        else:
+            agg = extremum_aggregate(X, graph, self.aggr)
+        return _Update.apply(X, self.weights_root) + _Update.apply(agg, self.weights_neigh)

@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GCNConv, GINConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GCNConv, GINConv, SAGEConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat", "sage"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -58,11 +58,15 @@ def parse_args(argv=None):
     # addition: attention heads of --model gat (GNN_model.GATConv: the heads' outputs are averaged)
     p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat)")
     # addition: the first and hidden GAT layers concatenate their heads (hidden / heads features each), the last averages
+    # addition: neighbour aggregation of --model sage (GNN_model.SAGEConv: out = X W_root + AGG(X) W_neigh)
+    p.add_argument("--aggr", type=str, default="max", choices=["max", "min", "mean"], help="aggregation of --model sage")
     p.add_argument("--gat-concat", action="store_true",
                    help="--model gat: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
     args = p.parse_args(argv)
     if args.model == "gat" and args.norm != "none":
         p.error("--norm does not apply to --model gat: its edge values are the attention weights")
+    if args.model == "sage" and args.norm != "none":
+        p.error("--norm does not apply to --model sage: its aggregation is --aggr")
     if args.heads < 1:
         p.error("--heads must be at least 1")
     if args.gat_concat and args.model != "gat":
@@ -149,6 +153,9 @@ def main(argv=None):
         return SAG(*graph).profile(dataset.x)
 
     conv_cls = {"gcn": GCNConv, "gin": GINConv}.get(args.model)
+    if args.model == "sage":
+        def conv_cls(input_dim, output_dim, fixed):
+            return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated

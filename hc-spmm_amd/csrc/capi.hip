@@ -359,6 +359,109 @@ extern "C" int hcspmm_forward_weighted_heads(const void* X, int64_t x_rows, int6
                       plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads);
 }
 
+namespace {
+// the plan fields of a hybrid launch (forward_impl's), for the extremum launches
+void fill_plan_args(hcspmm::PlanArgs& a, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int D) {
+  a = hcspmm::PlanArgs{};
+  a.plan = plan_d;
+  a.off_tasks = ph->off_tasks;
+  a.n_tasks = ph->n_tasks;
+  a.n_tiny = ph->n_tiny;
+  a.off_slice_table = ph->off_slice_table;
+  a.off_slice_tasks = ph->off_slice_tasks;
+  a.n_slices = ph->n_slices;
+  a.slice_xcd_tasks = ph->slice_xcd_tasks;
+  a.off_dense_index = ph->off_dense_index;
+  a.off_dense_pack = ph->off_dense_pack;
+  a.n_dense = ph->n_dense;
+  a.off_dense_compact = ph->off_dense_compact;
+  a.n_dense_compact = ph->n_dense_compact;
+  a.off_dense_compact2 = ph->off_dense_compact2;
+  a.n_dense_compact2 = ph->n_dense_compact2;
+  a.off_fixups = ph->off_fixups;
+  a.n_split_rows = ph->n_split_rows;
+  wide_choice(ph, D, HCSPMM_DTYPE_F32, &a.n_wide, &a.panel_cols);
+  a.N = (int)N;
+  a.D = D;
+}
+
+// backward = false: hcspmm_forward_extremum (src = X, dst = Z); true: its backward (src = grad_Z, dst = grad_X, square)
+int extremum_impl(bool backward, const float* src, int64_t src_rows, int64_t lds, float* dst, int64_t ldd, int dtype,
+                  const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
+                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d, const hcspmm_plan_header* ph,
+                  int64_t N, int64_t E, int D, void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out,
+                  const int32_t* arg_in, int64_t ldarg, const int32_t* perm) {
+  if (dtype != HCSPMM_DTYPE_F32 || (reduce != HCSPMM_REDUCE_MAX && reduce != HCSPMM_REDUCE_MIN)) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || D <= 0 || lds < D || ldd < D) return HCSPMM_EINVAL;
+  if ((backward || arg_out) && ldarg < D) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!src || !dst || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (backward && (!arg_in || (E > 0 && !perm))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::XArgs x{};
+  if (plan_d && ph) {
+    const int rc = hcspmm_plan_check(ph, N, E, 0);
+    if (rc != HCSPMM_OK) return rc;
+    if (src_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows the source does not have
+    const size_t part = hcspmm_workspace_bytes(ph, D);      // fp32 values (forward: positions behind them)
+    const size_t need = backward ? part : 2 * part;
+    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
+    fill_plan_args(x.p, plan_d, ph, N, D);
+    x.p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
+    x.ppos = (need && !backward) ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + part) : nullptr;
+    x.segment_len = ph->segment_len;
+  } else {
+    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
+    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
+    x.p.N = (int)N;
+    x.p.D = D;
+  }
+  x.p.X = src;
+  x.p.Z = dst;
+  x.p.ldx = (size_t)lds;
+  x.p.ldz = (size_t)ldd;
+  x.p.col = col;
+  x.rowptr = rowptr;
+  x.flip = reduce == HCSPMM_REDUCE_MIN ? 0x80000000u : 0u;
+  x.arg = arg_out;
+  x.garg = arg_in;
+  x.perm = perm;
+  x.ldarg = (size_t)ldarg;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, lds, ldd, src, dst, nullptr);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+  const hipError_t e = backward ? hcspmm::launch_extremum_backward_f32(x, vec, stream) : hcspmm::launch_extremum_f32(x, vec, stream);
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+}  // namespace
+
+extern "C" size_t hcspmm_extremum_workspace_bytes(const hcspmm_plan_header* ph, int D) {
+  return 2 * hcspmm_workspace_bytes(ph, D);
+}
+
+// Max / min aggregation (spmm_extremum.hip): the plan and checks of hcspmm_forward_weighted, fp32 only.
+extern "C" int hcspmm_forward_extremum(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                       const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                       const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                       const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                       void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out,
+                                       int64_t ldarg) {
+  return extremum_impl(false, reinterpret_cast<const float*>(X), x_rows, ldx, reinterpret_cast<float*>(Z), ldz, dtype, rowptr, col,
+                       blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes,
+                       stream_v, reduce, arg_out, nullptr, ldarg, nullptr);
+}
+
+extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg, const int32_t* arg, int64_t ldarg, float* grad_X,
+                                                int64_t ldgx, const int32_t* rowptr, const int32_t* col,
+                                                const int32_t* blockPartition, const int32_t* edgeToColumn,
+                                                const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
+                                                const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                                const int32_t* transpose_perm, void* workspace, size_t workspace_bytes,
+                                                void* stream_v) {
+  return extremum_impl(true, grad_Z, N, ldg, grad_X, ldgx, HCSPMM_DTYPE_F32, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
+                       hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, HCSPMM_REDUCE_MAX, nullptr, arg,
+                       ldarg, transpose_perm);
+}
+
 extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int kind,
                                        float* values_out, void* stream_v) {
   if (N < 0 || E < 0 || (kind != HCSPMM_NORM_SYM && kind != HCSPMM_NORM_MEAN)) return HCSPMM_EINVAL;

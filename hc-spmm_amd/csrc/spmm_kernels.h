@@ -193,5 +193,24 @@ struct GatArgs {
 hipError_t launch_gat_attention(const GatArgs& a, hipStream_t stream);
 hipError_t launch_gat_attention_backward(const GatArgs& a, hipStream_t stream);
 
+// Max / min aggregation and its backward (spmm_extremum.hip; include/hcspmm.h hcspmm_forward_extremum*), fp32.  p as for
+// launch_plan_f32 (forward: X, Z; backward: X = grad_Z, Z = grad_X, ldx = its row stride), or p.plan == nullptr for the
+// plan-free launch (then only X, Z, col, ldx, ldz, N, D are read).  Forward: partial = the fp32 values of the split rows'
+// partial slots, ppos = their positions (n_partials x D each); backward: partial = fp32 sums of the split rows.
+struct XArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  unsigned flip;      // forward: 0 = max, 0x80000000 = min (max of the negated values)
+  int* arg;           // forward: [N][ldarg] winning entries, or nullptr
+  int* ppos;          // forward: positions of the partial slots
+  const int* garg;    // backward: the forward's arg, [N][ldarg]
+  const int* perm;    // backward: [E] hcspmm_transpose_permutation
+  size_t ldarg;
+};
+// vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
+hipError_t launch_extremum_f32(const XArgs& a, int vec, hipStream_t stream);
+hipError_t launch_extremum_backward_f32(const XArgs& a, int vec, hipStream_t stream);
+
 
 }  // namespace hcspmm

@@ -26,6 +26,7 @@ __all__ = [
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
+    "forward_max", "forward_min", "forward_extremum_backward",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
@@ -536,6 +537,89 @@ def forward_weighted_heads(X, values, row_pointers, column_index, blockPartition
                                               ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
                                               _ptr(values if E else torch.zeros(1, device=X.device)), heads))
     return [Z]
+
+
+def _extremum(X, graph, reduce, return_arg):
+    L = lib()
+    row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr = graph
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
+                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
+        _check_input(t, n)
+    if not X.is_cuda:
+        raise RuntimeError("input must be a CUDA tensor")
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)")
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), X.size(1)
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0))
+    Z = torch.empty((N, D), dtype=torch.float32, device=X.device)
+    arg = torch.empty((N, D), dtype=torch.int32, device=X.device) if return_arg else None
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_extremum_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(L.hcspmm_forward_extremum(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, 0, _ptr(row_pointers), _ptr(column_index),
+                                        _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow), _ptr(hybrid_type),
+                                        _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                        ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream, reduce,
+                                        _ptr(arg) if arg is not None else ctypes.c_void_p(0), D))
+    return [Z, arg] if return_arg else [Z]
+
+
+def forward_max(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                return_arg=True):
+    """Max over each row's neighbours -> [Z, arg] ([Z] with return_arg=False): Z[r][d] = max of X[col(e)][d] over the
+    entries e of row r, arg[r][d] = the winning e (int32).  Ties go to the lowest e, NaN wins, rows without entries give 0
+    and -1 (hcspmm.h hcspmm_forward_extremum).  X: float32 [rows, D] view with unit inner stride (rows >= the columns the
+    graph refers to)."""
+    return _extremum(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr),
+                     0, return_arg)
+
+
+def forward_min(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                return_arg=True):
+    """Min over each row's neighbours: forward_max's contract with min (NaN still wins)."""
+    return _extremum(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr),
+                     1, return_arg)
+
+
+def forward_extremum_backward(grad_Z, arg, perm, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow,
+                              hybrid_type, row_nzr, col_nzr):
+    """Backward of forward_max / forward_min on a square, pattern-symmetric graph -> grad_X [N, D]:
+    grad_X[j][d] = sum of grad_Z[i][d] over the entries e = (i, j) with arg[i][d] == e.  perm: the int32 transpose
+    permutation (transpose_permutation(...).int()).  Deterministic, no atomics (hcspmm.h hcspmm_forward_extremum_backward)."""
+    L = lib()
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
+                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow"), (grad_Z, "grad_Z"), (arg, "arg"), (perm, "perm")):
+        _check_input(t, n)
+    N, E = row_pointers.size(0) - 1, column_index.size(0)
+    if grad_Z.dtype != torch.float32 or grad_Z.dim() != 2 or grad_Z.size(0) != N:
+        raise RuntimeError("grad_Z must be a float32 [num_nodes, D] tensor")
+    D = grad_Z.size(1)
+    if arg.dtype != torch.int32 or tuple(arg.shape) != (N, D):
+        raise RuntimeError("arg must be the int32 [num_nodes, D] argmax of the forward")
+    if perm.dtype != torch.int32 or perm.dim() != 1 or perm.numel() != E:
+        raise RuntimeError("perm must be an int32 [E] tensor with E = %d, got %s %s" % (E, perm.dtype, tuple(perm.shape)))
+    for t, n in ((arg, "arg"), (perm, "perm")):
+        if t.device != grad_Z.device:
+            raise RuntimeError("%s must be on the device of grad_Z" % n)
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, N)
+    grad_X = torch.empty((N, D), dtype=torch.float32, device=grad_Z.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=grad_Z.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(grad_Z.device).cuda_stream)
+    with _on_device(grad_Z.device):
+        check(L.hcspmm_forward_extremum_backward(_ptr(grad_Z), D, _ptr(arg), D, _ptr(grad_X), D, _ptr(row_pointers),
+                                                 _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                                 _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                                 ctypes.byref(h) if h is not None else None, N, E, D, _ptr(perm), _ptr(ws),
+                                                 ws_bytes, stream))
+    return grad_X
 
 
 _NORMS = {"sym": 0, "mean": 1}

@@ -69,6 +69,11 @@ SYMBOLS = {
                                        _vp, _sz, _vp, _vp]),
     "hcspmm_forward_weighted_heads": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
                                              _int, _vp, _sz, _vp, _vp, _int]),
+    "hcspmm_extremum_workspace_bytes": (_sz, [_hp, _int]),
+    "hcspmm_forward_extremum": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
+                                       _vp, _sz, _vp, _int, _vp, _i64]),
+    "hcspmm_forward_extremum_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
+                                                _int, _vp, _vp, _sz, _vp]),
     "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "hcspmm_sddmm": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp]),

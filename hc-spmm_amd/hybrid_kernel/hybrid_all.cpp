@@ -261,6 +261,63 @@ std::vector<torch::Tensor> spmm_forward_weighted_heads(torch::Tensor input, torc
   return {output};
 }
 
+// Max / min aggregation (hcspmm_forward_extremum): float32 X, a strided view with unit inner stride whose rows the column ids
+// index -> {Z, arg} ({Z} without arg)
+std::vector<torch::Tensor> spmm_forward_extremum(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                 torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                                 torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
+                                                 bool return_arg, int reduce) {
+  CHECK_CUDA(input);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
+              "input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)");
+  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, true, true);
+  if (c.has_plan) {  // values and positions of the split rows' partial slots
+    const size_t need = hcspmm_extremum_workspace_bytes(&c.header, c.D);
+    if (need) c.workspace = torch::empty({(int64_t)(need / 4)}, input.options());
+  }
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
+  torch::Tensor arg;
+  if (return_arg) arg = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kInt));
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_forward_extremum(
+      input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, HCSPMM_DTYPE_F32, iptr(nodePointer), iptr(edgeList),
+      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
+      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, reduce, return_arg ? mptr(arg) : nullptr, c.D);
+  check_rc(rc, reduce == HCSPMM_REDUCE_MAX ? "forward_max" : "forward_min");
+  if (return_arg) return {output, arg};
+  return {output};
+}
+
+// Backward of forward_max / forward_min (hcspmm_forward_extremum_backward): square, pattern-symmetric graph, perm int32
+torch::Tensor spmm_forward_extremum_backward(torch::Tensor grad_Z, torch::Tensor arg, torch::Tensor perm, torch::Tensor nodePointer,
+                                             torch::Tensor edgeList, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                             torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                                             torch::Tensor col_nzr) {
+  CHECK_INPUT(grad_Z);
+  CHECK_INPUT(arg);
+  CHECK_INPUT(perm);
+  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0);
+  TORCH_CHECK(grad_Z.scalar_type() == torch::kFloat && grad_Z.dim() == 2 && grad_Z.size(0) == N,
+              "grad_Z must be a float32 [num_nodes, D] tensor");
+  const int64_t D = grad_Z.size(1);
+  TORCH_CHECK(arg.scalar_type() == torch::kInt && arg.dim() == 2 && arg.size(0) == N && arg.size(1) == D,
+              "arg must be the int32 [num_nodes, D] argmax of the forward");
+  TORCH_CHECK(perm.scalar_type() == torch::kInt && perm.dim() == 1 && perm.numel() == E, "perm must be an int32 [E] tensor with E = ",
+              E, ", got ", perm.scalar_type(), " ", perm.sizes());
+  TORCH_CHECK(arg.device() == grad_Z.device() && perm.device() == grad_Z.device(), "arg and perm must be on the device of grad_Z");
+  Call c = prepare(grad_Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr);
+  auto grad_X = torch::empty({N, D}, grad_Z.options());
+  const c10::DeviceGuard guard(grad_Z.device());
+  const int rc = hcspmm_forward_extremum_backward(
+      grad_Z.data_ptr<float>(), D, iptr(arg), D, grad_X.data_ptr<float>(), D, iptr(nodePointer), iptr(edgeList), iptr(blockPartition),
+      iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr, c.has_plan ? &c.header : nullptr,
+      c.N, c.E, c.D, iptr(perm), c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  check_rc(rc, "forward_extremum_backward");
+  return grad_X;
+}
+
 // Multi-head SDDMM (hcspmm_sddmm_heads): float32 [heads, E], out[h][e] = <A[row(e)][h-th Dh slice], B[col(e)][same slice]>
 torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
                                torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
@@ -718,6 +775,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-head edge-weighted aggregation [Z]: values [heads, E], head h weights columns h*Dh ... (h+1)*Dh - 1 (gfx950)");
   m.def("sddmm_heads", &spmm_sddmm_heads,
         "multi-head sampled dense-dense product: float32 [heads, E], one Dh-column slice per head (gfx950)");
+  m.def("forward_max", [](torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
+                          torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                          torch::Tensor col_nzr, bool return_arg) {
+    return spmm_forward_extremum(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                                 return_arg, HCSPMM_REDUCE_MAX);
+  }, "max over each row's neighbours -> [Z, arg] ([Z] with return_arg=False); ties to the lowest entry, NaN wins (gfx950)",
+        pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
+        pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
+        pybind11::arg("col_nzr"), pybind11::arg("return_arg") = true);
+  m.def("forward_min", [](torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
+                          torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                          torch::Tensor col_nzr, bool return_arg) {
+    return spmm_forward_extremum(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                                 return_arg, HCSPMM_REDUCE_MIN);
+  }, "min over each row's neighbours -> [Z, arg] ([Z] with return_arg=False); ties to the lowest entry, NaN wins (gfx950)",
+        pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
+        pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
+        pybind11::arg("col_nzr"), pybind11::arg("return_arg") = true);
+  m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
+        "backward of forward_max / forward_min (square, pattern-symmetric graph; perm = int32 transpose_permutation) -> grad_X (gfx950)");
   m.def("sddmm", &spmm_sddmm, "sampled dense-dense product on the stored entries: float32 [E], out[e] = <A[row(e)], B[col(e)]> (gfx950)");
   m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
   m.def("edge_softmax_backward", &edge_softmax_backward,

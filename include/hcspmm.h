@@ -29,7 +29,8 @@ extern "C" {
 /* 3 = the signatures below.  Entry points ADDED since 3 was introduced leave it unchanged (a consumer built against an older header keeps
  * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
  * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6); hcspmm_gat_attention,
- * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8); hcspmm_extremum_workspace_bytes,
+ * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -334,6 +335,52 @@ int hcspmm_forward_weighted_heads(const void* X_d, int64_t x_rows, int64_t ldx, 
                                   const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                                   int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                                   const float* values_d, int heads);
+
+/* ------------------------------------------------------------------------------------------
+ * Max / min neighbour aggregation with its argmax (GraphSAGE-pool, GIN-max, PNA; PyG aggr = "max" / "min"):
+ *   Z[r][d]   = max (HCSPMM_REDUCE_MAX) or min (HCSPMM_REDUCE_MIN) over e in [row_pointers[r], row_pointers[r+1]) of
+ *               X[column_index[e]][d]
+ *   arg[r][d] = the CSR position e of the winning entry
+ * The winner is exact and does not depend on how a row is split (lanes, wide tasks, column slices, segments, panels,
+ * plan-free): ties go to the lowest e (-0.0 and +0.0 compare equal, so the earlier entry's bits are the output), a NaN
+ * beats every number for max and min alike (torch's amax / amin) and among NaNs the lowest e wins.  Rows without
+ * entries get Z = +0.0 and arg = -1.  Z holds the winning entry's own bits.
+ * Arguments of hcspmm_forward_weighted without values_d (strided X / Z, x_rows, rectangular blocks, with a plan or
+ * plan-free), plus
+ *   reduce       HCSPMM_REDUCE_MAX or HCSPMM_REDUCE_MIN
+ *   arg_out_d    int32 [num_nodes][ldarg], or NULL: no positions are stored (inference)
+ *   ldarg        row stride of arg_out_d in elements (>= embedding_dim when arg_out_d is set)
+ *   workspace_d  >= hcspmm_extremum_workspace_bytes() (values and positions of split rows' partial slots)
+ * fp32 only: HCSPMM_DTYPE_F16 / BF16, a bad reduce, short strides and the other argument errors of
+ * hcspmm_forward_weighted are HCSPMM_EINVAL before any device call.  MFMA takes no maximum: dense-tile windows are served
+ * from CSR by the sparse-row gather.  Separate kernels (spmm_extremum.hip) on the binary product's plan.
+ * ---------------------------------------------------------------------------------------- */
+#define HCSPMM_REDUCE_MAX 0
+#define HCSPMM_REDUCE_MIN 1
+size_t hcspmm_extremum_workspace_bytes(const hcspmm_plan_header* header_h, int embedding_dim); /* 2 x hcspmm_workspace_bytes */
+int hcspmm_forward_extremum(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype,
+                            const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                            const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                            const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                            int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
+                            int reduce, int32_t* arg_out_d, int64_t ldarg);
+
+/* Backward of hcspmm_forward_extremum on a square, pattern-symmetric graph:
+ *   grad_X[j][d] = sum of grad_Z[i][d] over the entries e = (i, j) with arg[i][d] == e
+ * computed by walking A^T -- A's own pattern: row j's entry e_t has i = column_index[e_t] and e = transpose_perm[e_t]
+ * (hcspmm_transpose_permutation) -- on the forward's plan and schedule, so hubs stay balanced.  Each (j, d) is summed in
+ * a fixed order (CSR order, the wide tasks' shuffle tree, split rows through the fp32 fix-up pass and workspace), with
+ * no atomics: two calls give the same bits.  Columns no entry won get +0.0.  grad_Z_d, arg_d and grad_X_out_d are
+ * [num_nodes] rows of ldg / ldarg / ldgx elements (each >= embedding_dim); arg_d is the forward's arg_out_d.
+ * workspace_d >= hcspmm_workspace_bytes() (hcspmm_extremum_workspace_bytes also serves).  Argument errors as
+ * hcspmm_forward_extremum, a NULL arg_d or transpose_perm_d (E > 0) included.  Asynchronous on `stream`. */
+int hcspmm_forward_extremum_backward(const float* grad_Z_d, int64_t ldg, const int32_t* arg_d, int64_t ldarg,
+                                     float* grad_X_out_d, int64_t ldgx, const int32_t* row_pointers_d,
+                                     const int32_t* column_index_d, const int32_t* blockPartition_d,
+                                     const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                                     const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                                     int64_t num_edges, int embedding_dim, const int32_t* transpose_perm_d, void* workspace_d,
+                                     size_t workspace_bytes, void* stream);
 
 /* Edge normalisations of a square graph, on the device (asynchronous on `stream`); deg(r) = stored entries of row r, so
  * self-loops count only when the graph stores them.  Rows of degree 0 own no entries.
