@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the hybrid SpMM hot path (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dim D] [--frontend ctypes|extension]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path, Z = A*X, over one synthetic batch (graph + embedding matrix)
 already resident in HBM.  N = 1 runs BASELINE.json config 3, "Reddit-scale": 233 000 nodes /
@@ -15,19 +15,26 @@ step the path has.  `--workload products | powerlaw16m | c5` are the STRONG-scal
 configs 4 and 5: the same full graph (2.45 M / 62 M, 16 M / 256 M) at every N, its rows split over the ranks
 in nnz-balanced, window-aligned blocks.
 
-Prints ONE JSON line on rank 0 (contract in the task description).  At N = 1 the same line carries
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run does only what that line's headline
+needs: it generates the graph, preprocesses, warms up, times the steps, writes --dump-outputs and prints the line, whose
+`roofline` takes the kernel time from the HIP events of the timed steps and traffic from the recorded table under
+profiles/ (if it matches the kernel sources).  Everything else is measured with `--full` only.  At N = 1 `--full` adds
   * `roofline`: live HIP-event kernel time, and -- measured by THIS run -- the bytes that crossed the fabric
     per launch: before the process touches the GPU it runs itself under `rocprofv3 --pmc` (FETCH_SIZE,
     WRITE_SIZE, TCC hit/miss: separate passes, as MI355X_MICROARCH.md prescribes) on the same graph and reads
     the counters back.  `frac` is that traffic / time / 8 TB/s (<= 1 by construction); the algorithmic and
     compulsory figures stand beside it.  If the profiler is unavailable the recorded figure under profiles/
-    is used and labelled with its source; failing that, the compulsory-bytes fraction.
+    is used and labelled with its source; failing that, the compulsory-bytes fraction.  `roofline.l2` adds the
+    all-hit floor: the same rows with their column ids folded, timed in a run of their own;
   * `sweep`: the other BASELINE points timed in the same process -- Reddit-scale at dim 32 and 256, the
     Cora-scale config 2, one GPU's share of config 4 (dim 256) and one GPU's share of config 5 as SURVEY.md 8(d)
     defines it (planted <= 24-column groups over 16 M columns: most windows on the dense-tile / MFMA path), plus an
     RD-sized low-degree graph (the paper's Table II) and the all-dense MFMA-utilisation probe -- each
     with ITS counters from the same child passes (one rocprofv3 run per counter set covers every workload);
+  * `fused`, `frontends`, `loi`: the fused aggregate+update operator, the headline through the other front-end, and the
+    LOI reorder x classifier cases (see their functions);
   * `cpu_baseline`: torch.sparse.mm on the box's host cores (threads stated), the oracle port nested beside it.
+`--no-sweep`, `--no-pmc`, `--no-loi` and `--no-cpu-baseline` leave parts of `--full` out.
 `--dump-outputs DIR` also writes what the last timed step computed to DIR (dump_outputs); the graphs and features are
 seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -428,9 +435,10 @@ def dump_outputs(out_dir, Z_pm):
 
 
 def run_case(fe, dev, workload, D, rp, col, n_local, world, rank, vworld, steps, warmup, dtype_name="f32", rule=0,
-             no_plan=False, n_gather_panels=0, dist=None, prep_runs=3, keep_op=False, dump_dir=None):
+             no_plan=False, n_gather_panels=0, dist=None, prep_runs=3, keep_op=False, dump_dir=None, hip_graph=True):
     """Preprocess + `steps` timed steps of one workload on this rank; returns the measurements (no printing).
-    dump_dir: write what the last timed step computed there (dump_outputs)."""
+    dump_dir: write what the last timed step computed there (dump_outputs).  hip_graph: on a launch-bound workload, also
+    time the step replayed from a HIP graph (hip_graph_ms_per_step)."""
     import torch
     from hcspmm.sharded import ShardedGraph, ShardedSpMM
     E = int(len(col))
@@ -495,7 +503,7 @@ def run_case(fe, dev, workload, D, rp, col, n_local, world, rank, vworld, steps,
         dump_outputs(dump_dir, op.Z_pm)
     kern_ms = float(np.sum([s.elapsed_time(e) for s, e in ev_pairs])) / steps if ev_pairs else float("nan")
     graph_ms = None
-    if world == 1 and E <= 2_000_000:
+    if hip_graph and world == 1 and E <= 2_000_000:
         # a launch-bound workload (Cora-scale: the kernel is a few microseconds, a Python call several times that): the
         # same steps captured in a HIP graph -- the operator neither synchronises nor allocates -- and replayed
         try:
@@ -658,10 +666,14 @@ def main():
     ap.add_argument("--frontend", default="extension", choices=["ctypes", "extension"],
                     help="Python front-end over the C ABI: the torch extension HCSPMM (the reference's boundary, hybrid_all.cpp:500-525; default) "
                          "or the ctypes glue; the line's `frontends` block times both")
-    ap.add_argument("--no-loi", action="store_true", help="skip the `loi` block (community-structured graph: reorder x classifier)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="headline only (no dim 32 / 256, config 2 / 4 / 5 entries)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (traffic then comes from profiles/ or is null)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else at N = 1: rocprofv3 counter passes, the L2 all-hit floor, "
+                         "`sweep`, `fused`, `frontends`, `loi` and `cpu_baseline` (a plain run times the headline only)")
+    ap.add_argument("--no-loi", action="store_true", help="with --full: skip the `loi` block (community-structured graph: reorder x classifier)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: headline only (no dim 32 / 256, config 2 / 4 / 5 entries, "
+                                                            "all-hit floor, `fused`, `frontends`, `loi`)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes (traffic then comes from profiles/ or is null)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16", "bf16"],
                     help="feature element type; f32 is the reference's (and BASELINE's) -- the 16-bit variants are the paper's Table VII extension")
     ap.add_argument("--rule", type=int, default=3, help="window classifier (hcspmm.h): 3 = MI355X refit, width-agnostic (the library's default), 4 = MI355X refit for "
@@ -715,10 +727,12 @@ def main():
     # ---- the graphs (host, numpy): made before anything touches the GPU so that the counter passes share them
     cache_dir = args.graph_cache
     own_cache = False
-    do_sweep = world == 1 and not args.no_sweep and not strong and not args.pmc_child
+    # a plain run measures the headline alone; --full adds everything else (the counter passes' children run plain)
+    extras = args.full and world == 1 and not args.pmc_child
+    do_sweep = extras and not args.no_sweep and not strong
     # (a strong-scaling graph on one GPU gets its counter passes too, up to 100 M entries: beyond that the passes' second copy
     # of the graph on the host and their run time are not worth a `traffic` figure)
-    do_pmc = world == 1 and not args.pmc_child and not args.no_pmc and not (strong and STRONG_WORKLOADS[args.workload][1] // max(1, args.strong_scale) > 100_000_000)
+    do_pmc = extras and not args.no_pmc and not (strong and STRONG_WORKLOADS[args.workload][1] // max(1, args.strong_scale) > 100_000_000)
     if do_pmc and not cache_dir:
         cache_dir = tempfile.mkdtemp(prefix="hcspmm_bench_")
         own_cache = True
@@ -810,7 +824,7 @@ def main():
             torch.cuda.empty_cache()
         return
     case = run_case(fe, dev, args.workload, D, rp, col, n_local, world, rank, vworld, args.steps, args.warmup, args.dtype,
-                    args.rule, args.no_plan, n_gather_panels, dist, dump_dir=args.dump_outputs if rank == 0 else None)
+                    args.rule, args.no_plan, n_gather_panels, dist, dump_dir=args.dump_outputs if rank == 0 else None, hip_graph=False)
     elapsed, E, header = case["elapsed"], case["E"], case["header"]
 
     red_dev = torch.device("cpu") if rehearsal else dev
@@ -838,7 +852,7 @@ def main():
                 source = "recorded: %s (builder rocprofv3 run, kernel_src_sha %s)" % (rec.get("source"), rec.get("kernel_src_sha"))
                 extra = {"l2_hit_rate": rec.get("l2_hit_rate")}
         all_hit_ms = None
-        if world == 1 and not strong and not args.no_sweep and not args.no_plan and len(col) <= 64_000_000:
+        if extras and not strong and not args.no_sweep and not args.no_plan and len(col) <= 64_000_000:
             try:  # the L2 gather floor of this degree sequence (a few seconds: one sort on the host, 20 steps)
                 floor = run_case(fe, dev, args.workload, D, rp, fold_columns(rp, col), n_local, 1, 0, vworld, 20, 5, args.dtype, 2,
                                  False, 0, None, prep_runs=1)
@@ -895,11 +909,11 @@ def main():
             out["sweep"] = sweep(fe, dev, args, sweep_plan, graph_of, pmc)
         if sweep_plan and any(w == "rd_like" for w, _ in sweep_plan):
             out["fused"] = fused_block(dev, graph_of)
-        if world == 1 and not strong and not args.no_sweep:
+        if extras and not strong and not args.no_sweep:
             out["frontends"] = frontends_block(fe, dev, args, rp, col, n_local, vworld, D, ms_per_step, case["kernel_ms"])
         if do_loi:
             out["loi"] = loi_block(fe, dev, args, graph_of, pmc, loi_info)
-        if world == 1 and not args.no_cpu_baseline and not strong:
+        if extras and not args.no_cpu_baseline and not strong:
             Xh = torch.randn(case["x_rows"], D, generator=torch.Generator().manual_seed(1234)).numpy()
             out["cpu_baseline"] = cpu_baseline(rp, col, Xh, D, case["x_rows"])
         print(json.dumps(out))

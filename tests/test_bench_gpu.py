@@ -52,6 +52,19 @@ def test_more_ranks_than_gpus_is_refused_with_the_count():
     assert "needs %d visible GPUs, found %d" % (n + 1, n) in r.stderr
 
 
+def test_plain_run_times_the_headline_alone_and_full_adds_the_rest():
+    """A plain run prints the headline line with nothing measured beside it; --full (here without the counter passes and the
+    sweep, which bring the other graphs) adds the CPU baseline to the same line."""
+    extra = ("sweep", "fused", "frontends", "loi", "cpu_baseline")
+    r, plain = _bench(["--workload", "cora", "--steps", "3", "--warmup", "1"])
+    assert r.returncode == 0 and plain is not None, r.stderr[-2000:]
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 3 and plain["roofline"]["kernel_ms"] > 0
+    assert not [k for k in extra if k in plain] and "all_hit_kernel_ms" not in plain["roofline"].get("l2", {})
+    r, full = _bench(["--workload", "cora", "--steps", "3", "--warmup", "1", "--full", "--no-pmc", "--no-sweep"])
+    assert r.returncode == 0 and full is not None, r.stderr[-2000:]
+    assert full["cpu_baseline"]["value"] > 0 and full["metric"] == plain["metric"]
+
+
 def test_dumped_outputs_are_the_product_of_the_seeded_inputs(tmp_path):
     """--dump-outputs on the Cora-scale workload (Z = 10 000 x 32, written whole): z.npy is A*X within the oracle's bar, A the
     seeded graph bench.py generates and X its seeded features (torch.manual_seed(1234), normal_ over the [1, rows, 32] buffer)."""

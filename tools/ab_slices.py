@@ -1,6 +1,6 @@
 """A/B of the XCD-affine column slices (include/hcspmm.h n_slices) on one GPU: the same graph and X,
 plans built with different (slice_threshold, n_slices, segment_len), each checked against the unsliced launch and timed
-with HIP events.  L2 hit rate / fabric traffic of a chosen variant: bench.py under HCSPMM_SLICE_THRESHOLD / HCSPMM_SLICES
+with HIP events.  L2 hit rate / fabric traffic of a chosen variant: bench.py --full under HCSPMM_SLICE_THRESHOLD / HCSPMM_SLICES
 (its counter passes inherit the environment).
 
   python tools/ab_slices.py [--workloads reddit:128,reddit:32,reddit:256,products_share:256,c5_share:128]
