@@ -357,6 +357,38 @@ def gat_attention(s_dst, s_src, graph, negative_slope=0.2):
     return GATAttention.apply(s_dst, s_src, float(negative_slope), perm32, graph[0], graph[1])
 
 
+class GATv2Scores(torch.autograd.Function):
+    """GATv2 attention logits [heads, E]: l[h, e] = sum_k att[h, k] * LeakyReLU(H_dst[row(e), h*Dh + k] + H_src[col(e), h*Dh + k])
+    from node features H_dst, H_src [N, heads * Dh] (float32 views with unit inner stride: the halves of one projection need
+    no copy) and att [heads, Dh] (HCSPMM.gatv2_scores, one launch), with the gradients of all three
+    (HCSPMM.gatv2_scores_backward, three launches; perm32 = transpose_permutation_i32 of the graph).  No [E, D] tensor in
+    either pass."""
+
+    @staticmethod
+    def forward(ctx, H_dst, H_src, att, negative_slope, perm32, row_pointers, column_index):
+        att = att.contiguous()
+        logits = HCSPMM.gatv2_scores(H_dst, H_src, att, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(H_dst, H_src, att, perm32, row_pointers, column_index)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        H_dst, H_src, att, perm32, row_pointers, column_index = ctx.saved_tensors
+        d_dst, d_src, d_att = HCSPMM.gatv2_scores_backward(d_logits.contiguous(), H_dst, H_src, att, row_pointers, column_index,
+                                                           perm32, ctx.negative_slope)
+        return d_dst, d_src, d_att, None, None, None, None
+
+
+def gatv2_attention(H_dst, H_src, att, graph, negative_slope=0.2):
+    """GATv2 attention weights alpha [heads, E] = edge softmax of GATv2Scores' logits, with autograd for H_dst, H_src and att;
+    graph = the eight graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over
+    A^T)."""
+    perm32 = transpose_permutation_i32(graph[0], graph[1])
+    logits = GATv2Scores.apply(H_dst, H_src, att, float(negative_slope), perm32, graph[0], graph[1])
+    return EdgeSoftmax.apply(logits, graph[0])
+
+
 class ExtremumAggregate(torch.autograd.Function):
     """Max or min of each row's neighbour features (HCSPMM.forward_max / forward_min, with the argmax) and its gradient
     dX[j][d] = sum of dY[i][d] over the entries (i, j) that won (i, d) (HCSPMM.forward_extremum_backward: A^T walked on
@@ -504,6 +536,54 @@ class GATConv(torch.nn.Module):
         s = _Update.apply(h, a_blk)  # [N, 2 heads]: s_dst | s_src
         alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope)  # [heads, E]
         return edge_weighted_aggregate_heads(h, alpha, graph)
+
+
+class GATv2Conv(torch.nn.Module):
+    """GATv2 layer (Brody et al., "How attentive are graph attention networks?"): the non-linearity sits inside the score,
+        [H_src | H_dst] = X [W_src | W_dst]                  (one update, _Update; [N, 2 * heads * output_dim])
+        l_k[e] = <att_k, LeakyReLU(H_dst_k[row(e)] + H_src_k[col(e)])>   (row = destination, col = source)
+        alpha_k = softmax of l_k over each row's entries;   out_k = A_alpha_k H_src_k
+    through gatv2_attention on the two halves of the projection (views, no copy) and one multi-head aggregation
+    (edge_weighted_aggregate_heads).  concat=True returns the heads side by side [N, heads * output_dim], otherwise their
+    mean [N, output_dim].  share_weights=True uses one projection for both roles (H_dst = H_src, [N, heads * output_dim]).
+    No per-entry torch op and no [E, D] tensor in either pass.  The kernels need output_dim % 4 == 0.  _Conv's call
+    signature, so that Net builds it; the attention weights are the edge values, so edge_weight is refused.  The pattern must
+    be symmetric."""
+
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, share_weights=False):
+        super().__init__()
+        self.fixed, self.heads, self.negative_slope = fixed, int(heads), float(negative_slope)
+        self.concat, self.share_weights, self.output_dim = bool(concat), bool(share_weights), int(output_dim)
+        if self.heads < 1:
+            raise ValueError("GATv2Conv needs heads >= 1, got %d" % self.heads)
+        if output_dim < 4 or output_dim % 4 != 0:
+            raise ValueError("GATv2Conv needs output_dim (the width of one head) to be a multiple of 4, got %d" % output_dim)
+        width = self.heads * self.output_dim
+        # column block 0 = W_src, block 1 = W_dst (absent with share_weights); within a block, head k's columns are contiguous
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, width if self.share_weights else 2 * width))
+        self.att = torch.nn.Parameter(torch.empty(self.heads, self.output_dim))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.output_dim)
+        for p in (self.weights, self.att):
+            p.data.uniform_(-stdv, stdv)
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("GATv2Conv computes its edge values from the features: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        width = self.heads * self.output_dim
+        h = _Update.apply(X, self.weights)
+        h_src = h[:, :width]
+        h_dst = h_src if self.share_weights else h[:, width:]
+        alpha = gatv2_attention(h_dst, h_src, self.att, graph, self.negative_slope)  # [heads, E]
+        out = edge_weighted_aggregate_heads(h_src, alpha, graph)  # [N, heads * output_dim]
+        if self.concat or self.heads == 1:
+            return out
+        return out.view(out.size(0), self.heads, self.output_dim).mean(1)
 
 
 class SAGEConv(torch.nn.Module):

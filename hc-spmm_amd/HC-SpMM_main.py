@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GCN / GIN / GAT training driver and single-kernel profiler over the HCSPMM operators -- counterpart
+"""GCN / GIN / GAT / GATv2 / SAGE training driver and single-kernel profiler over the HCSPMM operators -- counterpart
 of the reference's HC-SpMM_main.py (same eight flags, HC-SpMM_main.py:18-27, same printed lines
 "Prep. (ms)" :54 and "=> SAG profiling avg (ms)" GNN_model.py:261, same model shape :66-110, same
 schedule: 9 untimed warm-up epochs then --epochs timed ones, Adam lr 0.01, nll_loss :114-158).
@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GCNConv, GINConv, SAGEConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, SAGEConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat", "sage"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat", "gatv2", "sage"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -55,25 +55,27 @@ def parse_args(argv=None):
     # aggregation with edge values: "sym" = D^-1/2 A D^-1/2 (GCN), "mean" = D^-1 A (GraphSAGE-mean), deg = row length
     # (HCSPMM.edge_norm); "none" = the binary A of the reference
     p.add_argument("--norm", type=str, default="none", choices=["none", "sym", "mean"], help="edge normalisation of A")
-    # addition: attention heads of --model gat (GNN_model.GATConv: the heads' outputs are averaged)
-    p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat)")
+    # addition: attention heads of --model gat / gatv2 (GNN_model.GATConv / GATv2Conv: the heads' outputs are averaged)
+    p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat / gatv2)")
     # addition: the first and hidden GAT layers concatenate their heads (hidden / heads features each), the last averages
     # addition: neighbour aggregation of --model sage (GNN_model.SAGEConv: out = X W_root + AGG(X) W_neigh)
     p.add_argument("--aggr", type=str, default="max", choices=["max", "min", "mean"], help="aggregation of --model sage")
     p.add_argument("--gat-concat", action="store_true",
-                   help="--model gat: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
+                   help="--model gat / gatv2: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
     args = p.parse_args(argv)
-    if args.model == "gat" and args.norm != "none":
-        p.error("--norm does not apply to --model gat: its edge values are the attention weights")
+    if args.model in ("gat", "gatv2") and args.norm != "none":
+        p.error("--norm does not apply to --model %s: its edge values are the attention weights" % args.model)
     if args.model == "sage" and args.norm != "none":
         p.error("--norm does not apply to --model sage: its aggregation is --aggr")
     if args.heads < 1:
         p.error("--heads must be at least 1")
-    if args.gat_concat and args.model != "gat":
-        p.error("--gat-concat applies to --model gat only")
+    if args.gat_concat and args.model not in ("gat", "gatv2"):
+        p.error("--gat-concat applies to --model gat / gatv2 only")
     if args.gat_concat and args.hidden % (4 * args.heads) != 0:
         p.error("--gat-concat needs --hidden to be a multiple of 4 * heads (= %d): each head's width must be a multiple of 4"
                 % (4 * args.heads))
+    if args.model == "gatv2" and not args.gat_concat and args.hidden % 4 != 0:
+        p.error("--model gatv2 needs --hidden to be a multiple of 4 (the width of one head)")
     return args
 
 
@@ -82,6 +84,18 @@ def nll_loss(log_probs, target):
     233 K rows in one workgroup on this stack (154 + 96 us forward + backward, 9 % of a Reddit-scale epoch:
     profiles/r01/gnn_epoch_kernels.log); the same number from two parallel kernels."""
     return -log_probs.gather(1, target.long().unsqueeze(1)).mean()
+
+
+class _FirstColumns(nn.Module):
+    """conv built `width` columns wide, of which the first `keep` are the layer's output: the GATv2 kernels take head widths
+    that are multiples of 4, a class count need not be one."""
+
+    def __init__(self, conv, keep):
+        super().__init__()
+        self.conv, self.keep = conv, keep
+
+    def forward(self, *args, **kwargs):
+        return self.conv(*args, **kwargs)[:, :self.keep]
 
 
 class Net(nn.Module):
@@ -161,6 +175,13 @@ def main(argv=None):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated
                 return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True)
             return GATConv(input_dim, output_dim, fixed, heads=args.heads)
+    if args.model == "gatv2":
+        def conv_cls(input_dim, output_dim, fixed):
+            if args.gat_concat and fixed != 2:
+                return GATv2Conv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True)
+            if output_dim % 4 != 0:  # (the class count of the last layer)
+                return _FirstColumns(GATv2Conv(input_dim, (output_dim + 3) // 4 * 4, fixed, heads=args.heads), output_dim)
+            return GATv2Conv(input_dim, output_dim, fixed, heads=args.heads)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 

@@ -570,6 +570,59 @@ extern "C" int hcspmm_gat_attention_backward(const float* alpha, const float* gr
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// GATv2 attention logits (gatv2_attention.hip).  Every array with at least one element needs a pointer; column ids (and
+// perm) are trusted, as on the plan-free paths.
+namespace {
+bool gatv2_shape_ok(int D, int heads) { return heads > 0 && D > 0 && D % heads == 0 && (D / heads) % 4 == 0; }
+}  // namespace
+
+extern "C" int hcspmm_gatv2_scores(const float* H_dst, int64_t ld_dst, const float* H_src, int64_t src_rows, int64_t ld_src,
+                                   const float* att, float slope, float* logits, const int32_t* rowptr, const int32_t* col,
+                                   int64_t N, int64_t E, int D, int heads, void* stream_v) {
+  if (N < 0 || E < 0 || src_rows < 0 || !gatv2_shape_ok(D, heads) || ld_dst < D || ld_src < D || !rowptr || !att ||
+      !__builtin_isfinite(slope))
+    return HCSPMM_EINVAL;
+  if ((N > 0 && !H_dst) || (src_rows > 0 && !H_src)) return HCSPMM_EINVAL;
+  if (E > 0 && (!logits || !col || N == 0 || src_rows == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::Gatv2Args a{};
+  a.H_dst = H_dst, a.H_src = H_src, a.att = att, a.rowptr = rowptr, a.col = col, a.out = logits;
+  a.ld_dst = (size_t)ld_dst, a.ld_src = (size_t)ld_src;
+  a.slope = slope, a.N = (int)N, a.D = D, a.heads = heads, a.E = (long long)E;
+  const hipError_t e = hcspmm::launch_gatv2_scores(a, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" size_t hcspmm_gatv2_backward_workspace_bytes(int64_t N, int64_t E, int D, int heads) {
+  if (N <= 0 || E < 0 || !gatv2_shape_ok(D, heads) || N > INT32_MAX - 2048) return 0;
+  return (size_t)hcspmm::gatv2_grad_blocks((long long)N, D) * (size_t)D * sizeof(float);
+}
+
+extern "C" int hcspmm_gatv2_scores_backward(const float* grad_logits, const float* H_dst, int64_t ld_dst, const float* H_src,
+                                            int64_t ld_src, const float* att, float slope, const int32_t* rowptr,
+                                            const int32_t* col, const int32_t* perm, int64_t N, int64_t E, int D, int heads,
+                                            float* grad_dst, int64_t ld_gdst, float* grad_src, int64_t ld_gsrc, float* grad_att,
+                                            void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || E < 0 || !gatv2_shape_ok(D, heads) || ld_dst < D || ld_src < D || ld_gdst < D || ld_gsrc < D || !rowptr || !att ||
+      !grad_att || !__builtin_isfinite(slope))
+    return HCSPMM_EINVAL;
+  if (N > 0 && (!H_dst || !H_src || !grad_dst || !grad_src)) return HCSPMM_EINVAL;
+  if (E > 0 && (!grad_logits || !col || !perm || N == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 2048 || E > INT32_MAX - 4096 || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  const size_t need = hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads);
+  if (workspace_bytes < need) return HCSPMM_EWORKSPACE;
+  if (need > 0 && !workspace) return HCSPMM_EINVAL;
+  hcspmm::Gatv2Args a{};
+  a.H_dst = H_dst, a.H_src = H_src, a.att = att, a.g = grad_logits, a.rowptr = rowptr, a.col = col, a.perm = perm;
+  a.grad_dst = grad_dst, a.grad_src = grad_src, a.grad_att = grad_att, a.partial = static_cast<float*>(workspace);
+  a.ld_dst = (size_t)ld_dst, a.ld_src = (size_t)ld_src, a.ld_gdst = (size_t)ld_gdst, a.ld_gsrc = (size_t)ld_gsrc;
+  a.slope = slope, a.N = (int)N, a.D = D, a.heads = heads, a.E = (long long)E;
+  // E = 0 takes the same launches: every row is empty, so all three gradients come out as zeros
+  const hipError_t e = hcspmm::launch_gatv2_backward(a, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,
                                       const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                                       const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,

@@ -193,6 +193,31 @@ struct GatArgs {
 hipError_t launch_gat_attention(const GatArgs& a, hipStream_t stream);
 hipError_t launch_gat_attention_backward(const GatArgs& a, hipStream_t stream);
 
+// GATv2 attention logits and their backward (gatv2_attention.hip; include/hcspmm.h hcspmm_gatv2_scores*), fp32:
+//   forward   out[h*E + e] = sum_k att[h][k] * LeakyReLU(H_dst[row(e)][h*Dh + k] + H_src[col(e)][h*Dh + k]),  Dh = D / heads
+//   backward  grad_dst / grad_src / grad_att from g = the gradient of out; partial holds gatv2_grad_blocks(N, D) * D floats
+struct Gatv2Args {
+  const float* H_dst;  // [N][ld_dst]
+  const float* H_src;  // [src_rows][ld_src] (backward: src_rows = N)
+  const float* att;    // [heads][Dh]
+  const float* g;      // backward: [heads][E]
+  const int* rowptr;   // [N + 1]
+  const int* col;      // [E]
+  const int* perm;     // backward: [E], hcspmm_transpose_permutation's
+  float* out;          // forward: [heads][E]
+  float* grad_dst;     // backward: [N][ld_gdst]
+  float* grad_src;     // backward: [N][ld_gsrc]
+  float* grad_att;     // backward: [heads][Dh]
+  float* partial;      // backward: the workgroups' [D] partials of grad_att
+  size_t ld_dst, ld_src, ld_gdst, ld_gsrc;
+  float slope;
+  int N, D, heads;
+  long long E;
+};
+long long gatv2_grad_blocks(long long N, int D);
+hipError_t launch_gatv2_scores(const Gatv2Args& a, hipStream_t stream);
+hipError_t launch_gatv2_backward(const Gatv2Args& a, hipStream_t stream);
+
 // Max / min aggregation and its backward (spmm_extremum.hip; include/hcspmm.h hcspmm_forward_extremum*), fp32.  p as for
 // launch_plan_f32 (forward: X, Z; backward: X = grad_Z, Z = grad_X, ldx = its row stride), or p.plan == nullptr for the
 // plan-free launch (then only X, Z, col, ldx, ldz, N, D are read).  Forward: partial = the fp32 values of the split rows'

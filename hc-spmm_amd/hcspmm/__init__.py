@@ -26,6 +26,7 @@ __all__ = [
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
+    "gatv2_scores", "gatv2_scores_backward",
     "forward_max", "forward_min", "forward_extremum_backward",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
@@ -834,6 +835,78 @@ def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column
                                                   _ptr(row_pointers), _ptr(column_index), _ptr(perm), N, E, heads,
                                                   _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src), stream))
     return grad_s_dst, grad_s_src, grad_scores
+
+
+def _gatv2_operands(H_dst, H_src, att, row_pointers, column_index):
+    """-> (N, E, D, heads) of a GATv2 call: H_dst [N, D] and H_src [src_rows, D] float32 views with unit inner stride, att
+    [heads, Dh] (or [Dh] for one head) contiguous, D = heads * Dh, Dh % 4 == 0"""
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    if row_pointers.dtype != torch.int32 or column_index.dtype != torch.int32:
+        raise RuntimeError("nodePointer / edgeList must be int32")
+    _check_view(H_dst, "H_dst", torch.float32)
+    _check_view(H_src, "H_src", torch.float32)
+    _check_input(att, "att")
+    if att.dtype != torch.float32 or att.dim() not in (1, 2) or att.numel() == 0:
+        raise RuntimeError("att must be a float32 [Dh] or [heads, Dh] tensor, got %s %s" % (att.dtype, tuple(att.shape)))
+    N, E, D = row_pointers.numel() - 1, column_index.numel(), H_dst.size(1)
+    heads = 1 if att.dim() == 1 else att.size(0)
+    if H_dst.size(0) != N:
+        raise RuntimeError("H_dst has %d rows but the graph has %d nodes" % (H_dst.size(0), N))
+    if H_src.size(1) != D:
+        raise RuntimeError("H_src has %d columns but H_dst has %d" % (H_src.size(1), D))
+    if att.numel() != D:
+        raise RuntimeError("att has %d elements but H_dst has %d columns" % (att.numel(), D))
+    if H_src.device != H_dst.device or att.device != H_dst.device or row_pointers.device != H_dst.device:
+        raise RuntimeError("H_src, att and the graph must be on the device of H_dst")
+    return N, E, D, heads  # (Dh % 4 and the slope are the library's to refuse: HCSPMM_EINVAL)
+
+
+def gatv2_scores(H_dst, H_src, att, row_pointers, column_index, negative_slope=0.2):
+    """GATv2 attention logits -> float32 [heads, E] ([E] for a 1-D att):
+    out[h, e] = sum_k att[h, k] * LeakyReLU(H_dst[row(e), h*Dh + k] + H_src[column_index[e], h*Dh + k]), all heads in one
+    launch (include/hcspmm.h hcspmm_gatv2_scores).  H_dst [N, D] and H_src [src_rows, D] are float32 2-D views with unit
+    inner stride (the halves of one [N, 2 D] projection need no copy), att [heads, Dh] contiguous, D = heads * Dh,
+    Dh % 4 == 0.  H_src may have any number of rows (a row block); column ids are trusted to be below it.  edge_softmax of
+    the result is the attention; each head is bit for bit the single-head call on its column slice."""
+    N, E, D, heads = _gatv2_operands(H_dst, H_src, att, row_pointers, column_index)
+    out = torch.empty((E,) if att.dim() == 1 else (heads, E), dtype=torch.float32, device=H_dst.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
+    with _on_device(H_dst.device):
+        check(lib().hcspmm_gatv2_scores(_ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.size(0), H_src.stride(0), _ptr(att),
+                                        float(negative_slope), _ptr(out), _ptr(row_pointers), _ptr(column_index), N, E, D,
+                                        heads, stream))
+    return out
+
+
+def gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, perm, negative_slope=0.2):
+    """Backward of gatv2_scores on a square, pattern-symmetric graph -> (grad_H_dst, grad_H_src, grad_att), contiguous and
+    shaped as H_dst, H_src and att.  grad_logits is float32 of gatv2_scores' shape; perm is transpose_permutation's (int64
+    as it returns it, or an int32 copy; the kernel reads int32).  Three launches, no atomics: two calls give the same bits
+    (hcspmm_gatv2_scores_backward; the workspace is allocated here)."""
+    N, E, D, heads = _gatv2_operands(H_dst, H_src, att, row_pointers, column_index)
+    if H_src.size(0) != N:
+        raise RuntimeError("H_src has %d rows but the backward needs one per node (%d)" % (H_src.size(0), N))
+    shape = (E,) if att.dim() == 1 else (heads, E)
+    _check_input(grad_logits, "grad_logits")
+    if grad_logits.dtype != torch.float32 or tuple(grad_logits.shape) != shape:
+        raise RuntimeError("grad_logits must be float32 of shape %s, got %s %s" % (shape, grad_logits.dtype, tuple(grad_logits.shape)))
+    if grad_logits.device != H_dst.device:
+        raise RuntimeError("grad_logits must be on the device of H_dst")
+    perm = _perm_i32(perm, E, row_pointers.device)
+    L = lib()
+    grad_dst = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
+    grad_src = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
+    grad_att = torch.empty_like(att)
+    ws_bytes = int(L.hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=H_dst.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
+    with _on_device(H_dst.device):
+        check(L.hcspmm_gatv2_scores_backward(_ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.stride(0),
+                                             _ptr(att), float(negative_slope), _ptr(row_pointers), _ptr(column_index), _ptr(perm),
+                                             N, E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D, _ptr(grad_att), _ptr(ws),
+                                             ws_bytes, stream))
+    return grad_dst, grad_src, grad_att
 
 
 def update(X, W):

@@ -83,6 +83,10 @@ SYMBOLS = {
     "hcspmm_gat_attention": (_int, [_vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_gat_attention_backward": (_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp,
                                              _vp]),
+    "hcspmm_gatv2_scores": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
+    "hcspmm_gatv2_backward_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "hcspmm_gatv2_scores_backward": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _int,
+                                            _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "hcspmm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_forward_strided": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz,
                                       _vp]),

@@ -493,6 +493,76 @@ std::vector<torch::Tensor> gat_attention_backward(torch::Tensor alpha, torch::Te
   return {grad_s_dst, grad_s_src, grad_scores};
 }
 
+// GATv2 operands: H_dst [N, D] and H_src [src_rows, D] float32 views with unit inner stride, att [heads, Dh] (or [Dh])
+// contiguous with D elements -> heads.  Dh % 4 and the slope are the library's to refuse (HCSPMM_EINVAL).
+int64_t gatv2_operands(const torch::Tensor& H_dst, const torch::Tensor& H_src, const torch::Tensor& att,
+                       const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  for (const torch::Tensor* t : {&H_dst, &H_src}) {
+    const char* name = t == &H_dst ? "H_dst" : "H_src";
+    TORCH_CHECK(t->is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1), name,
+                " must be a 2-D float32 view with unit inner stride");
+  }
+  CHECK_INPUT(att);
+  TORCH_CHECK(att.scalar_type() == torch::kFloat && (att.dim() == 1 || att.dim() == 2) && att.numel() > 0,
+              "att must be a float32 [Dh] or [heads, Dh] tensor, got ", att.scalar_type(), " ", att.sizes());
+  const int64_t N = nodePointer.numel() - 1;
+  TORCH_CHECK(H_dst.size(0) == N, "H_dst has ", H_dst.size(0), " rows but the graph has ", N, " nodes");
+  TORCH_CHECK(H_src.size(1) == H_dst.size(1), "H_src has ", H_src.size(1), " columns but H_dst has ", H_dst.size(1));
+  TORCH_CHECK(att.numel() == H_dst.size(1), "att has ", att.numel(), " elements but H_dst has ", H_dst.size(1), " columns");
+  TORCH_CHECK(H_src.device() == H_dst.device() && att.device() == H_dst.device() && nodePointer.device() == H_dst.device(),
+              "H_src, att and the graph must be on the device of H_dst");
+  return att.dim() == 1 ? 1 : att.size(0);
+}
+
+// GATv2 attention logits (hcspmm_gatv2_scores): float32 [heads, E] ([E] for a 1-D att)
+torch::Tensor gatv2_scores(torch::Tensor H_dst, torch::Tensor H_src, torch::Tensor att, torch::Tensor nodePointer,
+                           torch::Tensor edgeList, double negative_slope) {
+  const int64_t heads = gatv2_operands(H_dst, H_src, att, nodePointer, edgeList);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), D = H_dst.size(1);
+  auto out = att.dim() == 1 ? torch::empty({E}, att.options()) : torch::empty({heads, E}, att.options());
+  const c10::DeviceGuard guard(H_dst.device());
+  check_rc(hcspmm_gatv2_scores(fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.size(0), H_src.stride(0), fptr(att),
+                               (float)negative_slope, mfptr(out), iptr(nodePointer), iptr(edgeList), N, E, (int)D, (int)heads,
+                               (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
+           "gatv2_scores");
+  return out;
+}
+
+// Backward of gatv2_scores (hcspmm_gatv2_scores_backward; the workspace is allocated here) -> [grad_H_dst, grad_H_src, grad_att]
+std::vector<torch::Tensor> gatv2_scores_backward(torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src,
+                                                 torch::Tensor att, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                 torch::Tensor perm, double negative_slope) {
+  const int64_t heads = gatv2_operands(H_dst, H_src, att, nodePointer, edgeList);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), D = H_dst.size(1);
+  TORCH_CHECK(H_src.size(0) == N, "H_src has ", H_src.size(0), " rows but the backward needs one per node (", N, ")");
+  const std::vector<int64_t> shape = att.dim() == 1 ? std::vector<int64_t>{E} : std::vector<int64_t>{heads, E};
+  CHECK_INPUT(grad_logits);
+  TORCH_CHECK(grad_logits.scalar_type() == torch::kFloat && grad_logits.sizes() == c10::IntArrayRef(shape),
+              "grad_logits must be float32 of shape ", c10::IntArrayRef(shape), ", got ", grad_logits.scalar_type(), " ",
+              grad_logits.sizes());
+  TORCH_CHECK(grad_logits.device() == H_dst.device(), "grad_logits must be on the device of H_dst");
+  CHECK_INPUT(perm);
+  TORCH_CHECK((perm.scalar_type() == torch::kInt || perm.scalar_type() == torch::kLong) && perm.dim() == 1 && perm.numel() == E,
+              "perm must be an int32 / int64 [E] tensor with E = ", E, ", got ", perm.scalar_type(), " ", perm.sizes());
+  TORCH_CHECK(perm.device() == nodePointer.device(), "perm must be on the device of row_pointers");
+  auto perm32 = perm.scalar_type() == torch::kInt ? perm : perm.to(torch::kInt);
+  auto grad_dst = torch::empty({N, D}, att.options()), grad_src = torch::empty({N, D}, att.options());
+  auto grad_att = torch::empty_like(att);
+  const size_t ws_bytes = hcspmm_gatv2_backward_workspace_bytes(N, E, (int)D, (int)heads);
+  auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, att.options());
+  const c10::DeviceGuard guard(H_dst.device());
+  check_rc(hcspmm_gatv2_scores_backward(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0), fptr(att),
+                                        (float)negative_slope, iptr(nodePointer), iptr(edgeList), iptr(perm32), N, E, (int)D,
+                                        (int)heads, mfptr(grad_dst), D, mfptr(grad_src), D, mfptr(grad_att), mfptr(ws), ws_bytes,
+                                        (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
+           "gatv2_scores_backward");
+  return {grad_dst, grad_src, grad_att};
+}
+
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
                                      const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
@@ -808,6 +878,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "backward of gat_attention (square, pattern-symmetric graph; perm = transpose_permutation) -> [grad_s_dst, grad_s_src, "
         "grad_scores] (gfx950)",
         pybind11::arg("alpha"), pybind11::arg("grad_alpha"), pybind11::arg("s_dst"), pybind11::arg("s_src"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("perm"), pybind11::arg("negative_slope") = 0.2);
+  m.def("gatv2_scores", &gatv2_scores,
+        "GATv2 attention logits: float32 [heads, E], out[h][e] = sum_k att[h][k] * LeakyReLU(H_dst[row(e)][h*Dh + k] + "
+        "H_src[col(e)][h*Dh + k]) (gfx950)",
+        pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"), pybind11::arg("row_pointers"),
+        pybind11::arg("column_index"), pybind11::arg("negative_slope") = 0.2);
+  m.def("gatv2_scores_backward", &gatv2_scores_backward,
+        "backward of gatv2_scores (square, pattern-symmetric graph; perm = transpose_permutation) -> [grad_H_dst, grad_H_src, "
+        "grad_att] (gfx950)",
+        pybind11::arg("grad_logits"), pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"),
         pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("perm"), pybind11::arg("negative_slope") = 0.2);
   m.def("abi_version", []() { return hcspmm_abi_version(); });
   // LOI layout reorder on the host (the reference ships it as a separate file-to-file program, LOI.cpp)

@@ -30,7 +30,8 @@ extern "C" {
  * working): hcspmm_loi_reorder_fast, hcspmm_dense_update (round 4); hcspmm_forward_weighted, hcspmm_edge_norm_device,
  * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6); hcspmm_gat_attention,
  * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8); hcspmm_extremum_workspace_bytes,
- * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9); hcspmm_gatv2_scores, hcspmm_gatv2_backward_workspace_bytes,
+ * hcspmm_gatv2_scores_backward (round 10).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -469,6 +470,51 @@ int hcspmm_gat_attention_backward(const float* alpha_d, const float* grad_alpha_
                                   float* grad_scores_out_d /* g, [heads][E] */,
                                   float* grad_s_dst_out_d /* [N][heads] */, float* grad_s_src_out_d /* [N][heads] */,
                                   void* stream);
+
+/* GATv2 attention logits (Brody et al.: the non-linearity inside the dot product), all heads in one launch, from fp32 node
+ * features H_dst [num_nodes][ld_dst] and H_src [src_rows][ld_src] of embedding_dim = heads * Dh columns (Dh % 4 == 0; leading
+ * dimensions >= embedding_dim in elements, so the two halves of one [N, 2 D] projection can be passed as views) and att
+ * [heads][Dh]:
+ *   z = H_dst[r][h*Dh + k] + H_src[c][h*Dh + k],  l = z > 0 ? z : z * negative_slope,  logits[h][e] = sum_k att[h][k] * l
+ * for entry e of row r with column c; logits_out_d is head-major [heads][E], the layout of hcspmm_edge_softmax.  z and l
+ * are each rounded once (never contracted into a neighbouring operation) and never stored; per entry and head the sum runs
+ * over a lane's four columns in column order with fmaf, then over the head's lanes by a fixed xor butterfly, so two calls
+ * give the same bits and every head has the bits of a single-head call on its column slice.  H_src may be rectangular (a
+ * row block): column ids are trusted to be below src_rows, as on the plan-free paths.  Argument errors (NULL pointers,
+ * heads <= 0, embedding_dim <= 0 or not a multiple of heads, Dh % 4 != 0, a leading dimension below embedding_dim,
+ * negative sizes, a non-finite negative_slope) are HCSPMM_EINVAL before any device call; E = 0 launches nothing.
+ * Asynchronous on `stream`, no allocation, no synchronisation: capturable into a HIP graph. */
+int hcspmm_gatv2_scores(const float* H_dst_d, int64_t ld_dst, const float* H_src_d, int64_t src_rows, int64_t ld_src,
+                        const float* att_d /* [heads][Dh] */, float negative_slope, float* logits_out_d /* [heads][E] */,
+                        const int32_t* row_pointers_d, const int32_t* column_index_d, int64_t num_nodes,
+                        int64_t num_edges, int embedding_dim, int heads, void* stream);
+
+/* Bytes of workspace hcspmm_gatv2_scores_backward needs: one [embedding_dim] fp32 partial of grad_att per workgroup of its
+ * row launches, whose grid (at most 4096 workgroups) depends on (num_nodes, embedding_dim) alone.  0 for shapes the
+ * backward refuses. */
+size_t hcspmm_gatv2_backward_workspace_bytes(int64_t num_nodes, int64_t num_edges, int embedding_dim, int heads);
+
+/* Backward of hcspmm_gatv2_scores on a square, pattern-symmetric graph (H_src has num_nodes rows), given g = grad_logits
+ * [heads][E], with d(z) = z > 0 ? 1 : negative_slope from the forward's z (the derivative at z == 0 is negative_slope) and
+ * h(j) = j / Dh:
+ *   grad_H_dst[r][j] = att[j] * sum_{e in row r}  g[h(j)][e]                   * d(H_dst[r][j] + H_src[col(e)][j])
+ *   grad_H_src[c][j] = att[j] * sum_{e' in row c} g[h(j)][transpose_perm[e']] * d(H_dst[col(e')][j] + H_src[c][j])
+ *   grad_att[h][k]   = sum_e g[h][e] * l[h][e][k]
+ * with transpose_perm_d [E] from hcspmm_transpose_permutation.  Three launches.  Two row-parallel ones write every row of
+ * grad_H_dst / grad_H_src exactly once (workgroup b takes the row tiles b, b + grid, ...): a row of up to 256 entries is
+ * summed in entry order by one lane group, a longer
+ * one by the lane groups of a workgroup (entry i by group i mod NG, in order), the partial rows folded by an xor butterfly
+ * over a wave's groups and then in wave order.  The grad_H_dst launch also sums g * l per workgroup into workspace_d in a
+ * fixed order; the third launch adds those partials in index order.  No atomics: every sum's order is a function of
+ * (num_nodes, embedding_dim) and the row lengths, so two calls give the same bits.  Rows without entries get zeros; with
+ * E = 0 all three gradients are zeroed.  Argument errors as hcspmm_gatv2_scores; a workspace below
+ * hcspmm_gatv2_backward_workspace_bytes is HCSPMM_EWORKSPACE.  Asynchronous on `stream`, capturable into a HIP graph. */
+int hcspmm_gatv2_scores_backward(const float* grad_logits_d, const float* H_dst_d, int64_t ld_dst, const float* H_src_d,
+                                 int64_t ld_src, const float* att_d, float negative_slope, const int32_t* row_pointers_d,
+                                 const int32_t* column_index_d, const int32_t* transpose_perm_d, int64_t num_nodes,
+                                 int64_t num_edges, int embedding_dim, int heads, float* grad_H_dst_out_d, int64_t ld_gdst,
+                                 float* grad_H_src_out_d, int64_t ld_gsrc, float* grad_att_out_d /* [heads][Dh] */,
+                                 void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
