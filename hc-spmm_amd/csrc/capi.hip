@@ -133,6 +133,10 @@ extern "C" int32_t hcspmm_wide_threshold(const hcspmm_plan_header* h, int D) {
   return hcspmm_wide_threshold_typed(h, D, HCSPMM_DTYPE_F32);
 }
 
+extern "C" int32_t hcspmm_own_tiny_launch(const hcspmm_plan_header* h, int fused) {
+  return h && hcspmm::plan_own_tiny_launch(h->n_tiny, fused) ? 1 : 0;
+}
+
 extern "C" int hcspmm_abi_version(void) { return HCSPMM_ABI_VERSION; }
 
 // Device variant of hcspmm_graph_fingerprint_host: every thread adds the terms of its grid-stride share, a wave

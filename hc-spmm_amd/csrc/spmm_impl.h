@@ -832,6 +832,15 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
 #ifndef HCSPMM_TINY_KERNEL_MIN_TASKS
 #define HCSPMM_TINY_KERNEL_MIN_TASKS 524288  // fewer tiny tasks than this stay in the hybrid launch: even at 465 K, -15 % at 240 K, +3-4 % at 900 K (profiles/r03/ab_tiny_sizes.log)
 #endif
+// The one predicate behind that choice: launch_plan_LV, launch_plan_w_LV, launch_plan_wh_LV and hcspmm_own_tiny_launch all ask
+// it.  fused: PlanArgs::fused (the fused operators keep their tiny tasks in their own launches); the weighted forms pass 0.
+inline bool own_tiny_launch(int n_tiny, int fused) {
+  static const int tiny_kernel_min = [] {
+    const char* e = getenv("HCSPMM_TINY_KERNEL_MIN_TASKS");
+    return e ? atoi(e) : HCSPMM_TINY_KERNEL_MIN_TASKS;
+  }();
+  return !fused && tiny_kernel_min >= 0 && n_tiny >= tiny_kernel_min && n_tiny > 0;
+}
 template <typename E, int L, int VEC>
 __global__ __launch_bounds__(kThreads, HCSPMM_TINY_KERNEL_WAVES) void tiny_kernel(PlanArgs a) {
   constexpr int R = 64 / L, T = HCSPMM_TINY_KERNEL_T;
@@ -1018,13 +1027,9 @@ static hipError_t launch_plan_LV(const PlanArgs& a, hipStream_t stream) {
   }
   b.wide_wgs = (b.n_wide + kWaves - 1) / kWaves;
   // tiny tasks: a region of the hybrid launch, or -- when there are enough of them -- a launch of their own behind it
-  static const int tiny_kernel_min = [] {
-    const char* e = getenv("HCSPMM_TINY_KERNEL_MIN_TASKS");
-    return e ? atoi(e) : HCSPMM_TINY_KERNEL_MIN_TASKS;
-  }();
-  const bool own_tiny_launch = !a.fused && tiny_kernel_min >= 0 && b.n_tiny >= tiny_kernel_min && b.n_tiny > 0;
-  b.tiny_kernel_wgs = own_tiny_launch ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
-  b.tiny_wgs = own_tiny_launch ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
+  const bool own_tiny = own_tiny_launch(b.n_tiny, a.fused);
+  b.tiny_kernel_wgs = own_tiny ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
+  b.tiny_wgs = own_tiny ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
   b.free_wgs_pp = b.wide_wgs + (b.n_tasks - b.n_tiny - b.n_wide + kWaves * R - 1) / (kWaves * R) + b.tiny_wgs;
   // the sliced region: per XCD ceil(slice_xcd_tasks / tasks per workgroup) workgroups, interleaved b = x (mod 8); a panel is
   // padded to a multiple of 8 workgroups so that b mod 8 == blockIdx mod 8 in every panel (the idle ones return at once)

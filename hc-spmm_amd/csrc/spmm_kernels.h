@@ -83,6 +83,8 @@ struct WWindowArgs {
 // vec = elements per lane access.  fp32: 4 for every D >= 4 (element-aligned vectors: any stride, any base address), 2 / 1 for
 // D = 2, 3 / 1.  16-bit: 8 (D >= 32) or 4 when D and the strides are even and the bases 4-byte aligned (dword-aligned vectors), else 1.
 hipError_t launch_plan_f32(const PlanArgs& a, int vec, hipStream_t stream);
+// what the planned launchers decide for a plan's n_tiny tiny tasks (spmm_impl.h own_tiny_launch): true = a launch of their own
+bool plan_own_tiny_launch(int n_tiny, int fused);
 hipError_t launch_window_f32(const WindowArgs& a, int vec, hipStream_t stream);
 hipError_t launch_plan_f16(const PlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_f16(const WindowArgs& a, int vec, hipStream_t stream);

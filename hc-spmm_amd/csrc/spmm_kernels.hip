@@ -13,6 +13,8 @@ hipError_t launch_plan_f32(const PlanArgs& a, int vec, hipStream_t stream) {
   return launch_plan_LV<F32, 4, 1>(a, stream);
 }
 
+bool plan_own_tiny_launch(int n_tiny, int fused) { return own_tiny_launch(n_tiny, fused); }
+
 hipError_t launch_window_f32(const WindowArgs& a, int vec, hipStream_t stream) {
   if (vec == 4) { HCSPMM_DISPATCH_L(launch_window_LV, F32, 4, a.D, a, stream) }
   if (a.D > 4 * vec) return hipErrorInvalidValue;

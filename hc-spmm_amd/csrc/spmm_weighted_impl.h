@@ -602,13 +602,9 @@ static hipError_t launch_plan_w_LV(const WPlanArgs& wa, hipStream_t stream) {
   b.fused = 0;
   b.n_wide = (R > 1) ? a.n_wide : 0;
   b.wide_wgs = (b.n_wide + kWaves - 1) / kWaves;
-  static const int tiny_kernel_min = [] {
-    const char* e = getenv("HCSPMM_TINY_KERNEL_MIN_TASKS");
-    return e ? atoi(e) : HCSPMM_TINY_KERNEL_MIN_TASKS;
-  }();
-  const bool own_tiny_launch = tiny_kernel_min >= 0 && b.n_tiny >= tiny_kernel_min && b.n_tiny > 0;
-  b.tiny_kernel_wgs = own_tiny_launch ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
-  b.tiny_wgs = own_tiny_launch ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
+  const bool own_tiny = own_tiny_launch(b.n_tiny, 0);
+  b.tiny_kernel_wgs = own_tiny ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
+  b.tiny_wgs = own_tiny ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
   b.free_wgs_pp = b.wide_wgs + (b.n_tasks - b.n_tiny - b.n_wide + kWaves * R - 1) / (kWaves * R) + b.tiny_wgs;
   b.slice_wgs = a.n_slices > 0 ? 8 * ((a.slice_xcd_tasks + kWaves * R - 1) / (kWaves * R)) : 0;
   b.sparse_wgs_pp = b.slice_wgs + b.free_wgs_pp;

@@ -28,7 +28,7 @@ __all__ = [
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
     "gatv2_scores", "gatv2_scores_backward",
     "forward_max", "forward_min", "forward_extremum_backward",
-    "wide_threshold", "workspace_bytes", "fused_in_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
+    "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
 
@@ -170,6 +170,13 @@ def fused_in_launch(row_nzr, embedding_dim, hidden_dim):
     1 = dense-tile windows update inside the hybrid launch, 2 = the sparse-row path as well (row-tile form)."""
     h = plan_header(row_nzr)
     return int(lib().hcspmm_fused_in_launch(ctypes.byref(h), int(embedding_dim), int(hidden_dim))) if h is not None else 0
+
+
+def own_tiny_launch(row_nzr, fused=False):
+    """True when the tiny tasks of this plan run as a launch of their own (tiny_kernel, tiny_w_kernel, tiny_wh_kernel) rather
+    than as a region of the hybrid launch (hcspmm_own_tiny_launch, include/hcspmm.h); fused: ask about forward_*_fused."""
+    h = plan_header(row_nzr)
+    return bool(lib().hcspmm_own_tiny_launch(ctypes.byref(h), int(bool(fused)))) if h is not None else False
 
 
 def _ptr(t):

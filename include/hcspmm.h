@@ -519,6 +519,14 @@ int hcspmm_gatv2_scores_backward(const float* grad_logits_d, const float* H_dst_
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
 
+/* 1 when the tiny tasks of this plan (header n_tiny: tasks of at most two entries, indices inline in the descriptor) run as
+ * a launch of their own behind the hybrid launch, 0 when they stay a region of it: the one predicate hcspmm_forward*,
+ * hcspmm_forward_weighted and hcspmm_forward_weighted_heads decide by (n_tiny at least 524 288, or what
+ * HCSPMM_TINY_KERNEL_MIN_TASKS says: -1 never, 1 always).  fused != 0 asks about hcspmm_forward_fused, whose tiny tasks never
+ * take that launch.  The results are the same bits either way; the query exists so that a caller -- a test -- can tell which
+ * kernel a call reaches.  header_h == NULL (plan-free kernel): 0. */
+int32_t hcspmm_own_tiny_launch(const hcspmm_plan_header* header_h, int fused);
+
 /* ------------------------------------------------------------------------------------------
  * Fused aggregate + update: out2 = A * X (N x D), out = out2 * weights (N x H), weights row-major
  * D x H with row stride weights_ld_row and column stride weights_ld_col in elements (so a

@@ -67,6 +67,22 @@ def test_forward_argument_checks_need_no_gpu(capi):
     assert L.hcspmm_wide_threshold_typed(None, 256, 2) == 64  # 16-bit rows of 256 columns still fit 32 lanes
 
 
+def test_own_tiny_launch_query_follows_the_plan(capi):
+    """hcspmm_own_tiny_launch: the launchers' own predicate on the plan's n_tiny -- a launch of their own from 524 288 tiny
+    tasks on (unless HCSPMM_TINY_KERNEL_MIN_TASKS says otherwise), never for the fused operators, never without a plan."""
+    assert "HCSPMM_TINY_KERNEL_MIN_TASKS" not in os.environ, "unset it: the default threshold is the subject"
+    for N, want in ((524288, True), (524287, False)):
+        rp = np.arange(N + 1, dtype=np.int32)  # one entry per row: every task is tiny
+        col = ((np.arange(N, dtype=np.int64) * 7919 + 1) % N).astype(np.int32)
+        plan = _pre(rp, col, 2)[4]
+        h = hcspmm.plan_header(plan)
+        assert h.n_tiny == N and h.n_tasks == N
+        assert hcspmm.own_tiny_launch(plan) is want and hcspmm.own_tiny_launch(plan, fused=True) is False
+        assert capi.lib().hcspmm_own_tiny_launch(ctypes.byref(h), 0) == int(want)
+    assert capi.lib().hcspmm_own_tiny_launch(None, 0) == 0
+    assert hcspmm.own_tiny_launch(torch.zeros(1, dtype=torch.int32)) is False  # the reference's [0] placeholder
+
+
 def test_missing_library_fails_loudly(monkeypatch, capi):
     monkeypatch.setattr(capi, "_LIB", None)
     monkeypatch.setattr(capi, "LIB_PATH", "/nonexistent/libhcspmm.so")
