@@ -229,11 +229,69 @@ def transpose_permutation(row_pointers, column_index):
     return perm
 
 
-def weighted_aggregate(X, edge_weight, graph):
-    """A_w X with autograd for X (graph = the eight graph tensors)."""
+_TRANSPOSED_GRAPH = {}  # as _TRANSPOSED -> (weak refs, the nine tensors of transposed_graph)
+
+
+def transposed_graph(graph):
+    """A^T of a square graph, for the backward of message passing over a directed edge_index: the eight graph tensors of A^T
+    -- HCSPMM.transpose_graph, then HCSPMM.preprocess on A^T, so A^T has its own windows, classification and plan and
+    in-degree hubs are balanced like out-degree hubs -- plus entry_index_t (int32 [E]: the position in A of every entry of
+    A^T).  Cached per (row_pointers, column_index) tensor pair; graph = the eight graph tensors of A."""
+    import weakref
+    row_pointers, column_index = graph[0], graph[1]
+    key = (row_pointers.data_ptr(), column_index.data_ptr(), row_pointers.numel(), column_index.numel())
+    hit = _TRANSPOSED_GRAPH.get(key)
+    if hit is not None and hit[0]() is row_pointers and hit[1]() is column_index:
+        return hit[2]
+    n = row_pointers.numel() - 1
+    try:
+        rp_t, col_t, eid_t = HCSPMM.transpose_graph(row_pointers, column_index)
+    except RuntimeError as e:
+        raise RuntimeError("HCSPMM: transposed_graph needs a square graph whose rows hold strictly ascending column ids "
+                           "below the number of nodes (%d)" % n) from e
+    out = (rp_t, col_t) + tuple(HCSPMM.preprocess(col_t, rp_t, n, col_t.numel(), (n + 15) // 16)) + (eid_t,)
+    for k in [k for k, v in _TRANSPOSED_GRAPH.items() if v[0]() is None or v[1]() is None]:
+        del _TRANSPOSED_GRAPH[k]
+    _TRANSPOSED_GRAPH[key] = (weakref.ref(row_pointers), weakref.ref(column_index), out)
+    return out
+
+
+class EdgeWeightedAggregateDirected(torch.autograd.Function):
+    """A_w X on any square graph, edge_weight [E] or [heads, E]: the forward is EdgeWeightedAggregate(Heads)'s;
+    dX = A_w^T dY = HCSPMM.forward_weighted_indexed(dY, w, entry_index_t) on A^T's graph tensors and plan (the values are read
+    in place through the index, no permuted copy) and dw = HCSPMM.sddmm(_heads)(dY, X) on A.  tail = the eight graph tensors
+    of A followed by transposed_graph's nine."""
+
+    @staticmethod
+    def forward(ctx, X, edge_weight, *tail):
+        X = X.contiguous()
+        edge_weight = edge_weight.contiguous()
+        ctx.save_for_backward(X, edge_weight, *tail)
+        fn = HCSPMM.forward_weighted if edge_weight.dim() == 1 else HCSPMM.forward_weighted_heads
+        return fn(X, edge_weight, *tail[:N_GRAPH])[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, edge_weight, *tail = ctx.saved_tensors
+        graph, graph_t, eid_t = tail[:N_GRAPH], tail[N_GRAPH:2 * N_GRAPH], tail[2 * N_GRAPH]
+        d_out = d_out.contiguous()
+        d_x = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_x = HCSPMM.forward_weighted_indexed(d_out, edge_weight, eid_t, *graph_t)[0]
+        if ctx.needs_input_grad[1]:
+            d_w = (HCSPMM.sddmm(d_out, X, *graph) if edge_weight.dim() == 1
+                   else HCSPMM.sddmm_heads(d_out, X, *graph, edge_weight.size(0)))
+        return (d_x, d_w) + (None,) * len(tail)
+
+
+def weighted_aggregate(X, edge_weight, graph, directed=False):
+    """A_w X with autograd for X (graph = the eight graph tensors).  directed=True: the pattern need not be symmetric (the
+    backward runs on transposed_graph(graph))."""
     if edge_weight.requires_grad:
         raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented; "
                                   "pass values that do not require grad")
+    if directed:
+        return EdgeWeightedAggregateDirected.apply(X, edge_weight, *graph, *transposed_graph(graph))
     values_t = edge_weight.detach()[transpose_permutation(graph[0], graph[1])].contiguous()
     return HCSPMMFunction_Weighted.apply(X, edge_weight, values_t, *graph)
 
@@ -258,9 +316,12 @@ class EdgeWeightedAggregate(torch.autograd.Function):
         return (d_x, d_w, None) + (None,) * N_GRAPH
 
 
-def edge_weighted_aggregate(X, edge_weight, graph):
+def edge_weighted_aggregate(X, edge_weight, graph, directed=False):
     """A_w X with autograd for X and edge_weight (float32 [E], aligned with column_index), e.g. learned or attention
-    weights; graph = the eight graph tensors, whose pattern must be symmetric (the backward's A_w^T)."""
+    weights; graph = the eight graph tensors, whose pattern must be symmetric (the backward's A_w^T) unless directed=True:
+    the backward then runs on transposed_graph(graph)."""
+    if directed:
+        return EdgeWeightedAggregateDirected.apply(X, edge_weight, *graph, *transposed_graph(graph))
     perm = transpose_permutation(graph[0], graph[1])
     return EdgeWeightedAggregate.apply(X, edge_weight, perm, *graph)
 
@@ -289,9 +350,12 @@ class EdgeWeightedAggregateHeads(torch.autograd.Function):
         return (d_x, d_w, None) + (None,) * N_GRAPH
 
 
-def edge_weighted_aggregate_heads(X, edge_weight, graph):
+def edge_weighted_aggregate_heads(X, edge_weight, graph, directed=False):
     """Multi-head A_w X with autograd for X [N, heads*Dh] and edge_weight [heads, E] (float32, Dh % 4 == 0); graph = the
-    eight graph tensors, whose pattern must be symmetric (the backward's A_w^T)."""
+    eight graph tensors, whose pattern must be symmetric (the backward's A_w^T) unless directed=True: the backward then
+    runs on transposed_graph(graph)."""
+    if directed:
+        return EdgeWeightedAggregateDirected.apply(X, edge_weight, *graph, *transposed_graph(graph))
     perm = transpose_permutation(graph[0], graph[1])
     return EdgeWeightedAggregateHeads.apply(X, edge_weight, perm, *graph)
 
@@ -350,9 +414,33 @@ class GATAttention(torch.autograd.Function):
         return d_dst, d_src, None, None, None, None
 
 
-def gat_attention(s_dst, s_src, graph, negative_slope=0.2):
+class GATAttentionDirected(torch.autograd.Function):
+    """GATAttention on any square graph: the backward's column side walks A^T (HCSPMM.gat_attention_backward_directed with
+    transposed_graph's row_pointers_t and entry_index_t)."""
+
+    @staticmethod
+    def forward(ctx, s_dst, s_src, negative_slope, row_pointers, column_index, row_pointers_t, entry_index_t):
+        s_dst, s_src = s_dst.contiguous(), s_src.contiguous()
+        alpha = HCSPMM.gat_attention(s_dst, s_src, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t, entry_index_t)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, d_alpha):
+        alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t, entry_index_t = ctx.saved_tensors
+        d_dst, d_src, _ = HCSPMM.gat_attention_backward_directed(alpha, d_alpha.contiguous(), s_dst, s_src, row_pointers,
+                                                                 column_index, row_pointers_t, entry_index_t, ctx.negative_slope)
+        return d_dst, d_src, None, None, None, None, None
+
+
+def gat_attention(s_dst, s_src, graph, negative_slope=0.2, directed=False):
     """GAT attention weights [heads, E] ([E] for 1-D scores) with autograd for both node-major scores; graph = the eight
-    graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over A^T)."""
+    graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over A^T) unless
+    directed=True: the backward then walks transposed_graph(graph)."""
+    if directed:
+        gt = transposed_graph(graph)
+        return GATAttentionDirected.apply(s_dst, s_src, float(negative_slope), graph[0], graph[1], gt[0], gt[N_GRAPH])
     perm32 = transpose_permutation_i32(graph[0], graph[1])
     return GATAttention.apply(s_dst, s_src, float(negative_slope), perm32, graph[0], graph[1])
 
@@ -380,10 +468,35 @@ class GATv2Scores(torch.autograd.Function):
         return d_dst, d_src, d_att, None, None, None, None
 
 
-def gatv2_attention(H_dst, H_src, att, graph, negative_slope=0.2):
+class GATv2ScoresDirected(torch.autograd.Function):
+    """GATv2Scores on any square graph: the backward's grad_H_src walks A^T (HCSPMM.gatv2_scores_backward_directed with
+    transposed_graph's row_pointers_t, column_index_t and entry_index_t)."""
+
+    @staticmethod
+    def forward(ctx, H_dst, H_src, att, negative_slope, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t):
+        att = att.contiguous()
+        logits = HCSPMM.gatv2_scores(H_dst, H_src, att, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t = ctx.saved_tensors
+        d_dst, d_src, d_att = HCSPMM.gatv2_scores_backward_directed(d_logits.contiguous(), H_dst, H_src, att, row_pointers,
+                                                                    column_index, row_pointers_t, column_index_t, entry_index_t,
+                                                                    ctx.negative_slope)
+        return (d_dst, d_src, d_att) + (None,) * 6
+
+
+def gatv2_attention(H_dst, H_src, att, graph, negative_slope=0.2, directed=False):
     """GATv2 attention weights alpha [heads, E] = edge softmax of GATv2Scores' logits, with autograd for H_dst, H_src and att;
     graph = the eight graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over
-    A^T)."""
+    A^T) unless directed=True: the backward then walks transposed_graph(graph)."""
+    if directed:
+        gt = transposed_graph(graph)
+        logits = GATv2ScoresDirected.apply(H_dst, H_src, att, float(negative_slope), graph[0], graph[1], gt[0], gt[1], gt[N_GRAPH])
+        return EdgeSoftmax.apply(logits, graph[0])
     perm32 = transpose_permutation_i32(graph[0], graph[1])
     logits = GATv2Scores.apply(H_dst, H_src, att, float(negative_slope), perm32, graph[0], graph[1])
     return EdgeSoftmax.apply(logits, graph[0])
@@ -409,11 +522,35 @@ class ExtremumAggregate(torch.autograd.Function):
         return (d_x, None, None) + (None,) * N_GRAPH
 
 
-def extremum_aggregate(X, graph, reduce="max"):
+class ExtremumAggregateDirected(torch.autograd.Function):
+    """ExtremumAggregate on any square graph: the forward on A, the backward (HCSPMM.forward_extremum_backward, which walks
+    whatever graph it is handed) on A^T's graph tensors and plan with entry_index_t in the place of the permutation.
+    tail = the eight graph tensors of A followed by transposed_graph's nine."""
+
+    @staticmethod
+    def forward(ctx, X, reduce, *tail):
+        fn = HCSPMM.forward_max if reduce == "max" else HCSPMM.forward_min
+        Z, arg = fn(X.contiguous(), *tail[:N_GRAPH], True)
+        ctx.save_for_backward(arg, *tail[N_GRAPH:])
+        ctx.mark_non_differentiable(arg)
+        return Z
+
+    @staticmethod
+    def backward(ctx, d_out):
+        arg, *rest = ctx.saved_tensors
+        graph_t, eid_t = rest[:N_GRAPH], rest[N_GRAPH]
+        d_x = HCSPMM.forward_extremum_backward(d_out.contiguous(), arg, eid_t, *graph_t) if ctx.needs_input_grad[0] else None
+        return (d_x, None) + (None,) * (2 * N_GRAPH + 1)
+
+
+def extremum_aggregate(X, graph, reduce="max", directed=False):
     """max / min over each row's neighbours with autograd for X (float32 [N, D]); graph = the eight graph tensors, whose
-    pattern must be symmetric (checked before any launch: the backward walks A^T).  Rows without entries give 0."""
+    pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then
+    runs on transposed_graph(graph).  Rows without entries give 0."""
     if reduce not in ("max", "min"):
         raise ValueError("reduce must be 'max' or 'min', got %r" % (reduce,))
+    if directed:
+        return ExtremumAggregateDirected.apply(X, reduce, *graph, *transposed_graph(graph))
     perm32 = transpose_permutation_i32(graph[0], graph[1])
     return ExtremumAggregate.apply(X, reduce, perm32, *graph)
 
@@ -441,10 +578,11 @@ class _Conv(torch.nn.Module):
     first_fn = hidden_fn = last_fn = None
     last_takes_output = False
 
-    def __init__(self, input_dim, output_dim, fixed=0):
+    def __init__(self, input_dim, output_dim, fixed=0, directed=False):
         super().__init__()
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
         self.fixed = fixed
+        self.directed = bool(directed)  # the edge_weight path only: the binary layer functions aggregate with A, as the reference
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights.size(1))
@@ -459,8 +597,8 @@ class _Conv(torch.nn.Module):
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         if edge_weight is not None:
             if self.aggregate_first:
-                return _Update.apply(weighted_aggregate(X, edge_weight, graph), self.weights)
-            return weighted_aggregate(_Update.apply(X, self.weights), edge_weight, graph)
+                return _Update.apply(weighted_aggregate(X, edge_weight, graph, self.directed), self.weights)
+            return weighted_aggregate(_Update.apply(X, self.weights), edge_weight, graph, self.directed)
         if self.fixed == 0:
             return self.hidden_fn.apply(X, self.weights, *graph)
         if self.fixed == 2:
@@ -487,7 +625,8 @@ class GATConv(torch.nn.Module):
     -> mean_k out_k  [N, output_dim].  The per-node scores <a_dst_k, h_k> and <a_src_k, h_k> go node-major [N, heads] into
     gat_attention, which computes every head's logits and softmax in one launch and their backward in two (no per-entry
     torch op); the backward is autograd over these pieces.  _Conv's call signature, so that Net builds it; the attention
-    weights are the edge values, so edge_weight is refused.  The pattern must be symmetric.
+    weights are the edge values, so edge_weight is refused.  The pattern must be symmetric unless directed=True (message
+    passing over a directed edge_index: the backward runs on transposed_graph).
 
     concat=True concatenates the heads instead -> [N, heads * output_dim] (the hidden layers of the GAT paper): one
     update X W_cat for all heads, both scores as one product H A_blk (A_blk block-diagonal [heads * output_dim, 2 heads]
@@ -495,9 +634,10 @@ class GATConv(torch.nn.Module):
     gat_attention, and one multi-head aggregation (edge_weighted_aggregate_heads).  The kernels need output_dim % 4 == 0.
     The parameters are the same in both modes, so a state dict loads into either."""
 
-    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False):
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, directed=False):
         super().__init__()
         self.fixed, self.heads, self.negative_slope, self.concat = fixed, int(heads), float(negative_slope), bool(concat)
+        self.directed = bool(directed)
         if self.concat and output_dim % 4 != 0:
             raise ValueError("GATConv(concat=True) needs output_dim (the width of one head) to be a multiple of 4, got %d"
                              % output_dim)
@@ -516,16 +656,17 @@ class GATConv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("GATConv computes its edge values from the features: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
-        transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        if not self.directed:
+            transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
         if self.concat:
             return self._forward_concat(X, graph)
         hs = [_Update.apply(X, self.weights[k]) for k in range(self.heads)]
         s_dst = torch.stack([h @ self.a_dst[k] for k, h in enumerate(hs)], 1)  # [N, heads]
         s_src = torch.stack([h @ self.a_src[k] for k, h in enumerate(hs)], 1)
-        alpha = gat_attention(s_dst, s_src, graph, self.negative_slope)  # [heads, E]
-        out = edge_weighted_aggregate(hs[0], alpha[0], graph)
+        alpha = gat_attention(s_dst, s_src, graph, self.negative_slope, self.directed)  # [heads, E]
+        out = edge_weighted_aggregate(hs[0], alpha[0], graph, self.directed)
         for k in range(1, self.heads):
-            out = out + edge_weighted_aggregate(hs[k], alpha[k], graph)
+            out = out + edge_weighted_aggregate(hs[k], alpha[k], graph, self.directed)
         return out / self.heads if self.heads > 1 else out
 
     def _forward_concat(self, X, graph):
@@ -534,8 +675,8 @@ class GATConv(torch.nn.Module):
         h = _Update.apply(X, w_cat)  # [N, heads * dout]
         a_blk = torch.cat([torch.block_diag(*self.a_dst.unsqueeze(2)), torch.block_diag(*self.a_src.unsqueeze(2))], 1)
         s = _Update.apply(h, a_blk)  # [N, 2 heads]: s_dst | s_src
-        alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope)  # [heads, E]
-        return edge_weighted_aggregate_heads(h, alpha, graph)
+        alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope, self.directed)  # [heads, E]
+        return edge_weighted_aggregate_heads(h, alpha, graph, self.directed)
 
 
 class GATv2Conv(torch.nn.Module):
@@ -548,11 +689,13 @@ class GATv2Conv(torch.nn.Module):
     mean [N, output_dim].  share_weights=True uses one projection for both roles (H_dst = H_src, [N, heads * output_dim]).
     No per-entry torch op and no [E, D] tensor in either pass.  The kernels need output_dim % 4 == 0.  _Conv's call
     signature, so that Net builds it; the attention weights are the edge values, so edge_weight is refused.  The pattern must
-    be symmetric."""
+    be symmetric unless directed=True (the backward then runs on transposed_graph)."""
 
-    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, share_weights=False):
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, share_weights=False,
+                 directed=False):
         super().__init__()
         self.fixed, self.heads, self.negative_slope = fixed, int(heads), float(negative_slope)
+        self.directed = bool(directed)
         self.concat, self.share_weights, self.output_dim = bool(concat), bool(share_weights), int(output_dim)
         if self.heads < 1:
             raise ValueError("GATv2Conv needs heads >= 1, got %d" % self.heads)
@@ -574,13 +717,14 @@ class GATv2Conv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("GATv2Conv computes its edge values from the features: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
-        transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        if not self.directed:
+            transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
         width = self.heads * self.output_dim
         h = _Update.apply(X, self.weights)
         h_src = h[:, :width]
         h_dst = h_src if self.share_weights else h[:, width:]
-        alpha = gatv2_attention(h_dst, h_src, self.att, graph, self.negative_slope)  # [heads, E]
-        out = edge_weighted_aggregate_heads(h_src, alpha, graph)  # [N, heads * output_dim]
+        alpha = gatv2_attention(h_dst, h_src, self.att, graph, self.negative_slope, self.directed)  # [heads, E]
+        out = edge_weighted_aggregate_heads(h_src, alpha, graph, self.directed)  # [N, heads * output_dim]
         if self.concat or self.heads == 1:
             return out
         return out.view(out.size(0), self.heads, self.output_dim).mean(1)
@@ -591,13 +735,14 @@ class SAGEConv(torch.nn.Module):
       "max" / "min"  extremum_aggregate (GraphSAGE-pool without the pre-MLP, PyG aggr="max" / "min");
       "mean"         edge_weighted_aggregate with HCSPMM.edge_norm(..., "mean") values, computed once per graph.
     Both products run on _Update (the library's update and weight-gradient kernels).  _Conv's call signature, so that Net
-    builds it; the aggregation is fixed by `aggr`, so edge_weight is refused.  The pattern must be symmetric."""
+    builds it; the aggregation is fixed by `aggr`, so edge_weight is refused.  The pattern must be symmetric unless
+    directed=True (the backward then runs on transposed_graph)."""
 
-    def __init__(self, input_dim, output_dim, fixed=0, aggr="max"):
+    def __init__(self, input_dim, output_dim, fixed=0, aggr="max", directed=False):
         super().__init__()
         if aggr not in ("max", "min", "mean"):
             raise ValueError("SAGEConv aggr must be 'max', 'min' or 'mean', got %r" % (aggr,))
-        self.fixed, self.aggr = fixed, aggr
+        self.fixed, self.aggr, self.directed = fixed, aggr, bool(directed)
         self.weights_root = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self.weights_neigh = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self._mean = None  # (row_pointers, column_index, values) of the last graph
@@ -620,7 +765,7 @@ class SAGEConv(torch.nn.Module):
             raise ValueError("SAGEConv aggregates with its own `aggr`: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         if self.aggr == "mean":
-            agg = edge_weighted_aggregate(X, self._mean_values(row_pointers, column_index), graph)
+            agg = edge_weighted_aggregate(X, self._mean_values(row_pointers, column_index), graph, self.directed)
         else:
-            agg = extremum_aggregate(X, graph, self.aggr)
+            agg = extremum_aggregate(X, graph, self.aggr, self.directed)
         return _Update.apply(X, self.weights_root) + _Update.apply(agg, self.weights_neigh)

@@ -62,7 +62,13 @@ def parse_args(argv=None):
     p.add_argument("--aggr", type=str, default="max", choices=["max", "min", "mean"], help="aggregation of --model sage")
     p.add_argument("--gat-concat", action="store_true",
                    help="--model gat / gatv2: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
+    # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
+    p.add_argument("--directed", action="store_true",
+                   help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
     args = p.parse_args(argv)
+    if args.directed and args.model in ("gcn", "gin") and args.norm == "none":
+        p.error("--directed with --model %s needs --norm: the binary layer functions aggregate with A in the backward, as the "
+                "reference does" % args.model)
     if args.model in ("gat", "gatv2") and args.norm != "none":
         p.error("--norm does not apply to --model %s: its edge values are the attention weights" % args.model)
     if args.model == "sage" and args.norm != "none":
@@ -166,22 +172,26 @@ def main(argv=None):
     if args.single_kernel:
         return SAG(*graph).profile(dataset.x)
 
-    conv_cls = {"gcn": GCNConv, "gin": GINConv}.get(args.model)
+    directed = args.directed
+    if args.model in ("gcn", "gin"):
+        def conv_cls(input_dim, output_dim, fixed):
+            return (GCNConv if args.model == "gcn" else GINConv)(input_dim, output_dim, fixed, directed=directed)
     if args.model == "sage":
         def conv_cls(input_dim, output_dim, fixed):
-            return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr)
+            return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated
-                return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True)
-            return GATConv(input_dim, output_dim, fixed, heads=args.heads)
+                return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True, directed=directed)
+            return GATConv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
     if args.model == "gatv2":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:
-                return GATv2Conv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True)
+                return GATv2Conv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True, directed=directed)
             if output_dim % 4 != 0:  # (the class count of the last layer)
-                return _FirstColumns(GATv2Conv(input_dim, (output_dim + 3) // 4 * 4, fixed, heads=args.heads), output_dim)
-            return GATv2Conv(input_dim, output_dim, fixed, heads=args.heads)
+                return _FirstColumns(GATv2Conv(input_dim, (output_dim + 3) // 4 * 4, fixed, heads=args.heads, directed=directed),
+                                     output_dim)
+            return GATv2Conv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 

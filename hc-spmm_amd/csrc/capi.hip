@@ -215,11 +215,14 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
                  const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
                  size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr,
-                 int heads = 0) {
+                 int heads = 0, const int32_t* vindex = nullptr, int64_t num_values = 0) {
   if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
   if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
   // heads > 0: the multi-head weighted product (fp32, Dh = D / heads columns per head, Dh % 4 == 0)
-  if (heads > 0 && (dtype != HCSPMM_DTYPE_F32 || !values || fused || D % heads != 0 || (D / heads) % 4 != 0)) return HCSPMM_EINVAL;
+  // vindex: the indexed form (entry e weighs values[h * num_values + vindex[e]]); one head then takes any D
+  if (heads > 0 && (dtype != HCSPMM_DTYPE_F32 || !values || fused || D % heads != 0 ||
+                    ((D / heads) % 4 != 0 && !(vindex && heads == 1))))
+    return HCSPMM_EINVAL;
   if (N == 0) return HCSPMM_OK;
   if (!X || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
   if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
@@ -286,7 +289,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     if (values) {
       if (fused) return HCSPMM_EINVAL;
       const hcspmm::WPlanArgs wa{a, values, rowptr, ph->segment_len};
-      if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads}, vec, stream);
+      if (vindex) e = hcspmm::launch_plan_wi_f32(hcspmm::WIPlanArgs{{wa, (long long)num_values, D / heads}, vindex}, vec, stream);
+      else if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads}, vec, stream);
       else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_w_f16(wa, vec, stream)
                                       : hcspmm::launch_plan_w_bf16(wa, vec, stream);
@@ -315,7 +319,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, nullptr);
     if (values) {
       const hcspmm::WWindowArgs wa{a, values};
-      if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads}, vec, stream);
+      if (vindex) e = hcspmm::launch_window_wi_f32(hcspmm::WIWindowArgs{{wa, (long long)num_values, D / heads}, vindex}, vec, stream);
+      else if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads}, vec, stream);
       else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_w_f16(wa, vec, stream)
                                       : hcspmm::launch_window_w_bf16(wa, vec, stream);
@@ -361,6 +366,22 @@ extern "C" int hcspmm_forward_weighted_heads(const void* X, int64_t x_rows, int6
   if ((long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
   return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
                       plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads);
+}
+
+// Multi-head edge-weighted product with indexed values (spmm_weighted_indexed.hip): hcspmm_forward_weighted_heads's checks and
+// launch decisions, entry e of head h weighing values[h * num_values + value_index[e]].
+extern "C" int hcspmm_forward_weighted_indexed(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                               const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                               const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                               const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                               void* workspace, size_t workspace_bytes, void* stream_v, const float* values,
+                                               int heads, const int32_t* value_index, int64_t num_values) {
+  if (!values || heads <= 0 || num_values < 0 || (E > 0 && (!value_index || num_values == 0))) return HCSPMM_EINVAL;
+  if (num_values > INT32_MAX || num_values > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  static const int32_t no_entries = 0;  // E = 0: nothing is read through the index, which may be NULL
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d,
+                      ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads,
+                      value_index ? value_index : &no_entries, num_values);
 }
 
 namespace {
@@ -560,18 +581,40 @@ extern "C" int hcspmm_gat_attention(const float* s_dst, const float* s_src, int6
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+namespace {
+// rowptr_t / perm / n_t: the rows of A^T (the pattern-symmetric entry point passes A's own and N)
+int gat_backward_impl(const float* alpha, const float* grad_alpha, const float* s_dst, const float* s_src, float slope,
+                      const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* perm, int64_t n_t, int64_t N,
+                      int64_t E, int heads, float* grad_scores, float* grad_s_dst, float* grad_s_src, void* stream_v) {
+  if (N < 0 || E < 0 || n_t < 0 || heads <= 0 || !rowptr || !rowptr_t || !__builtin_isfinite(slope)) return HCSPMM_EINVAL;
+  if ((N > 0 && (!s_dst || !grad_s_dst)) || (n_t > 0 && (!s_src || !grad_s_src))) return HCSPMM_EINVAL;
+  if (E > 0 && (!alpha || !grad_alpha || !col || !perm || !grad_scores || N == 0 || n_t == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || n_t > INT32_MAX - 16 || E > INT32_MAX || E * heads > INT64_MAX / 4 || N * heads > INT64_MAX / 4 ||
+      n_t * heads > INT64_MAX / 4)
+    return HCSPMM_ERANGE;
+  const hcspmm::GatArgs a{s_dst, s_src, alpha, grad_alpha, rowptr, col, perm, grad_scores, grad_s_dst, grad_s_src, slope, (int)N,
+                          heads, (long long)E, rowptr_t, (int)n_t};
+  const hipError_t e = hcspmm::launch_gat_attention_backward(a, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+}  // namespace
+
 extern "C" int hcspmm_gat_attention_backward(const float* alpha, const float* grad_alpha, const float* s_dst, const float* s_src,
                                              float slope, const int32_t* rowptr, const int32_t* col, const int32_t* perm, int64_t N,
                                              int64_t E, int heads, float* grad_scores, float* grad_s_dst, float* grad_s_src,
                                              void* stream_v) {
-  if (N < 0 || E < 0 || heads <= 0 || !rowptr || !__builtin_isfinite(slope)) return HCSPMM_EINVAL;
-  if (N > 0 && (!s_dst || !s_src || !grad_s_dst || !grad_s_src)) return HCSPMM_EINVAL;
-  if (E > 0 && (!alpha || !grad_alpha || !col || !perm || !grad_scores || N == 0)) return HCSPMM_EINVAL;
-  if (N > INT32_MAX - 16 || E > INT32_MAX || E * heads > INT64_MAX / 4 || N * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
-  const hcspmm::GatArgs a{s_dst, s_src, alpha, grad_alpha, rowptr, col, perm, grad_scores, grad_s_dst, grad_s_src, slope, (int)N,
-                          heads, (long long)E};
-  const hipError_t e = hcspmm::launch_gat_attention_backward(a, reinterpret_cast<hipStream_t>(stream_v));
-  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+  return gat_backward_impl(alpha, grad_alpha, s_dst, s_src, slope, rowptr, col, rowptr, perm, N, N, E, heads, grad_scores,
+                           grad_s_dst, grad_s_src, stream_v);
+}
+
+// The same launches walking A^T's rows for the column side (hcspmm_transpose_graph): no symmetry needed.
+extern "C" int hcspmm_gat_attention_backward_directed(const float* alpha, const float* grad_alpha, const float* s_dst,
+                                                      const float* s_src, float slope, const int32_t* rowptr, const int32_t* col,
+                                                      const int32_t* rowptr_t, const int32_t* entry_t, int64_t src_rows, int64_t N,
+                                                      int64_t E, int heads, float* grad_scores, float* grad_s_dst,
+                                                      float* grad_s_src, void* stream_v) {
+  return gat_backward_impl(alpha, grad_alpha, s_dst, s_src, slope, rowptr, col, rowptr_t, entry_t, src_rows, N, E, heads,
+                           grad_scores, grad_s_dst, grad_s_src, stream_v);
 }
 
 // GATv2 attention logits (gatv2_attention.hip).  Every array with at least one element needs a pointer; column ids (and
@@ -603,28 +646,53 @@ extern "C" size_t hcspmm_gatv2_backward_workspace_bytes(int64_t N, int64_t E, in
   return (size_t)hcspmm::gatv2_grad_blocks((long long)N, D) * (size_t)D * sizeof(float);
 }
 
-extern "C" int hcspmm_gatv2_scores_backward(const float* grad_logits, const float* H_dst, int64_t ld_dst, const float* H_src,
-                                            int64_t ld_src, const float* att, float slope, const int32_t* rowptr,
-                                            const int32_t* col, const int32_t* perm, int64_t N, int64_t E, int D, int heads,
-                                            float* grad_dst, int64_t ld_gdst, float* grad_src, int64_t ld_gsrc, float* grad_att,
-                                            void* workspace, size_t workspace_bytes, void* stream_v) {
-  if (N < 0 || E < 0 || !gatv2_shape_ok(D, heads) || ld_dst < D || ld_src < D || ld_gdst < D || ld_gsrc < D || !rowptr || !att ||
-      !grad_att || !__builtin_isfinite(slope))
+namespace {
+// rowptr_t / col_t / perm / n_t: A^T (the pattern-symmetric entry point passes A's own arrays and N)
+int gatv2_backward_impl(const float* grad_logits, const float* H_dst, int64_t ld_dst, const float* H_src, int64_t ld_src,
+                        const float* att, float slope, const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t,
+                        const int32_t* col_t, const int32_t* perm, int64_t n_t, int64_t N, int64_t E, int D, int heads,
+                        float* grad_dst, int64_t ld_gdst, float* grad_src, int64_t ld_gsrc, float* grad_att, void* workspace,
+                        size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || E < 0 || n_t < 0 || !gatv2_shape_ok(D, heads) || ld_dst < D || ld_src < D || ld_gdst < D || ld_gsrc < D || !rowptr ||
+      !rowptr_t || !att || !grad_att || !__builtin_isfinite(slope))
     return HCSPMM_EINVAL;
-  if (N > 0 && (!H_dst || !H_src || !grad_dst || !grad_src)) return HCSPMM_EINVAL;
-  if (E > 0 && (!grad_logits || !col || !perm || N == 0)) return HCSPMM_EINVAL;
-  if (N > INT32_MAX - 2048 || E > INT32_MAX - 4096 || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  if ((N > 0 && (!H_dst || !grad_dst)) || (n_t > 0 && (!H_src || !grad_src))) return HCSPMM_EINVAL;
+  if (E > 0 && (!grad_logits || !col || !col_t || !perm || N == 0 || n_t == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 2048 || n_t > INT32_MAX - 2048 || E > INT32_MAX - 4096 || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
   const size_t need = hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads);
   if (workspace_bytes < need) return HCSPMM_EWORKSPACE;
   if (need > 0 && !workspace) return HCSPMM_EINVAL;
   hcspmm::Gatv2Args a{};
   a.H_dst = H_dst, a.H_src = H_src, a.att = att, a.g = grad_logits, a.rowptr = rowptr, a.col = col, a.perm = perm;
+  a.rowptr_t = rowptr_t, a.col_t = col_t, a.n_t = (int)n_t;
   a.grad_dst = grad_dst, a.grad_src = grad_src, a.grad_att = grad_att, a.partial = static_cast<float*>(workspace);
   a.ld_dst = (size_t)ld_dst, a.ld_src = (size_t)ld_src, a.ld_gdst = (size_t)ld_gdst, a.ld_gsrc = (size_t)ld_gsrc;
   a.slope = slope, a.N = (int)N, a.D = D, a.heads = heads, a.E = (long long)E;
   // E = 0 takes the same launches: every row is empty, so all three gradients come out as zeros
   const hipError_t e = hcspmm::launch_gatv2_backward(a, reinterpret_cast<hipStream_t>(stream_v));
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+}  // namespace
+
+extern "C" int hcspmm_gatv2_scores_backward(const float* grad_logits, const float* H_dst, int64_t ld_dst, const float* H_src,
+                                            int64_t ld_src, const float* att, float slope, const int32_t* rowptr,
+                                            const int32_t* col, const int32_t* perm, int64_t N, int64_t E, int D, int heads,
+                                            float* grad_dst, int64_t ld_gdst, float* grad_src, int64_t ld_gsrc, float* grad_att,
+                                            void* workspace, size_t workspace_bytes, void* stream_v) {
+  return gatv2_backward_impl(grad_logits, H_dst, ld_dst, H_src, ld_src, att, slope, rowptr, col, rowptr, col, perm, N, N, E, D, heads,
+                             grad_dst, ld_gdst, grad_src, ld_gsrc, grad_att, workspace, workspace_bytes, stream_v);
+}
+
+// The same launches walking A^T (hcspmm_transpose_graph) for grad_H_src: no symmetry needed.
+extern "C" int hcspmm_gatv2_scores_backward_directed(const float* grad_logits, const float* H_dst, int64_t ld_dst,
+                                                     const float* H_src, int64_t ld_src, const float* att, float slope,
+                                                     const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t,
+                                                     const int32_t* col_t, const int32_t* entry_t, int64_t src_rows, int64_t N,
+                                                     int64_t E, int D, int heads, float* grad_dst, int64_t ld_gdst, float* grad_src,
+                                                     int64_t ld_gsrc, float* grad_att, void* workspace, size_t workspace_bytes,
+                                                     void* stream_v) {
+  return gatv2_backward_impl(grad_logits, H_dst, ld_dst, H_src, ld_src, att, slope, rowptr, col, rowptr_t, col_t, entry_t, src_rows, N,
+                             E, D, heads, grad_dst, ld_gdst, grad_src, ld_gsrc, grad_att, workspace, workspace_bytes, stream_v);
 }
 
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,

@@ -186,11 +186,11 @@ __global__ __launch_bounds__(kSoftmaxThreads) void gat_attention_rows_kernel(Gat
   });
 }
 
-// backward, launch 2: grad_s_src[c] = sum over row c's entries e' of g[perm[e']]
+// backward, launch 2: grad_s_src[c] = sum over the entries e' of row c of A^T of g[perm[e']]
 template <int HG>
 __global__ __launch_bounds__(kSoftmaxThreads) void gat_attention_cols_kernel(GatArgs a) {
   const int H = a.heads;
-  walk_rows<HG>(a.rowptr, a.N, H, [&](int r, long long b, int n, int t, int nt, int h0, auto fold) {
+  walk_rows<HG>(a.rowptr_t, a.n_t, H, [&](int r, long long b, int n, int t, int nt, int h0, auto fold) {
     const float* __restrict__ g = a.out + (long long)h0 * a.E;
     float acc[HG];
 #pragma unroll
@@ -211,9 +211,9 @@ __global__ __launch_bounds__(kSoftmaxThreads) void gat_attention_cols_kernel(Gat
 // heads per group: the largest of 4, 3, 2, 1 that divides heads (heads 1-4: one group, each column id loaded once)
 inline int gat_group(int heads) { return heads % 4 == 0 ? 4 : heads % 3 == 0 ? 3 : heads % 2 == 0 ? 2 : 1; }
 
-#define HCSPMM_GAT_LAUNCH(KERNEL, ARGS, STREAM)                                                             \
+#define HCSPMM_GAT_LAUNCH(KERNEL, ARGS, ROWS, STREAM)                                                       \
   do {                                                                                                      \
-    const unsigned blocks_ = (unsigned)(((ARGS).N + kSoftmaxThreads - 1) / kSoftmaxThreads);                \
+    const unsigned blocks_ = (unsigned)(((ROWS) + kSoftmaxThreads - 1) / kSoftmaxThreads);                  \
     switch (gat_group((ARGS).heads)) {                                                                      \
       case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(blocks_), dim3(kSoftmaxThreads), 0, STREAM, ARGS); break;  \
       case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(blocks_), dim3(kSoftmaxThreads), 0, STREAM, ARGS); break;  \
@@ -227,17 +227,19 @@ inline int gat_group(int heads) { return heads % 4 == 0 ? 4 : heads % 3 == 0 ? 3
 hipError_t launch_gat_attention(const GatArgs& a, hipStream_t stream) {
   if (a.heads <= 0) return hipErrorInvalidValue;
   if (a.N == 0 || a.E == 0) return hipSuccess;
-  HCSPMM_GAT_LAUNCH(gat_attention_kernel, a, stream);
+  HCSPMM_GAT_LAUNCH(gat_attention_kernel, a, a.N, stream);
   return hipGetLastError();
 }
 
 hipError_t launch_gat_attention_backward(const GatArgs& a, hipStream_t stream) {
   if (a.heads <= 0) return hipErrorInvalidValue;
-  if (a.N == 0) return hipSuccess;
-  HCSPMM_GAT_LAUNCH(gat_attention_rows_kernel, a, stream);  // every row writes its grad_s_dst, empty rows zeros
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  HCSPMM_GAT_LAUNCH(gat_attention_cols_kernel, a, stream);
+  if (a.N == 0 && a.n_t == 0) return hipSuccess;
+  if (a.N > 0) {
+    HCSPMM_GAT_LAUNCH(gat_attention_rows_kernel, a, a.N, stream);  // every row writes its grad_s_dst, empty rows zeros
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (a.n_t > 0) HCSPMM_GAT_LAUNCH(gat_attention_cols_kernel, a, a.n_t, stream);
   return hipGetLastError();
 }
 

@@ -235,7 +235,7 @@ __device__ __forceinline__ f32x4 block_fold4(f32x4 v, float (*red)[L * 4], int w
 }
 
 // SIDE 0: grad_H_dst (own = H_dst[r], gathered = H_src[col], g[e]) and the att partials; SIDE 1: grad_H_src (own =
-// H_src[r], gathered = H_dst[col], g[perm[e]])
+// H_src[c], gathered = H_dst[col_t], g[perm[e]], over the rows of A^T)
 template <int SIDE, int L>
 __global__ __launch_bounds__(kGradThreads) void gatv2_grad_kernel(Gatv2Args a) {
   constexpr int G = 64 / L, NG = kGradWaves * G, R = NG * kGradRowsPerGroup;
@@ -243,14 +243,15 @@ __global__ __launch_bounds__(kGradThreads) void gatv2_grad_kernel(Gatv2Args a) {
   __shared__ unsigned long long longmask[kMaskIters * kGradWaves], midmask[kMaskIters * kGradWaves];
   __shared__ float red[kGradWaves][L * 4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane / L, sub = lane % L, gid = wid * G + g;
-  const int N = a.N, D = a.D, Dh = a.D / a.heads;
+  const int N = SIDE == 0 ? a.N : a.n_t, D = a.D, Dh = a.D / a.heads;
   const float slope = a.slope;
   const float* __restrict__ own = SIDE == 0 ? a.H_dst : a.H_src;
   const float* __restrict__ oth = SIDE == 0 ? a.H_src : a.H_dst;
   const size_t ld_own = SIDE == 0 ? a.ld_dst : a.ld_src, ld_oth = SIDE == 0 ? a.ld_src : a.ld_dst;
   float* __restrict__ out = SIDE == 0 ? a.grad_dst : a.grad_src;
   const size_t ld_out = SIDE == 0 ? a.ld_gdst : a.ld_gsrc;
-  const int* __restrict__ rowptr = a.rowptr;
+  const int* __restrict__ rowptr = SIDE == 0 ? a.rowptr : a.rowptr_t;
+  const int* __restrict__ colp = SIDE == 0 ? a.col : a.col_t;
   const int n_tiles = (N + R - 1) / R;
   for (int cb = 0; cb < D; cb += L * 4) {  // one pass unless D > 256
     const int c = cb + sub * 4;
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(kGradThreads) void gatv2_grad_kernel(Gatv2Args a) {
           const int iu = i + u * stride;
           cc[u] = -1;
           if (iu < n) {
-            cc[u] = a.col[b + iu];
+            cc[u] = colp[b + iu];
             ge[u] = SIDE == 0 ? b + iu : (long long)a.perm[b + iu];
           }
         }
@@ -407,11 +408,16 @@ __global__ __launch_bounds__(kFoldCols* kFoldParts) void gatv2_att_fold_kernel(c
 
 template <int L>
 hipError_t launch_grad_L(const Gatv2Args& a, hipStream_t stream) {
-  const unsigned blocks = (unsigned)gatv2_grad_blocks(a.N, a.D);
-  hipLaunchKernelGGL((gatv2_grad_kernel<0, L>), dim3(blocks), dim3(kGradThreads), 0, stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((gatv2_grad_kernel<1, L>), dim3(blocks), dim3(kGradThreads), 0, stream, a);
+  if (a.N > 0) {
+    const unsigned blocks = (unsigned)gatv2_grad_blocks(a.N, a.D);
+    hipLaunchKernelGGL((gatv2_grad_kernel<0, L>), dim3(blocks), dim3(kGradThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (a.n_t > 0) {
+    const unsigned blocks_t = (unsigned)gatv2_grad_blocks(a.n_t, a.D);
+    hipLaunchKernelGGL((gatv2_grad_kernel<1, L>), dim3(blocks_t), dim3(kGradThreads), 0, stream, a);
+  }
   return hipGetLastError();
 }
 
@@ -445,7 +451,7 @@ hipError_t launch_gatv2_scores(const Gatv2Args& a, hipStream_t stream) {
 hipError_t launch_gatv2_backward(const Gatv2Args& a, hipStream_t stream) {
   if (a.heads <= 0 || a.D <= 0 || a.D % a.heads != 0 || (a.D / a.heads) % 4 != 0) return hipErrorInvalidValue;
   hipError_t e = hipSuccess;
-  if (a.N > 0) {
+  if (a.N > 0 || a.n_t > 0) {
     switch (sddmm_L(a.D, 4)) {
       case 1: e = launch_grad_L<1>(a, stream); break;
       case 2: e = launch_grad_L<2>(a, stream); break;

@@ -111,6 +111,19 @@ struct WHWindowArgs {
 };
 hipError_t launch_plan_wh_f32(const WHPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_wh_f32(const WHWindowArgs& a, int vec, hipStream_t stream);
+// the multi-head weighted forms with indexed values (spmm_weighted_indexed.hip, hcspmm_forward_weighted_indexed): entry e of
+// head h weighs values[h * h.E + vindex[e]], h.E = values per head.  fp32; vec 4 with the heads rules, or one head (dh = D)
+// with any vec launch_plan_w_f32 takes
+struct WIPlanArgs {
+  WHPlanArgs h;
+  const int* vindex;  // [entries]
+};
+struct WIWindowArgs {
+  WHWindowArgs h;
+  const int* vindex;
+};
+hipError_t launch_plan_wi_f32(const WIPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_wi_f32(const WIWindowArgs& a, int vec, hipStream_t stream);
 // values[e] = 1/sqrt(deg(row e) * deg(col e)) (kind 0) or 1/deg(row e) (kind 1), deg = row length
 hipError_t launch_edge_norm(const int* rowptr, const int* col, int N, long long E, int kind, float* values, hipStream_t stream);
 
@@ -184,13 +197,17 @@ struct GatArgs {
   const float* grad_alpha;  // backward: [heads][E]
   const int* rowptr;        // [N + 1]
   const int* col;           // [E]
-  const int* perm;          // backward: [E], hcspmm_transpose_permutation's
+  const int* perm;          // backward: [E], hcspmm_transpose_permutation's or hcspmm_transpose_graph's entry_index_t
   float* out;               // forward: alpha; backward: g
   float* grad_s_dst;        // backward: [N][heads]
-  float* grad_s_src;        // backward: [N][heads]
+  float* grad_s_src;        // backward: [n_t][heads]
   float slope;
   int N, heads;
   long long E;
+  // backward, column side: the rows of A^T and, per entry of A^T, its position in A (perm).  The pattern-symmetric entry point
+  // passes A's own row pointers and N
+  const int* rowptr_t;      // [n_t + 1]
+  int n_t;
 };
 hipError_t launch_gat_attention(const GatArgs& a, hipStream_t stream);
 hipError_t launch_gat_attention_backward(const GatArgs& a, hipStream_t stream);
@@ -205,7 +222,7 @@ struct Gatv2Args {
   const float* g;      // backward: [heads][E]
   const int* rowptr;   // [N + 1]
   const int* col;      // [E]
-  const int* perm;     // backward: [E], hcspmm_transpose_permutation's
+  const int* perm;     // backward: [E], hcspmm_transpose_permutation's or hcspmm_transpose_graph's entry_index_t
   float* out;          // forward: [heads][E]
   float* grad_dst;     // backward: [N][ld_gdst]
   float* grad_src;     // backward: [N][ld_gsrc]
@@ -215,6 +232,11 @@ struct Gatv2Args {
   float slope;
   int N, D, heads;
   long long E;
+  // backward, grad_src side: A^T's rows and column ids (the rows of A) and, per entry of A^T, its position in A (perm).  The
+  // pattern-symmetric entry point passes A's own arrays and N
+  const int* rowptr_t;  // [n_t + 1]
+  const int* col_t;     // [E]
+  int n_t;
 };
 long long gatv2_grad_blocks(long long N, int D);
 hipError_t launch_gatv2_scores(const Gatv2Args& a, hipStream_t stream);

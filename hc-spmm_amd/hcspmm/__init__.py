@@ -27,6 +27,7 @@ __all__ = [
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
     "gatv2_scores", "gatv2_scores_backward",
+    "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
@@ -547,6 +548,47 @@ def forward_weighted_heads(X, values, row_pointers, column_index, blockPartition
     return [Z]
 
 
+def forward_weighted_indexed(X, values, value_index, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow,
+                             hybrid_type, row_nzr, col_nzr):
+    """forward_weighted_heads whose weight for entry e is values[h, value_index[e]] -> [Z]: values [heads, V] (or [V]: one
+    head, any D forward_weighted takes), value_index int32 [E] with every index in [0, V).  Bit for bit
+    forward_weighted_heads(X, values[:, value_index]) without the gathered copy (hcspmm.h hcspmm_forward_weighted_indexed)."""
+    L = lib()
+    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                             row_nzr, False, dtypes=tuple(_DTYPES))
+    _check_input(values, "values")
+    _check_input(value_index, "value_index")
+    if values.dtype != torch.float32:
+        raise RuntimeError("values must be a float32 tensor")
+    if values.dim() not in (1, 2) or (values.dim() == 2 and values.size(0) < 1):
+        raise RuntimeError("values must be [heads, V] or [V], got %s" % (tuple(values.shape),))
+    if value_index.dtype != torch.int32 or value_index.dim() != 1 or value_index.numel() != E:
+        raise RuntimeError("value_index must be an int32 [E] tensor with E = %d, got %s %s"
+                           % (E, value_index.dtype, tuple(value_index.shape)))
+    if values.device != X.device or value_index.device != X.device:
+        raise RuntimeError("values and value_index must be on the device of the input")
+    heads, V = (1, values.size(0)) if values.dim() == 1 else tuple(values.shape)
+    if X.dtype != torch.float32:
+        raise RuntimeError("the indexed kernels take float32 features only, got %s" % X.dtype)
+    if heads > 1:
+        _check_heads_width(D, heads, X.dtype)
+    Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(L.hcspmm_forward_weighted_indexed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
+                                                _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                                _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                                ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
+                                                _ptr(values if V else torch.zeros(1, device=X.device)), heads,
+                                                _ptr(value_index), V))
+    return [Z]
+
+
 def _extremum(X, graph, reduce, return_arg):
     L = lib()
     row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr = graph
@@ -657,6 +699,23 @@ def transpose_permutation(row_pointers, column_index):
     perm = torch.empty(E, dtype=torch.int32)
     check(lib().hcspmm_transpose_permutation(_ptr(rp), _ptr(col), N, E, _ptr(perm)))
     return perm.to(device=row_pointers.device, dtype=torch.int64)
+
+
+def transpose_graph(row_pointers, column_index, num_cols=None):
+    """A^T of any CSR graph (hcspmm_transpose_graph, a host counting sort) -> (row_pointers_t, column_index_t,
+    entry_index_t), int32 on the inputs' device: entry e_t of row j of A^T is A's entry (i, j) with i = column_index_t[e_t]
+    at CSR position entry_index_t[e_t].  num_cols: the columns of a rectangular block (default: square)."""
+    rp = _i32_host(row_pointers)
+    col = _i32_host(column_index)
+    N, E = rp.numel() - 1, col.numel()
+    M = N if num_cols is None else int(num_cols)
+    if M < 0:
+        raise RuntimeError("num_cols must not be negative, got %d" % M)
+    rp_t = torch.empty(M + 1, dtype=torch.int32)
+    col_t, eid_t = torch.empty(E, dtype=torch.int32), torch.empty(E, dtype=torch.int32)
+    check(lib().hcspmm_transpose_graph(_ptr(rp), _ptr(col), N, M, E, _ptr(rp_t), _ptr(col_t), _ptr(eid_t)))
+    dev = row_pointers.device
+    return rp_t.to(dev), col_t.to(dev), eid_t.to(dev)
 
 
 def _check_view(t, name, dtype=None):
@@ -844,6 +903,43 @@ def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column
     return grad_s_dst, grad_s_src, grad_scores
 
 
+def _transposed_i32(t, name, n, device):
+    _check_input(t, name)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
+        raise RuntimeError("%s must be an int32 tensor of %d elements, got %s %s" % (name, n, t.dtype, tuple(t.shape)))
+    if t.device != device:
+        raise RuntimeError("%s must be on the device of row_pointers" % name)
+    return t
+
+
+def gat_attention_backward_directed(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t, entry_index_t,
+                                    negative_slope=0.2):
+    """gat_attention_backward on any square graph: (row_pointers_t, entry_index_t) are transpose_graph's, and grad_s_src sums
+    over the rows of A^T (hcspmm_gat_attention_backward_directed).  With (row_pointers, perm as int32) of a pattern-symmetric
+    graph it returns gat_attention_backward's bits."""
+    N, E, src_rows, heads = _gat_graph(row_pointers, column_index, s_dst, s_src)
+    if src_rows != N:
+        raise RuntimeError("s_src has %d rows but the backward needs one per node (%d)" % (src_rows, N))
+    shape = (E,) if s_dst.dim() == 1 else (heads, E)
+    for t, n in ((alpha, "alpha"), (grad_alpha, "grad_alpha")):
+        _check_input(t, n)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise RuntimeError("%s must be float32 of shape %s, got %s %s" % (n, shape, t.dtype, tuple(t.shape)))
+        if t.device != row_pointers.device:
+            raise RuntimeError("%s must be on the device of row_pointers" % n)
+    _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
+    _transposed_i32(entry_index_t, "entry_index_t", E, row_pointers.device)
+    grad_s_dst, grad_s_src = torch.empty_like(s_dst), torch.empty_like(s_src)
+    grad_scores = torch.empty(shape, dtype=torch.float32, device=alpha.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream)
+    with _on_device(alpha.device):
+        check(lib().hcspmm_gat_attention_backward_directed(_ptr(alpha), _ptr(grad_alpha), _ptr(s_dst), _ptr(s_src),
+                                                           float(negative_slope), _ptr(row_pointers), _ptr(column_index),
+                                                           _ptr(row_pointers_t), _ptr(entry_index_t), N, N, E, heads,
+                                                           _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src), stream))
+    return grad_s_dst, grad_s_src, grad_scores
+
+
 def _gatv2_operands(H_dst, H_src, att, row_pointers, column_index):
     """-> (N, E, D, heads) of a GATv2 call: H_dst [N, D] and H_src [src_rows, D] float32 views with unit inner stride, att
     [heads, Dh] (or [Dh] for one head) contiguous, D = heads * Dh, Dh % 4 == 0"""
@@ -913,6 +1009,39 @@ def gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_i
                                              _ptr(att), float(negative_slope), _ptr(row_pointers), _ptr(column_index), _ptr(perm),
                                              N, E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D, _ptr(grad_att), _ptr(ws),
                                              ws_bytes, stream))
+    return grad_dst, grad_src, grad_att
+
+
+def gatv2_scores_backward_directed(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
+                                   entry_index_t, negative_slope=0.2):
+    """gatv2_scores_backward on any square graph: (row_pointers_t, column_index_t, entry_index_t) are transpose_graph's, and
+    grad_H_src walks the rows of A^T (hcspmm_gatv2_scores_backward_directed).  With (row_pointers, column_index, perm as
+    int32) of a pattern-symmetric graph it returns gatv2_scores_backward's bits."""
+    N, E, D, heads = _gatv2_operands(H_dst, H_src, att, row_pointers, column_index)
+    if H_src.size(0) != N:
+        raise RuntimeError("H_src has %d rows but the backward needs one per node (%d)" % (H_src.size(0), N))
+    shape = (E,) if att.dim() == 1 else (heads, E)
+    _check_input(grad_logits, "grad_logits")
+    if grad_logits.dtype != torch.float32 or tuple(grad_logits.shape) != shape:
+        raise RuntimeError("grad_logits must be float32 of shape %s, got %s %s" % (shape, grad_logits.dtype, tuple(grad_logits.shape)))
+    if grad_logits.device != H_dst.device:
+        raise RuntimeError("grad_logits must be on the device of H_dst")
+    _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
+    _transposed_i32(column_index_t, "column_index_t", E, row_pointers.device)
+    _transposed_i32(entry_index_t, "entry_index_t", E, row_pointers.device)
+    L = lib()
+    grad_dst = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
+    grad_src = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
+    grad_att = torch.empty_like(att)
+    ws_bytes = int(L.hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=H_dst.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
+    with _on_device(H_dst.device):
+        check(L.hcspmm_gatv2_scores_backward_directed(_ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src),
+                                                      H_src.stride(0), _ptr(att), float(negative_slope), _ptr(row_pointers),
+                                                      _ptr(column_index), _ptr(row_pointers_t), _ptr(column_index_t),
+                                                      _ptr(entry_index_t), N, N, E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D,
+                                                      _ptr(grad_att), _ptr(ws), ws_bytes, stream))
     return grad_dst, grad_src, grad_att
 
 

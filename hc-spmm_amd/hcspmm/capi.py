@@ -70,6 +70,8 @@ SYMBOLS = {
                                        _vp, _sz, _vp, _vp]),
     "hcspmm_forward_weighted_heads": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
                                              _int, _vp, _sz, _vp, _vp, _int]),
+    "hcspmm_forward_weighted_indexed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
+                                               _int, _vp, _sz, _vp, _vp, _int, _vp, _i64]),
     "hcspmm_extremum_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_extremum": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
                                        _vp, _sz, _vp, _int, _vp, _i64]),
@@ -77,6 +79,7 @@ SYMBOLS = {
                                                 _int, _vp, _vp, _sz, _vp]),
     "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
+    "hcspmm_transpose_graph": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "hcspmm_sddmm": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp]),
     "hcspmm_sddmm_heads": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _int]),
     "hcspmm_edge_softmax": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
@@ -84,10 +87,14 @@ SYMBOLS = {
     "hcspmm_gat_attention": (_int, [_vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_gat_attention_backward": (_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp,
                                              _vp]),
+    "hcspmm_gat_attention_backward_directed": (_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int,
+                                                      _vp, _vp, _vp, _vp]),
     "hcspmm_gatv2_scores": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
     "hcspmm_gatv2_backward_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "hcspmm_gatv2_scores_backward": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _int,
                                             _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "hcspmm_gatv2_scores_backward_directed": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                     _i64, _i64, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "hcspmm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_forward_strided": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz,
                                       _vp]),

@@ -261,6 +261,38 @@ std::vector<torch::Tensor> spmm_forward_weighted_heads(torch::Tensor input, torc
   return {output};
 }
 
+// Multi-head edge-weighted aggregation with indexed values (hcspmm_forward_weighted_indexed): values [heads, V] (or [V]: one
+// head), value_index int32 [E] with every index in [0, V) -- checked here, the device trusts it
+std::vector<torch::Tensor> spmm_forward_weighted_indexed(torch::Tensor input, torch::Tensor values, torch::Tensor value_index,
+                                                         torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                         torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                                         torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                                                         torch::Tensor col_nzr) {
+  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  CHECK_INPUT(values);
+  CHECK_INPUT(value_index);
+  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
+  TORCH_CHECK((values.dim() == 1 || values.dim() == 2) && (values.dim() == 1 || values.size(0) >= 1),
+              "values must be [heads, V] or [V], got ", values.sizes());
+  TORCH_CHECK(value_index.scalar_type() == torch::kInt && value_index.dim() == 1 && value_index.numel() == c.E,
+              "value_index must be an int32 [E] tensor with E = ", c.E, ", got ", value_index.scalar_type(), " ", value_index.sizes());
+  TORCH_CHECK(values.device() == input.device() && value_index.device() == input.device(),
+              "values and value_index must be on the device of the input");
+  const int64_t heads = values.dim() == 1 ? 1 : values.size(0), V = values.size(values.dim() - 1);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat, "the indexed kernels take float32 features only, got ", input.scalar_type());
+  if (heads > 1) check_heads_width(c.D, heads, input);
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
+  auto vals = V > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_forward_weighted_indexed(
+      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
+      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
+      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>(), (int)heads, iptr(value_index), V);
+  check_rc(rc, "forward_weighted_indexed");
+  return {output};
+}
+
 // Max / min aggregation (hcspmm_forward_extremum): float32 X, a strided view with unit inner stride whose rows the column ids
 // index -> {Z, arg} ({Z} without arg)
 std::vector<torch::Tensor> spmm_forward_extremum(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -462,9 +494,17 @@ torch::Tensor gat_attention(torch::Tensor s_dst, torch::Tensor s_src, torch::Ten
   return alpha;
 }
 
-std::vector<torch::Tensor> gat_attention_backward(torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor s_dst, torch::Tensor s_src,
-                                                  torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor perm,
-                                                  double negative_slope) {
+// an int32 device tensor of n elements of the directed backwards' transposed graph
+void check_transposed(const torch::Tensor& t, const char* name, int64_t n, const torch::Tensor& nodePointer) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt && t.dim() == 1 && t.numel() == n, name,
+              " must be a contiguous int32 CUDA tensor of ", n, " elements, got ", t.scalar_type(), " ", t.sizes());
+  TORCH_CHECK(t.device() == nodePointer.device(), name, " must be on the device of row_pointers");
+}
+
+// rp_t undefined: the pattern-symmetric form (perm = transpose_permutation); defined: the directed form (perm = entry_index_t)
+std::vector<torch::Tensor> gat_attention_backward_any(torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor s_dst,
+                                                      torch::Tensor s_src, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                      torch::Tensor rp_t, torch::Tensor perm, double negative_slope) {
   const int64_t heads = gat_graph(nodePointer, edgeList, s_dst, s_src);
   const int64_t N = nodePointer.numel() - 1, E = edgeList.numel();
   TORCH_CHECK(s_src.size(0) == N, "s_src has ", s_src.size(0), " rows but the backward needs one per node (", N, ")");
@@ -485,12 +525,28 @@ std::vector<torch::Tensor> gat_attention_backward(torch::Tensor alpha, torch::Te
   auto grad_s_dst = torch::empty_like(s_dst), grad_s_src = torch::empty_like(s_src);
   auto grad_scores = torch::empty(shape, alpha.options());
   const c10::DeviceGuard guard(alpha.device());
+  if (rp_t.defined()) {
+    check_transposed(rp_t, "row_pointers_t", N + 1, nodePointer);
+    check_rc(hcspmm_gat_attention_backward_directed(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
+                                                    iptr(nodePointer), E ? iptr(edgeList) : nullptr, iptr(rp_t),
+                                                    E ? iptr(perm32) : nullptr, N, N, E, (int)heads, mfptr(grad_scores),
+                                                    mfptr(grad_s_dst), mfptr(grad_s_src),
+                                                    (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
+             "gat_attention_backward_directed");
+    return {grad_s_dst, grad_s_src, grad_scores};
+  }
   check_rc(hcspmm_gat_attention_backward(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
                                          iptr(nodePointer), E ? iptr(edgeList) : nullptr, E ? iptr(perm32) : nullptr, N, E, (int)heads,
                                          mfptr(grad_scores), mfptr(grad_s_dst), mfptr(grad_s_src),
                                          (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
            "gat_attention_backward");
   return {grad_s_dst, grad_s_src, grad_scores};
+}
+
+std::vector<torch::Tensor> gat_attention_backward(torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor s_dst, torch::Tensor s_src,
+                                                  torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor perm,
+                                                  double negative_slope) {
+  return gat_attention_backward_any(alpha, grad_alpha, s_dst, s_src, nodePointer, edgeList, torch::Tensor(), perm, negative_slope);
 }
 
 // GATv2 operands: H_dst [N, D] and H_src [src_rows, D] float32 views with unit inner stride, att [heads, Dh] (or [Dh])
@@ -533,9 +589,12 @@ torch::Tensor gatv2_scores(torch::Tensor H_dst, torch::Tensor H_src, torch::Tens
 }
 
 // Backward of gatv2_scores (hcspmm_gatv2_scores_backward; the workspace is allocated here) -> [grad_H_dst, grad_H_src, grad_att]
-std::vector<torch::Tensor> gatv2_scores_backward(torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src,
-                                                 torch::Tensor att, torch::Tensor nodePointer, torch::Tensor edgeList,
-                                                 torch::Tensor perm, double negative_slope) {
+// rp_t / col_t undefined: the pattern-symmetric form (perm = transpose_permutation); defined: the directed form (A^T's row
+// pointers and column ids, perm = entry_index_t)
+std::vector<torch::Tensor> gatv2_scores_backward_any(torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src,
+                                                     torch::Tensor att, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                     torch::Tensor rp_t, torch::Tensor col_t, torch::Tensor perm,
+                                                     double negative_slope) {
   const int64_t heads = gatv2_operands(H_dst, H_src, att, nodePointer, edgeList);
   const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), D = H_dst.size(1);
   TORCH_CHECK(H_src.size(0) == N, "H_src has ", H_src.size(0), " rows but the backward needs one per node (", N, ")");
@@ -555,12 +614,30 @@ std::vector<torch::Tensor> gatv2_scores_backward(torch::Tensor grad_logits, torc
   const size_t ws_bytes = hcspmm_gatv2_backward_workspace_bytes(N, E, (int)D, (int)heads);
   auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, att.options());
   const c10::DeviceGuard guard(H_dst.device());
+  if (rp_t.defined()) {
+    check_transposed(rp_t, "row_pointers_t", N + 1, nodePointer);
+    check_transposed(col_t, "column_index_t", E, nodePointer);
+    check_rc(hcspmm_gatv2_scores_backward_directed(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0),
+                                                   fptr(att), (float)negative_slope, iptr(nodePointer), iptr(edgeList), iptr(rp_t),
+                                                   iptr(col_t), iptr(perm32), N, N, E, (int)D, (int)heads, mfptr(grad_dst), D,
+                                                   mfptr(grad_src), D, mfptr(grad_att), mfptr(ws), ws_bytes,
+                                                   (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
+             "gatv2_scores_backward_directed");
+    return {grad_dst, grad_src, grad_att};
+  }
   check_rc(hcspmm_gatv2_scores_backward(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0), fptr(att),
                                         (float)negative_slope, iptr(nodePointer), iptr(edgeList), iptr(perm32), N, E, (int)D,
                                         (int)heads, mfptr(grad_dst), D, mfptr(grad_src), D, mfptr(grad_att), mfptr(ws), ws_bytes,
                                         (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
            "gatv2_scores_backward");
   return {grad_dst, grad_src, grad_att};
+}
+
+std::vector<torch::Tensor> gatv2_scores_backward(torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src,
+                                                 torch::Tensor att, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                 torch::Tensor perm, double negative_slope) {
+  return gatv2_scores_backward_any(grad_logits, H_dst, H_src, att, nodePointer, edgeList, torch::Tensor(), torch::Tensor(), perm,
+                                   negative_slope);
 }
 
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
@@ -841,6 +918,49 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              "transpose_permutation");
     return perm.to(row_pointers.device(), torch::kLong);
   }, "perm with values[perm] = the values of A_w^T in A's CSR order (pattern-symmetric graphs)");
+  m.def("transpose_graph", [](torch::Tensor row_pointers, torch::Tensor column_index, c10::optional<int64_t> num_cols) {
+    auto rp = row_pointers.to(torch::kCPU, torch::kInt).contiguous();
+    auto col = column_index.to(torch::kCPU, torch::kInt).contiguous();
+    TORCH_CHECK(rp.dim() == 1 && rp.numel() >= 1 && col.dim() == 1, "row_pointers [N + 1] and column_index [E] must be 1-D");
+    const int64_t N = rp.numel() - 1, E = col.numel(), M = num_cols.has_value() ? *num_cols : N;
+    TORCH_CHECK(M >= 0, "num_cols must not be negative, got ", M);
+    auto rp_t = torch::empty({M + 1}, rp.options()), col_t = torch::empty({E}, rp.options()), eid_t = torch::empty({E}, rp.options());
+    check_rc(hcspmm_transpose_graph(rp.data_ptr<int>(), E ? col.data_ptr<int>() : nullptr, N, M, E, rp_t.data_ptr<int>(),
+                                    E ? col_t.data_ptr<int>() : nullptr, E ? eid_t.data_ptr<int>() : nullptr),
+             "transpose_graph");
+    const auto dev = row_pointers.device();
+    return std::vector<torch::Tensor>{rp_t.to(dev), col_t.to(dev), eid_t.to(dev)};
+  }, "A^T of any CSR graph (host counting sort) -> [row_pointers_t, column_index_t, entry_index_t], int32 on the inputs' device; "
+     "entry_index_t[e_t] = the CSR position in A of A^T's entry e_t",
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("num_cols") = pybind11::none());
+  m.def("forward_weighted_indexed", &spmm_forward_weighted_indexed,
+        "multi-head edge-weighted aggregation with indexed values [Z]: entry e of head h weighs values[h][value_index[e]]; the "
+        "bits of forward_weighted_heads(X, values[:, value_index]) without the gathered copy (gfx950)");
+  m.def("gat_attention_backward_directed",
+        [](torch::Tensor alpha, torch::Tensor grad_alpha, torch::Tensor s_dst, torch::Tensor s_src, torch::Tensor row_pointers,
+           torch::Tensor column_index, torch::Tensor row_pointers_t, torch::Tensor entry_index_t, double negative_slope) {
+          TORCH_CHECK(row_pointers_t.defined(), "row_pointers_t is required");
+          return gat_attention_backward_any(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t,
+                                            entry_index_t, negative_slope);
+        },
+        "backward of gat_attention on any square graph; (row_pointers_t, entry_index_t) from transpose_graph -> [grad_s_dst, "
+        "grad_s_src, grad_scores] (gfx950)",
+        pybind11::arg("alpha"), pybind11::arg("grad_alpha"), pybind11::arg("s_dst"), pybind11::arg("s_src"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("row_pointers_t"),
+        pybind11::arg("entry_index_t"), pybind11::arg("negative_slope") = 0.2);
+  m.def("gatv2_scores_backward_directed",
+        [](torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src, torch::Tensor att, torch::Tensor row_pointers,
+           torch::Tensor column_index, torch::Tensor row_pointers_t, torch::Tensor column_index_t, torch::Tensor entry_index_t,
+           double negative_slope) {
+          TORCH_CHECK(row_pointers_t.defined() && column_index_t.defined(), "row_pointers_t and column_index_t are required");
+          return gatv2_scores_backward_any(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t,
+                                           column_index_t, entry_index_t, negative_slope);
+        },
+        "backward of gatv2_scores on any square graph; (row_pointers_t, column_index_t, entry_index_t) from transpose_graph -> "
+        "[grad_H_dst, grad_H_src, grad_att] (gfx950)",
+        pybind11::arg("grad_logits"), pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("row_pointers_t"),
+        pybind11::arg("column_index_t"), pybind11::arg("entry_index_t"), pybind11::arg("negative_slope") = 0.2);
   m.def("forward_weighted_heads", &spmm_forward_weighted_heads,
         "multi-head edge-weighted aggregation [Z]: values [heads, E], head h weights columns h*Dh ... (h+1)*Dh - 1 (gfx950)");
   m.def("sddmm_heads", &spmm_sddmm_heads,
@@ -864,7 +984,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
         pybind11::arg("col_nzr"), pybind11::arg("return_arg") = true);
   m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
-        "backward of forward_max / forward_min (square, pattern-symmetric graph; perm = int32 transpose_permutation) -> grad_X (gfx950)");
+        "backward of forward_max / forward_min -> grad_X: a square, pattern-symmetric graph with perm = int32 transpose_permutation, "
+        "or any square graph's A^T (transpose_graph's tensors and their preprocessing) with perm = entry_index_t (gfx950)");
   m.def("sddmm", &spmm_sddmm, "sampled dense-dense product on the stored entries: float32 [E], out[e] = <A[row(e)], B[col(e)]> (gfx950)");
   m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
   m.def("edge_softmax_backward", &edge_softmax_backward,

@@ -337,6 +337,28 @@ int hcspmm_forward_weighted_heads(const void* X_d, int64_t x_rows, int64_t ldx, 
                                   int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                                   const float* values_d, int heads);
 
+/* Multi-head edge-weighted forward with indexed values: hcspmm_forward_weighted_heads whose weight for entry e is fetched
+ * through value_index_d[e].  values_d is head-major fp32 [heads][num_values]:
+ *   Z[r][h * Dh + j] = sum over e in row r  values[h * num_values + value_index[e]] * X[column_index[e]][h * Dh + j]
+ * The result is bit for bit hcspmm_forward_weighted_heads (heads = 1: hcspmm_forward_weighted) called with the gathered
+ * values[:, value_index] -- the same fma chains, combine trees, MFMA order and fix-up order on every launch path (ordinary,
+ * wide, column-sliced, segmented and tiny tasks, dense-tile windows, plan-free, rectangular x_rows) -- so an identity index
+ * reproduces those entry points exactly.  It is what a backward through A^T wants: on the transposed graph
+ * (hcspmm_transpose_graph) with value_index = entry_index_t, or on a pattern-symmetric graph with value_index =
+ * hcspmm_transpose_permutation's perm, dX = A_w^T * dZ reads A's values in place and no permuted copy is written.
+ * value_index_d is int32 [num_edges]; every index must lie in [0, num_values) and is trusted on the device, as column ids
+ * are on the plan-free paths (many-to-one indices and num_values != num_edges are fine).  fp32 only.  heads >= 1,
+ * embedding_dim % heads == 0 and Dh % 4 == 0; heads = 1 takes every embedding_dim hcspmm_forward_weighted serves.  NULL
+ * values_d, a NULL value_index_d or num_values == 0 with num_edges > 0, num_values < 0 and the argument errors of
+ * hcspmm_forward_weighted_heads are HCSPMM_EINVAL before any device call.  Separate kernels
+ * (spmm_weighted_indexed.hip) on the binary product's plan. */
+int hcspmm_forward_weighted_indexed(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype,
+                                    const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                                    const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                                    const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                                    int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
+                                    const float* values_d, int heads, const int32_t* value_index_d /* [E] */, int64_t num_values);
+
 /* ------------------------------------------------------------------------------------------
  * Max / min neighbour aggregation with its argmax (GraphSAGE-pool, GIN-max, PNA; PyG aggr = "max" / "min"):
  *   Z[r][d]   = max (HCSPMM_REDUCE_MAX) or min (HCSPMM_REDUCE_MIN) over e in [row_pointers[r], row_pointers[r+1]) of
@@ -374,7 +396,10 @@ int hcspmm_forward_extremum(const void* X_d, int64_t x_rows, int64_t ldx, void* 
  * no atomics: two calls give the same bits.  Columns no entry won get +0.0.  grad_Z_d, arg_d and grad_X_out_d are
  * [num_nodes] rows of ldg / ldarg / ldgx elements (each >= embedding_dim); arg_d is the forward's arg_out_d.
  * workspace_d >= hcspmm_workspace_bytes() (hcspmm_extremum_workspace_bytes also serves).  Argument errors as
- * hcspmm_forward_extremum, a NULL arg_d or transpose_perm_d (E > 0) included.  Asynchronous on `stream`. */
+ * hcspmm_forward_extremum, a NULL arg_d or transpose_perm_d (E > 0) included.  Asynchronous on `stream`.
+ * Directed graphs: the launch walks whatever graph it is handed and assumes no symmetry of it.  Called with A^T's graph
+ * tensors and plan (hcspmm_transpose_graph, then the preprocessing and plan of A^T) and entry_index_t as transpose_perm_d, row
+ * j's entry e_t has i = column_index_t[e_t] and e = entry_index_t[e_t], which is the formula above for any square A. */
 int hcspmm_forward_extremum_backward(const float* grad_Z_d, int64_t ldg, const int32_t* arg_d, int64_t ldarg,
                                      float* grad_X_out_d, int64_t ldgx, const int32_t* row_pointers_d,
                                      const int32_t* column_index_d, const int32_t* blockPartition_d,
@@ -398,6 +423,18 @@ int hcspmm_edge_norm_device(const int32_t* row_pointers_d, const int32_t* column
  * symmetric (or a row's columns are not strictly ascending). */
 int hcspmm_transpose_permutation(const int32_t* row_pointers_h, const int32_t* column_index_h, int64_t num_nodes,
                                  int64_t num_edges, int32_t* perm_out_h);
+
+/* Transpose of any CSR graph (host; a counting sort): A is num_rows x num_cols with num_edges entries, A^T is num_cols x
+ * num_rows.  Entry e_t of row j of A^T is the entry (i, j) of A: column_index_t[e_t] = i and entry_index_t[e_t] = the CSR
+ * position e of (i, j) in A, so values[entry_index_t] are A_w^T's values.  Within a row of A^T the entries ascend in i: A^T
+ * has strictly ascending columns whenever A does.  On a pattern-symmetric square graph the three outputs are row_pointers,
+ * column_index and hcspmm_transpose_permutation's perm, element for element.  HCSPMM_EINVAL for NULL outputs, negative
+ * sizes, a column id outside [0, num_cols) or a row whose columns are not strictly ascending (nothing is written then);
+ * num_edges = 0 fills row_pointers_t with zeros. */
+int hcspmm_transpose_graph(const int32_t* row_pointers_h, const int32_t* column_index_h, int64_t num_rows, int64_t num_cols,
+                           int64_t num_edges, int32_t* row_pointers_t_out_h /* [num_cols + 1] */,
+                           int32_t* column_index_t_out_h /* [E]: the row i of A */,
+                           int32_t* entry_index_t_out_h /* [E]: the CSR position e of (i, j) in A */);
 
 /* ------------------------------------------------------------------------------------------
  * SDDMM (sampled dense-dense product) on the stored entries -- with the two edge softmax entry points below, the kernels
@@ -471,6 +508,20 @@ int hcspmm_gat_attention_backward(const float* alpha_d, const float* grad_alpha_
                                   float* grad_s_dst_out_d /* [N][heads] */, float* grad_s_src_out_d /* [N][heads] */,
                                   void* stream);
 
+/* hcspmm_gat_attention_backward without the symmetry requirement: the column side walks A^T (hcspmm_transpose_graph),
+ *   grad_s_src[c][h] = sum_{e_t in row c of A^T} g[h][entry_index_t[e_t]]
+ * with s_src and grad_s_src of src_rows rows (A is num_nodes x src_rows, row_pointers_t_d has src_rows + 1 elements).  The
+ * row-side launch is hcspmm_gat_attention_backward's; so is the column-side kernel, which only ever walked a row-pointer
+ * array and an index array: passing (row_pointers, perm, num_nodes) of a pattern-symmetric graph gives that function's bits.
+ * Same determinism contract and argument errors, NULL transposed arrays included. */
+int hcspmm_gat_attention_backward_directed(const float* alpha_d, const float* grad_alpha_d, const float* s_dst_d,
+                                           const float* s_src_d, float negative_slope, const int32_t* row_pointers_d,
+                                           const int32_t* column_index_d, const int32_t* row_pointers_t_d,
+                                           const int32_t* entry_index_t_d, int64_t src_rows, int64_t num_nodes,
+                                           int64_t num_edges, int heads, float* grad_scores_out_d /* g, [heads][E] */,
+                                           float* grad_s_dst_out_d /* [N][heads] */,
+                                           float* grad_s_src_out_d /* [src_rows][heads] */, void* stream);
+
 /* GATv2 attention logits (Brody et al.: the non-linearity inside the dot product), all heads in one launch, from fp32 node
  * features H_dst [num_nodes][ld_dst] and H_src [src_rows][ld_src] of embedding_dim = heads * Dh columns (Dh % 4 == 0; leading
  * dimensions >= embedding_dim in elements, so the two halves of one [N, 2 D] projection can be passed as views) and att
@@ -515,6 +566,21 @@ int hcspmm_gatv2_scores_backward(const float* grad_logits_d, const float* H_dst_
                                  int64_t num_edges, int embedding_dim, int heads, float* grad_H_dst_out_d, int64_t ld_gdst,
                                  float* grad_H_src_out_d, int64_t ld_gsrc, float* grad_att_out_d /* [heads][Dh] */,
                                  void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* hcspmm_gatv2_scores_backward without the symmetry requirement: grad_H_src walks A^T (hcspmm_transpose_graph),
+ *   grad_H_src[c][j] = att[j] * sum_{e_t in row c of A^T} g[h(j)][entry_index_t[e_t]] * d(H_dst[column_index_t[e_t]][j] + H_src[c][j])
+ * with H_src and grad_H_src of src_rows rows.  grad_H_dst and grad_att are hcspmm_gatv2_scores_backward's launches; the
+ * grad_H_src launch is the same kernel on the transposed arrays (its row classes follow A^T's row lengths), so passing
+ * (row_pointers, column_index, perm, num_nodes) of a pattern-symmetric graph gives that function's bits.  Same determinism
+ * contract, workspace and argument errors, NULL transposed arrays included. */
+int hcspmm_gatv2_scores_backward_directed(const float* grad_logits_d, const float* H_dst_d, int64_t ld_dst, const float* H_src_d,
+                                          int64_t ld_src, const float* att_d, float negative_slope,
+                                          const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                          const int32_t* row_pointers_t_d, const int32_t* column_index_t_d,
+                                          const int32_t* entry_index_t_d, int64_t src_rows, int64_t num_nodes, int64_t num_edges,
+                                          int embedding_dim, int heads, float* grad_H_dst_out_d, int64_t ld_gdst,
+                                          float* grad_H_src_out_d, int64_t ld_gsrc, float* grad_att_out_d /* [heads][Dh] */,
+                                          void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
