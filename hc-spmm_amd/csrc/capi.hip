@@ -210,6 +210,32 @@ struct FusedOperands {
   int mode;  // bit 0: dense-tile windows update inside the hybrid launch; bit 1: ordinary / tiny sparse rows in the row-tile launch
 };
 
+// the plan fields of a hybrid launch, from the host copy of the plan's header (the launcher-owned fields stay zero:
+// plan_layout.h fills them); dtype: the element type wide_choice decides for
+void fill_plan_args(hcspmm::PlanArgs& a, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int D, int dtype) {
+  a = hcspmm::PlanArgs{};
+  a.plan = plan_d;
+  a.off_tasks = ph->off_tasks;
+  a.n_tasks = ph->n_tasks;
+  a.n_tiny = ph->n_tiny;
+  a.off_slice_table = ph->off_slice_table;
+  a.off_slice_tasks = ph->off_slice_tasks;
+  a.n_slices = ph->n_slices;
+  a.slice_xcd_tasks = ph->slice_xcd_tasks;
+  a.off_dense_index = ph->off_dense_index;
+  a.off_dense_pack = ph->off_dense_pack;
+  a.n_dense = ph->n_dense;
+  a.off_dense_compact = ph->off_dense_compact;
+  a.n_dense_compact = ph->n_dense_compact;
+  a.off_dense_compact2 = ph->off_dense_compact2;
+  a.n_dense_compact2 = ph->n_dense_compact2;
+  a.off_fixups = ph->off_fixups;
+  a.n_split_rows = ph->n_split_rows;
+  wide_choice(ph, D, dtype, &a.n_wide, &a.panel_cols);
+  a.N = (int)N;
+  a.D = D;
+}
+
 int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype, const int32_t* rowptr,
                  const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
@@ -235,48 +261,21 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     const size_t need = hcspmm_workspace_bytes(ph, D);
     if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
     hcspmm::PlanArgs a;
+    fill_plan_args(a, plan_d, ph, N, D, dtype);
     a.X = X;
     a.Z = Z;
     a.ldx = (size_t)ldx;
     a.ldz = (size_t)ldz;
     a.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
     a.col = col;
-    a.plan = plan_d;
-    a.off_tasks = ph->off_tasks;
-    a.n_tasks = ph->n_tasks;
-    a.n_tiny = ph->n_tiny;
-    a.tiny_wgs = 0;
-    a.tiny_kernel_wgs = 0;
-    a.off_slice_table = ph->off_slice_table;
-    a.off_slice_tasks = ph->off_slice_tasks;
-    a.n_slices = ph->n_slices;
-    a.slice_xcd_tasks = ph->slice_xcd_tasks;
-    a.slice_wgs = 0;
-    a.free_wgs_pp = 0;
-    a.off_dense_index = ph->off_dense_index;
-    a.off_dense_pack = ph->off_dense_pack;
-    a.n_dense = ph->n_dense;
-    a.off_dense_compact = ph->off_dense_compact;
-    a.n_dense_compact = ph->n_dense_compact;
-    a.off_dense_compact2 = ph->off_dense_compact2;
-    a.n_dense_compact2 = ph->n_dense_compact2;
-    a.off_fixups = ph->off_fixups;
-    a.n_split_rows = ph->n_split_rows;
-    wide_choice(ph, D, dtype, &a.n_wide, &a.panel_cols);
-    a.sparse_wgs_pp = 0;
-    a.dense_vec = 0;
-    a.wide_wgs = 0;
-    a.N = (int)N;
-    a.D = D;
-    a.sparse_wgs = 0;
-    a.n_panels = 0;
-    a.fused = fused ? fused->mode : 0;
-    a.fused_dense_wgs = 0;
-    a.H = fused ? fused->H : 0;
-    a.W = fused ? fused->W : nullptr;
-    a.w_ldr = fused ? fused->ldr : 0;
-    a.w_ldc = fused ? fused->ldc : 0;
-    a.out = fused ? fused->out : nullptr;
+    if (fused) {
+      a.fused = fused->mode;
+      a.H = fused->H;
+      a.W = fused->W;
+      a.w_ldr = fused->ldr;
+      a.w_ldc = fused->ldc;
+      a.out = fused->out;
+    }
     const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, need ? workspace : nullptr);
     if (fused && (vec != 4 || dtype != HCSPMM_DTYPE_F32)) return HCSPMM_EINVAL;  // (fused_form said otherwise)
     if (fused && (fused->mode & 2)) {
@@ -289,8 +288,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     if (values) {
       if (fused) return HCSPMM_EINVAL;
       const hcspmm::WPlanArgs wa{a, values, rowptr, ph->segment_len};
-      if (vindex) e = hcspmm::launch_plan_wi_f32(hcspmm::WIPlanArgs{{wa, (long long)num_values, D / heads}, vindex}, vec, stream);
-      else if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads}, vec, stream);
+      if (vindex) e = hcspmm::launch_plan_wi_f32(hcspmm::WHPlanArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
+      else if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads, nullptr}, vec, stream);
       else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_w_f16(wa, vec, stream)
                                       : hcspmm::launch_plan_w_bf16(wa, vec, stream);
@@ -319,8 +318,8 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
     const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, nullptr);
     if (values) {
       const hcspmm::WWindowArgs wa{a, values};
-      if (vindex) e = hcspmm::launch_window_wi_f32(hcspmm::WIWindowArgs{{wa, (long long)num_values, D / heads}, vindex}, vec, stream);
-      else if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads}, vec, stream);
+      if (vindex) e = hcspmm::launch_window_wi_f32(hcspmm::WHWindowArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
+      else if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads, nullptr}, vec, stream);
       else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
           : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_w_f16(wa, vec, stream)
                                       : hcspmm::launch_window_w_bf16(wa, vec, stream);
@@ -385,31 +384,6 @@ extern "C" int hcspmm_forward_weighted_indexed(const void* X, int64_t x_rows, in
 }
 
 namespace {
-// the plan fields of a hybrid launch (forward_impl's), for the extremum launches
-void fill_plan_args(hcspmm::PlanArgs& a, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int D) {
-  a = hcspmm::PlanArgs{};
-  a.plan = plan_d;
-  a.off_tasks = ph->off_tasks;
-  a.n_tasks = ph->n_tasks;
-  a.n_tiny = ph->n_tiny;
-  a.off_slice_table = ph->off_slice_table;
-  a.off_slice_tasks = ph->off_slice_tasks;
-  a.n_slices = ph->n_slices;
-  a.slice_xcd_tasks = ph->slice_xcd_tasks;
-  a.off_dense_index = ph->off_dense_index;
-  a.off_dense_pack = ph->off_dense_pack;
-  a.n_dense = ph->n_dense;
-  a.off_dense_compact = ph->off_dense_compact;
-  a.n_dense_compact = ph->n_dense_compact;
-  a.off_dense_compact2 = ph->off_dense_compact2;
-  a.n_dense_compact2 = ph->n_dense_compact2;
-  a.off_fixups = ph->off_fixups;
-  a.n_split_rows = ph->n_split_rows;
-  wide_choice(ph, D, HCSPMM_DTYPE_F32, &a.n_wide, &a.panel_cols);
-  a.N = (int)N;
-  a.D = D;
-}
-
 // backward = false: hcspmm_forward_extremum (src = X, dst = Z); true: its backward (src = grad_Z, dst = grad_X, square)
 int extremum_impl(bool backward, const float* src, int64_t src_rows, int64_t lds, float* dst, int64_t ldd, int dtype,
                   const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
@@ -431,7 +405,7 @@ int extremum_impl(bool backward, const float* src, int64_t src_rows, int64_t lds
     const size_t part = hcspmm_workspace_bytes(ph, D);      // fp32 values (forward: positions behind them)
     const size_t need = backward ? part : 2 * part;
     if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
-    fill_plan_args(x.p, plan_d, ph, N, D);
+    fill_plan_args(x.p, plan_d, ph, N, D, HCSPMM_DTYPE_F32);
     x.p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
     x.ppos = (need && !backward) ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + part) : nullptr;
     x.segment_len = ph->segment_len;
@@ -758,7 +732,7 @@ static int fused_form(const hcspmm_plan_header* ph, const void* X, const void* o
   if (!(ph->flags & HCSPMM_PLAN_FUSE_IN_LAUNCH) && forced != 1) return 0;  // form 1 only where it was asked for by name
   bool dense_ok = ph->n_dense > 0 && D % 16 == 0 && D >= 32 && H % 16 == 0 && H <= 32 && H > 0;
   if (dense_ok) {
-    const int dv = D <= 32 ? 2 : 4;  // (launch_plan_LV: the narrowest lane width that covers the row in one panel)
+    const int dv = D <= 32 ? 2 : 4;  // (plan_layout.h: the narrowest lane width that covers the row in one panel)
     const int rows = (D + 16 * dv - 1) / (16 * dv) * 16 * dv;
     dense_ok = (size_t)rows * (size_t)(H + 4) * sizeof(float) <= 64 * 1024;
   }

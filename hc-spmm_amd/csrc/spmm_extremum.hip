@@ -506,7 +506,6 @@ __global__ __launch_bounds__(kThreads) void extremum_window_kernel(XArgs xa) {
 
 template <int L, int VEC, bool BWD>
 hipError_t launch_extremum_LV(const XArgs& xa, hipStream_t stream) {
-  constexpr int R = 64 / L;
   XArgs xb = xa;
   PlanArgs& b = xb.p;
   if (xa.p.plan == nullptr) {  // plan-free
@@ -517,17 +516,8 @@ hipError_t launch_extremum_LV(const XArgs& xa, hipStream_t stream) {
     return hipGetLastError();
   }
   b.fused = 0;
-  b.n_wide = (R > 1) ? b.n_wide : 0;
-  b.wide_wgs = (b.n_wide + kWaves - 1) / kWaves;
-  b.tiny_kernel_wgs = 0;
-  b.tiny_wgs = (b.n_tiny + kWaves * R * XTinyT<L>::value - 1) / (kWaves * R * XTinyT<L>::value);
-  b.free_wgs_pp = b.wide_wgs + (b.n_tasks - b.n_tiny - b.n_wide + kWaves * R - 1) / (kWaves * R) + b.tiny_wgs;
-  b.slice_wgs = b.n_slices > 0 ? 8 * ((b.slice_xcd_tasks + kWaves * R - 1) / (kWaves * R)) : 0;
-  b.sparse_wgs_pp = b.slice_wgs + b.free_wgs_pp;
-  if (b.slice_wgs > 0) b.sparse_wgs_pp = (b.sparse_wgs_pp + 7) & ~7;
-  const int n_col_panels = (b.D + b.panel_cols - 1) / b.panel_cols;
-  b.sparse_wgs = b.sparse_wgs_pp * n_col_panels;
-  if (b.sparse_wgs_pp == 0) b.sparse_wgs_pp = 1;
+  // the shared layout (plan_layout.h): no launch of their own for the tiny tasks, dense windows once per column panel
+  const int n_col_panels = plan_launch_layout(b, L, 0, 0, XTinyT<L>::value, false, 0);
   const long long dense_wgs = ((long long)b.n_dense * n_col_panels + kWaves - 1) / kWaves;
   const long long grid = (long long)b.sparse_wgs + dense_wgs;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;

@@ -40,6 +40,7 @@
 
 #include "hcspmm.h"
 #include "spmm_kernels.h"
+#include "plan_layout.h"
 
 namespace hcspmm {
 
@@ -174,8 +175,7 @@ template <typename E, int VEC> struct Lane {
 typedef const HCSPMM_CONST_AS int* cint_p;
 typedef const HCSPMM_CONST_AS unsigned long long* cu64_p;
 
-constexpr int kWaves = 4;            // waves per workgroup (256 threads)
-constexpr int kThreads = kWaves * 64;
+// (kWaves, kThreads: plan_layout.h)
 #ifndef HCSPMM_SPARSE_U
 #define HCSPMM_SPARSE_U 8  // row loads in flight per lane on the sparse-row path
 #endif
@@ -823,9 +823,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
 // stores, 0.8 of what the guide calls achievable for STREAMING.  Bytes are within 1.2x of compulsory: nothing left to fuse.
 // Taken when the plan has enough tiny tasks to fill the chip (launch_plan_LV); small graphs keep the in-kernel region
 // and its single launch.  Same order of additions: same bits.
-#ifndef HCSPMM_TINY_KERNEL_T
-#define HCSPMM_TINY_KERNEL_T 2
-#endif
+// (HCSPMM_TINY_KERNEL_T: plan_layout.h, which sizes this launch)
 #ifndef HCSPMM_TINY_KERNEL_WAVES
 #define HCSPMM_TINY_KERNEL_WAVES 8
 #endif
@@ -833,7 +831,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
 #define HCSPMM_TINY_KERNEL_MIN_TASKS 524288  // fewer tiny tasks than this stay in the hybrid launch: even at 465 K, -15 % at 240 K, +3-4 % at 900 K (profiles/r03/ab_tiny_sizes.log)
 #endif
 // The one predicate behind that choice: launch_plan_LV, launch_plan_w_LV, launch_plan_wh_LV and hcspmm_own_tiny_launch all ask
-// it.  fused: PlanArgs::fused (the fused operators keep their tiny tasks in their own launches); the weighted forms pass 0.
+// it (and hand the answer to plan_launch_layout).  fused: PlanArgs::fused (the fused operators keep their tiny tasks in their own launches); the weighted forms pass 0.
 inline bool own_tiny_launch(int n_tiny, int fused) {
   static const int tiny_kernel_min = [] {
     const char* e = getenv("HCSPMM_TINY_KERNEL_MIN_TASKS");
@@ -1013,40 +1011,13 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_kernel(WindowArgs a) {
 // ------------------------------------------------------------------------------------------
 template <typename E, int L, int VEC>
 static hipError_t launch_plan_LV(const PlanArgs& a, hipStream_t stream) {
-  constexpr int R = 64 / L;
   PlanArgs b = a;
-  b.n_wide = (R > 1) ? a.n_wide : 0;  // with one lane group per wave a wide task is an ordinary one
   // a.fused bit 0: dense-tile windows multiply their tile by the weights in this launch (FUSED kernel); bit 1: the ordinary and
   // tiny tasks of this call run in the row-tile fused launch (fused_rows.hip) -- this launch keeps the sliced region, the
   // wide tasks and the dense units
   const bool dense_fused = (a.fused & 1) != 0;
-  if (a.fused & 2) {
-    b.n_tasks = b.n_wide;
-    b.n_tiny = 0;
-    b.n_dense = b.n_dense_compact = b.n_dense_compact2 = 0;  // (dense windows are tiles of that launch as well)
-  }
-  b.wide_wgs = (b.n_wide + kWaves - 1) / kWaves;
-  // tiny tasks: a region of the hybrid launch, or -- when there are enough of them -- a launch of their own behind it
-  const bool own_tiny = own_tiny_launch(b.n_tiny, a.fused);
-  b.tiny_kernel_wgs = own_tiny ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
-  b.tiny_wgs = own_tiny ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
-  b.free_wgs_pp = b.wide_wgs + (b.n_tasks - b.n_tiny - b.n_wide + kWaves * R - 1) / (kWaves * R) + b.tiny_wgs;
-  // the sliced region: per XCD ceil(slice_xcd_tasks / tasks per workgroup) workgroups, interleaved b = x (mod 8); a panel is
-  // padded to a multiple of 8 workgroups so that b mod 8 == blockIdx mod 8 in every panel (the idle ones return at once)
-  b.slice_wgs = a.n_slices > 0 ? 8 * ((a.slice_xcd_tasks + kWaves * R - 1) / (kWaves * R)) : 0;
-  b.sparse_wgs_pp = b.slice_wgs + b.free_wgs_pp;
-  if (b.slice_wgs > 0) b.sparse_wgs_pp = (b.sparse_wgs_pp + 7) & ~7;
-  const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-  b.sparse_wgs = b.sparse_wgs_pp * n_col_panels;
-  if (b.sparse_wgs_pp == 0) b.sparse_wgs_pp = 1;  // divisor in the kernel
-  // dense-tile panel width: 16*dense_vec columns -- the narrowest of the three lane widths that covers the embedding in ONE panel
-  // (a second panel walks the window's column list and gathers its rows again: D = 48 as 32 + 16 columns took 382 us on the
-  // YeastH-sized graph where D = 50 in one 64-column panel takes 279, profiles/r04/ab_dense_panels.log), else the widest.  A 16-bit
-  // build wider than one element per lane is only launched on even widths (capi.hip pick_vec), so its narrower lanes, the last one
-  // moved back, stay on the dword grid.
-  constexpr int VM = DenseV<VEC>::mid;
-  b.dense_vec = a.D <= 16 ? 1 : (a.D <= 16 * VM ? VM : VEC);
-  b.n_panels = (a.D + 16 * b.dense_vec - 1) / (16 * b.dense_vec);
+  const int n_col_panels =
+      plan_launch_layout(b, L, VEC, DenseV<VEC>::mid, TinyT<L>::value, own_tiny_launch(a.n_tiny, a.fused), a.fused);
   constexpr bool kCanFuse = sizeof(typename E::T) == 4 && VEC == 4;
   constexpr int kMinWaves = sizeof(typename E::T) == 4 ? HCSPMM_MIN_WAVES_PER_SIMD : HCSPMM_MIN_WAVES_H16;
   if (dense_fused && !kCanFuse) return hipErrorInvalidValue;  // the caller checked (capi.hip fused_single_launch_ok)

@@ -97,33 +97,27 @@ hipError_t launch_plan_w_f16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_f16(const WWindowArgs& a, int vec, hipStream_t stream);
 hipError_t launch_plan_w_bf16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_bf16(const WWindowArgs& a, int vec, hipStream_t stream);
-// the multi-head weighted forms (spmm_weighted_heads.hip, hcspmm_forward_weighted_heads): values [heads][E], column c takes
-// head c / dh's; fp32 with vec 4 only, dh % 4 == 0, D % dh == 0
+// the multi-head weighted forms (spmm_weighted_heads_impl.h): values [heads][E], column c takes head c / dh's.  Entry e of
+// head h weighs values[h * E + e] (direct: vindex == nullptr; spmm_weighted_heads.hip, hcspmm_forward_weighted_heads) or
+// values[h * E + vindex[e]] (indexed; spmm_weighted_indexed.hip, hcspmm_forward_weighted_indexed).  fp32 only
 struct WHPlanArgs {
   WPlanArgs w;
-  long long E;  // entries per head slice of w.values
-  int dh;       // columns per head
+  long long E;        // values per head slice of w.values
+  int dh;             // columns per head
+  const int* vindex;  // [entries], or nullptr for the direct form
 };
 struct WHWindowArgs {
   WWindowArgs w;
   long long E;
   int dh;
-};
-hipError_t launch_plan_wh_f32(const WHPlanArgs& a, int vec, hipStream_t stream);
-hipError_t launch_window_wh_f32(const WHWindowArgs& a, int vec, hipStream_t stream);
-// the multi-head weighted forms with indexed values (spmm_weighted_indexed.hip, hcspmm_forward_weighted_indexed): entry e of
-// head h weighs values[h * h.E + vindex[e]], h.E = values per head.  fp32; vec 4 with the heads rules, or one head (dh = D)
-// with any vec launch_plan_w_f32 takes
-struct WIPlanArgs {
-  WHPlanArgs h;
-  const int* vindex;  // [entries]
-};
-struct WIWindowArgs {
-  WHWindowArgs h;
   const int* vindex;
 };
-hipError_t launch_plan_wi_f32(const WIPlanArgs& a, int vec, hipStream_t stream);
-hipError_t launch_window_wi_f32(const WIWindowArgs& a, int vec, hipStream_t stream);
+// direct form (a.vindex == nullptr): vec 4 only, dh % 4 == 0, D % dh == 0
+hipError_t launch_plan_wh_f32(const WHPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_wh_f32(const WHWindowArgs& a, int vec, hipStream_t stream);
+// indexed form (a.vindex set): vec 4 with the direct form's rules, or one head (dh = D) with any vec launch_plan_w_f32 takes
+hipError_t launch_plan_wi_f32(const WHPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_wi_f32(const WHWindowArgs& a, int vec, hipStream_t stream);
 // values[e] = 1/sqrt(deg(row e) * deg(col e)) (kind 0) or 1/deg(row e) (kind 1), deg = row length
 hipError_t launch_edge_norm(const int* rowptr, const int* col, int N, long long E, int kind, float* values, hipStream_t stream);
 

@@ -591,30 +591,15 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_w_kernel(WWindowArgs w
 }
 
 // ------------------------------------------------------------------------------------------
-// Host-side launchers: the grid of launch_plan_LV (same regions, same wide / tiny / slice decisions).
+// Host-side launchers: the grid of launch_plan_LV (plan_layout.h: same regions, same wide / tiny / slice decisions).
 // ------------------------------------------------------------------------------------------
 template <typename E, int L, int VEC>
 static hipError_t launch_plan_w_LV(const WPlanArgs& wa, hipStream_t stream) {
-  constexpr int R = 64 / L;
   const PlanArgs& a = wa.p;
   WPlanArgs wb = wa;
   PlanArgs& b = wb.p;
   b.fused = 0;
-  b.n_wide = (R > 1) ? a.n_wide : 0;
-  b.wide_wgs = (b.n_wide + kWaves - 1) / kWaves;
-  const bool own_tiny = own_tiny_launch(b.n_tiny, 0);
-  b.tiny_kernel_wgs = own_tiny ? (b.n_tiny + kWaves * R * HCSPMM_TINY_KERNEL_T - 1) / (kWaves * R * HCSPMM_TINY_KERNEL_T) : 0;
-  b.tiny_wgs = own_tiny ? 0 : (b.n_tiny + kWaves * R * TinyT<L>::value - 1) / (kWaves * R * TinyT<L>::value);
-  b.free_wgs_pp = b.wide_wgs + (b.n_tasks - b.n_tiny - b.n_wide + kWaves * R - 1) / (kWaves * R) + b.tiny_wgs;
-  b.slice_wgs = a.n_slices > 0 ? 8 * ((a.slice_xcd_tasks + kWaves * R - 1) / (kWaves * R)) : 0;
-  b.sparse_wgs_pp = b.slice_wgs + b.free_wgs_pp;
-  if (b.slice_wgs > 0) b.sparse_wgs_pp = (b.sparse_wgs_pp + 7) & ~7;
-  const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-  b.sparse_wgs = b.sparse_wgs_pp * n_col_panels;
-  if (b.sparse_wgs_pp == 0) b.sparse_wgs_pp = 1;
-  constexpr int VM = DenseV<VEC>::mid;
-  b.dense_vec = a.D <= 16 ? 1 : (a.D <= 16 * VM ? VM : VEC);
-  b.n_panels = (a.D + 16 * b.dense_vec - 1) / (16 * b.dense_vec);
+  const int n_col_panels = plan_launch_layout(b, L, VEC, DenseV<VEC>::mid, TinyT<L>::value, own_tiny_launch(b.n_tiny, 0), 0);
   constexpr int kMinWaves = sizeof(typename E::T) == 4 ? HCSPMM_MIN_WAVES_PER_SIMD : HCSPMM_MIN_WAVES_H16;
   const long long dense_wgs = ((long long)b.n_dense * b.n_panels + kWaves - 1) / kWaves;
   const long long grid = (long long)b.sparse_wgs + dense_wgs;

@@ -240,15 +240,17 @@ def _usage(src):
 def test_indexed_kernels_keep_the_heads_kernels_occupancy():
     """the occupancies pinned for the heads kernels (test_heads_cpu.py BUDGETS): 5 waves per SIMD planned, 8 tiny, 4 plan-free.
     No scratch, except the 20-byte reload of the planned L = 32 build (its weighted counterpart is allowed 36: DESIGN.md
-    section 3.14)."""
+    section 3.14).  The indexed builds are the heads kernels' templates with INDEXED = true (spmm_weighted_heads_impl.h), so they
+    carry the same kernel names."""
     usage = _usage("spmm_weighted_indexed.hip")
-    floors = {"hybrid_plan_wi_kernel": 5, "tiny_wi_kernel": 8, "hybrid_window_wi_kernel": 4, "fixup_kernel": 7}
+    assert all("Lb1E" in name or "fixup_kernel" in name for name in usage), sorted(usage)  # every build is the indexed form
+    floors = {"hybrid_plan_wh_kernel": 5, "tiny_wh_kernel": 8, "hybrid_window_wh_kernel": 4, "fixup_kernel": 7}
     seen = {k: 0 for k in floors}
     for name, v in usage.items():
         kernel = next((k for k in floors if k in name), None)
         assert kernel is not None, name
         seen[kernel] += 1
         assert v["occupancy"] >= floors[kernel], (name, v)
-        l32 = kernel == "hybrid_plan_wi_kernel" and "ELi32ELi4E" in name
+        l32 = kernel == "hybrid_plan_wh_kernel" and "ELi32ELi4E" in name
         assert v["scratch"] <= (20 if l32 else 0), (name, v)
-    assert seen == {"hybrid_plan_wi_kernel": 7, "tiny_wi_kernel": 7, "hybrid_window_wi_kernel": 7, "fixup_kernel": 3}, seen
+    assert seen == {"hybrid_plan_wh_kernel": 7, "tiny_wh_kernel": 7, "hybrid_window_wh_kernel": 7, "fixup_kernel": 3}, seen
