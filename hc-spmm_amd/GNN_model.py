@@ -296,6 +296,69 @@ def weighted_aggregate(X, edge_weight, graph, directed=False):
     return HCSPMMFunction_Weighted.apply(X, edge_weight, values_t, *graph)
 
 
+class HCSPMMFunction_WeightedFP8(HCSPMMFunction_Weighted):
+    """A_w X with X stored in 8 bits for the forward: quantise X per row (HCSPMM.quantize_fp8), then aggregate the codes with
+    values[e] * scale[col[e]] (HCSPMM.forward_weighted_fp8).  The backward is HCSPMMFunction_Weighted's, unchanged
+    (straight-through: the quantiser counts as the identity), so dX is the fp32 layer's for the same dY."""
+
+    @staticmethod
+    def forward(ctx, X, values, values_t, *graph):
+        if values.requires_grad:
+            raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented; "
+                                      "pass values that do not require grad")
+        ctx.save_for_backward(values_t, *graph)
+        Xq, scale = HCSPMM.quantize_fp8(X.contiguous())
+        return HCSPMM.forward_weighted_fp8(Xq, scale, values, *graph)[0]
+
+
+class EdgeWeightedAggregateDirectedFP8(EdgeWeightedAggregateDirected):
+    """HCSPMMFunction_WeightedFP8 on any square graph: EdgeWeightedAggregateDirected's backward (A^T's own graph tensors)."""
+
+    @staticmethod
+    def forward(ctx, X, edge_weight, *tail):
+        X = X.contiguous()
+        edge_weight = edge_weight.contiguous()
+        ctx.save_for_backward(X, edge_weight, *tail)
+        Xq, scale = HCSPMM.quantize_fp8(X)
+        return HCSPMM.forward_weighted_fp8(Xq, scale, edge_weight, *tail[:N_GRAPH])[0]
+
+
+def aggregate_fp8(X, edge_weight, graph, directed=False):
+    """weighted_aggregate with 8-bit feature storage in the forward: A_w (scale * e4m3(X / scale)), one fp32 scale per row of
+    X, accumulated in fp32.  The backward is weighted_aggregate's exact fp32 one.  X's width must be a multiple of 4."""
+    if edge_weight.requires_grad:
+        raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented; "
+                                  "pass values that do not require grad")
+    if X.size(1) % 4 != 0:
+        raise ValueError("aggregate_fp8 takes feature widths that are multiples of 4, got %d" % X.size(1))
+    if directed:
+        return EdgeWeightedAggregateDirectedFP8.apply(X, edge_weight, *graph, *transposed_graph(graph))
+    values_t = edge_weight.detach()[transpose_permutation(graph[0], graph[1])].contiguous()
+    return HCSPMMFunction_WeightedFP8.apply(X, edge_weight, values_t, *graph)
+
+
+class _UpdateOfAggregateFP8(torch.autograd.Function):
+    """agg8 W for agg8 = aggregate_fp8(X, ...), with the fp32 layer's weight gradient: dW = (A_w X)^T dY needs the fp32
+    aggregate, which the 8-bit forward never computed -- the backward computes it (one forward_weighted) instead of keeping
+    the quantised one.  d(agg8) = dY W^T goes on through aggregate_fp8's backward, so X, which is only read here, gets no
+    gradient from this function."""
+
+    @staticmethod
+    def forward(ctx, agg8, W, X, edge_weight, *graph):
+        ctx.save_for_backward(W, X, edge_weight, *graph)
+        return _mm(agg8.contiguous(), W)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        W, X, edge_weight, *graph = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_agg = _mm(d_out, W.transpose(0, 1)) if ctx.needs_input_grad[0] else None
+        d_w = None
+        if ctx.needs_input_grad[1]:
+            d_w = _weight_grad(HCSPMM.forward_weighted(X.contiguous(), edge_weight.contiguous(), *graph)[0], d_out)
+        return (d_agg, d_w, None, None) + (None,) * len(graph)
+
+
 class EdgeWeightedAggregate(torch.autograd.Function):
     """A_w X with the gradient for both operands: dX = A_w^T dY = forward_weighted(dY, w[perm]) as in
     HCSPMMFunction_Weighted, and dw[e] = <dY[row(e)], X[col(e)]> = HCSPMM.sddmm(dY, X)."""
@@ -583,6 +646,8 @@ class _Conv(torch.nn.Module):
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
         self.fixed = fixed
         self.directed = bool(directed)  # the edge_weight path only: the binary layer functions aggregate with A, as the reference
+        # "fp8": the edge_weight path aggregates 8-bit codes of its input (aggregate_fp8: quantised forward, exact fp32 backward)
+        self.feature_storage = "fp32"
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights.size(1))
@@ -595,6 +660,15 @@ class _Conv(torch.nn.Module):
         """edge_weight (float32 [E], aligned with column_index): aggregate with A_w (e.g. HCSPMM.edge_norm's "sym" / "mean"
         values) -- weighted aggregation + the update, no fused operators; None: the binary layer functions."""
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if self.feature_storage not in ("fp32", "fp8"):
+            raise ValueError("feature_storage must be 'fp32' or 'fp8', got %r" % (self.feature_storage,))
+        if self.feature_storage == "fp8":
+            if edge_weight is None:
+                raise ValueError("feature_storage = 'fp8' needs an edge_weight: the fused binary layer functions stay fp32")
+            if self.aggregate_first:
+                agg8 = aggregate_fp8(X, edge_weight, graph, self.directed)
+                return _UpdateOfAggregateFP8.apply(agg8, self.weights, X, edge_weight, *graph)
+            return aggregate_fp8(_Update.apply(X, self.weights), edge_weight, graph, self.directed)
         if edge_weight is not None:
             if self.aggregate_first:
                 return _Update.apply(weighted_aggregate(X, edge_weight, graph, self.directed), self.weights)

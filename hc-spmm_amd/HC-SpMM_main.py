@@ -65,7 +65,16 @@ def parse_args(argv=None):
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
     p.add_argument("--directed", action="store_true",
                    help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
+    # addition: 8-bit feature storage in the aggregation (GNN_model.aggregate_fp8: e4m3 codes + one fp32 scale per row in the
+    # forward, the exact fp32 backward); after training the model is evaluated once with each storage type
+    p.add_argument("--fp8", action="store_true", help="aggregate 8-bit (e4m3) features in the forward (--model gcn / gin with --norm)")
     args = p.parse_args(argv)
+    if args.fp8:
+        if args.model not in ("gcn", "gin") or args.norm == "none":
+            p.error("--fp8 needs --model gcn or gin and --norm sym or mean: the binary layer functions and the other models stay fp32")
+        widths = (args.dim, args.hidden) if args.model == "gin" else (args.hidden, args.classes)  # what the layers aggregate
+        if any(w % 4 != 0 for w in widths):
+            p.error("--fp8 aggregates widths %s, which must be multiples of 4" % (widths,))
     if args.directed and args.model in ("gcn", "gin") and args.norm == "none":
         p.error("--directed with --model %s needs --norm: the binary layer functions aggregate with A in the backward, as the "
                 "reference does" % args.model)
@@ -124,6 +133,13 @@ class Net(nn.Module):
             x = self.relu(conv(x, *self.graph, self.output, **self.ew))
         x = self.conv2(x, *self.graph, self.output, **self.ew)
         return F.log_softmax(x, dim=1)
+
+
+def set_feature_storage(model, storage):
+    """feature_storage of every GCNConv / GINConv of the model ("fp32" or "fp8")."""
+    for m in model.modules():
+        if isinstance(m, (GCNConv, GINConv)):
+            m.feature_storage = storage
 
 
 def main(argv=None):
@@ -193,6 +209,8 @@ def main(argv=None):
                                      output_dim)
             return GATv2Conv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
+    if args.fp8:
+        set_feature_storage(model, "fp8")
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 
     def train():
@@ -230,6 +248,17 @@ def main(argv=None):
     torch.cuda.synchronize()
     print("Train (ms/epoch):\t{:.3f}\tfinal loss {:.4f}".format((time.perf_counter() - t0) * 1e3 / max(args.epochs, 1),
                                                                  float(loss.detach()) if loss is not None else float("nan")))
+    if args.fp8:
+        log_probs = {}
+        model.eval()
+        with torch.no_grad():
+            for storage in ("fp8", "fp32"):
+                set_feature_storage(model, storage)
+                log_probs[storage] = model()
+        set_feature_storage(model, "fp8")
+        agree = (log_probs["fp8"].argmax(1) == log_probs["fp32"].argmax(1)).float().mean()
+        print("FP8 eval:\targmax agreement {:.4f}\tmax |log-prob diff| {:.4e}".format(
+            float(agree), float((log_probs["fp8"] - log_probs["fp32"]).abs().max())))
     return model
 
 

@@ -23,7 +23,11 @@ int fail_hip(hipError_t e) {
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
-inline int elem_bytes(int dtype) { return dtype == HCSPMM_DTYPE_F32 ? 4 : 2; }
+// 8-bit e4m3fn codes (hcspmm_forward_fp8): an element type of the launch decisions below only -- the typed entry points
+// refuse it (their dtype range ends at BF16)
+constexpr int kDtypeF8 = HCSPMM_DTYPE_BF16 + 1;
+
+inline int elem_bytes(int dtype) { return dtype == HCSPMM_DTYPE_F32 ? 4 : dtype == kDtypeF8 ? 1 : 2; }
 
 // Per-lane access width (in elements).  fp32: 16 bytes per lane for every embedding width of at least 4 columns, whatever
 // the row strides and base addresses are -- the kernels address fp32 vectors with element alignment and move a lane whose
@@ -47,6 +51,9 @@ int pick_vec(int dtype, int D, int64_t ldx, int64_t ldz, const void* X, const vo
 // the access width wide_choice assumes (from the embedding width alone, so that callers can ask ahead of a launch)
 inline int nominal_vec(int dtype, int D) {
   if (dtype == HCSPMM_DTYPE_F32) return D >= 4 ? 4 : D >= 2 ? 2 : 1;
+  // 8-bit codes: widths are multiples of 4 (hcspmm_forward_fp8 refuses the rest), 8 codes per lane from 32 columns up, as for the
+  // 16-bit types (whose accumulator shape those builds share)
+  if (dtype == kDtypeF8) return D >= 32 ? 8 : 4;
   return (D % 2 == 0 && D >= 32) ? 8 : (D % 2 == 0 && D >= 4) ? 4 : 1;
 }
 }  // namespace
@@ -82,7 +89,7 @@ static int panel_choice(const hcspmm_plan_header* h, int D, int dtype) {
     const long long cols = h->panel_cols < 0 ? D : (long long)h->panel_cols * (4 / elem_bytes(dtype));
     return cols >= D ? D : (int)cols;
   }
-  const int line_cols = 128 / elem_bytes(dtype);  // 32 fp32 or 64 16-bit columns: one cache line per gathered row
+  const int line_cols = 128 / elem_bytes(dtype);  // 32 fp32, 64 16-bit or 128 8-bit columns: one cache line per gathered row
   if (D < 2 * line_cols || h->n_tasks <= 0) return D;
   const double mean_len = (double)h->nnz_sparse / ((double)h->n_tasks + (double)h->n_slice_tasks);
   if (mean_len < 8.0) return D;
@@ -127,6 +134,13 @@ extern "C" int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* h, int 
   }
   int n_wide = 0;
   return wide_choice(h, D, dtype, &n_wide);
+}
+
+extern "C" int32_t hcspmm_wide_threshold_fp8(const hcspmm_plan_header* h, int D) {
+  if (D <= 0 || D % 4 != 0) return INT32_MAX;
+  if (!h) return (D + nominal_vec(kDtypeF8, D) - 1) / nominal_vec(kDtypeF8, D) > 32 ? INT32_MAX : 64;  // (as hcspmm_wide_threshold_typed)
+  int n_wide = 0;
+  return wide_choice(h, D, kDtypeF8, &n_wide);
 }
 
 extern "C" int32_t hcspmm_wide_threshold(const hcspmm_plan_header* h, int D) {
@@ -381,6 +395,76 @@ extern "C" int hcspmm_forward_weighted_indexed(const void* X, int64_t x_rows, in
   return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d,
                       ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads,
                       value_index ? value_index : &no_entries, num_values);
+}
+
+// 8-bit feature storage (quantize_fp8.hip, spmm_kernels_f8.hip, spmm_weighted_f8.hip): forward_impl's checks and launch
+// decisions for one-byte elements, fp32 Z, nullable values and per-row scales.
+extern "C" int hcspmm_quantize_fp8(const float* X, int64_t rows, int64_t ldx, int D, int format, const float* scale_in, void* Xq,
+                                   int64_t ldq, float* scale_out, void* stream_v) {
+  if (format != HCSPMM_FP8_E4M3) return HCSPMM_EINVAL;
+  if (rows < 0 || D <= 0 || D % 4 != 0 || ldx < D || ldq < D || ldq % 4 != 0) return HCSPMM_EINVAL;
+  if (rows == 0) return HCSPMM_OK;
+  if (!X || !Xq || (!scale_out && !scale_in) || !aligned(Xq, 4)) return HCSPMM_EINVAL;
+  const hipError_t e = hcspmm::launch_quantize_fp8(X, (long long)rows, (long long)ldx, D, scale_in, reinterpret_cast<unsigned char*>(Xq),
+                                                   (long long)ldq, scale_out, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" int hcspmm_forward_fp8(const void* Xq, int64_t x_rows, int64_t ldx, int format, const float* row_scale,
+                                  const float* values, float* Z, int64_t ldz, const int32_t* rowptr, const int32_t* col,
+                                  const int32_t* blockPartition, const int32_t* edgeToColumn, const int32_t* edgeToRow,
+                                  const int32_t* hybrid_type, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N,
+                                  int64_t E, int D, void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (format != HCSPMM_FP8_E4M3) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || x_rows < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
+  if (D % 4 != 0 || ldx % 4 != 0) return HCSPMM_EINVAL;  // rows of codes start on dwords
+  if (N == 0) return HCSPMM_OK;
+  if (!Xq || !Z || !rowptr || (E > 0 && !col) || !aligned(Xq, 4) || !aligned(Z, 4)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+  const int vec = nominal_vec(kDtypeF8, D);
+  const bool binary = !values && !row_scale;
+  hipError_t e;
+  if (plan_d && ph) {
+    const int rc = hcspmm_plan_check(ph, N, E, 0);
+    if (rc != HCSPMM_OK) return rc;
+    if (x_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows Xq does not have
+    const size_t need = hcspmm_workspace_bytes(ph, D);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
+    if (need > 0 && !aligned(workspace, 4)) return HCSPMM_EINVAL;
+    hcspmm::PlanArgs a;
+    fill_plan_args(a, plan_d, ph, N, D, kDtypeF8);
+    a.X = Xq;
+    a.Z = Z;
+    a.ldx = (size_t)ldx;
+    a.ldz = (size_t)ldz;
+    a.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
+    a.col = col;
+    if (binary) {
+      e = hcspmm::launch_plan_f8(a, vec, stream);
+    } else {
+      a.row_scale = row_scale;
+      e = hcspmm::launch_plan_w_f8(hcspmm::WPlanArgs{a, values, rowptr, ph->segment_len}, vec, stream);
+    }
+  } else {
+    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
+    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
+    hcspmm::WindowArgs a;
+    a.X = Xq;
+    a.Z = Z;
+    a.ldx = (size_t)ldx;
+    a.ldz = (size_t)ldz;
+    a.rowptr = rowptr;
+    a.col = col;
+    a.blockPartition = blockPartition;
+    a.edgeToColumn = edgeToColumn;
+    a.edgeToRow = edgeToRow;
+    a.hybrid_type = hybrid_type;
+    a.N = (int)N;
+    a.D = D;
+    e = binary ? hcspmm::launch_window_f8(a, vec, stream) : hcspmm::launch_window_w_f8(hcspmm::WWindowArgs{a, values, row_scale}, vec, stream);
+  }
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
 namespace {

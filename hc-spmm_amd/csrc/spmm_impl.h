@@ -45,9 +45,11 @@
 namespace hcspmm {
 
 // ---------------------------------------------------------------- element types and lane vectors
-struct F32 { typedef float T; };
-struct F16 { typedef unsigned short T; };   // IEEE binary16 bits
-struct BF16 { typedef unsigned short T; };  // bfloat16 bits
+// T: an element of X as stored; Z: an element of the output (the 8-bit build reads codes and stores fp32 sums)
+struct F32 { typedef float T; typedef float Z; };
+struct F16 { typedef unsigned short T; typedef unsigned short Z; };   // IEEE binary16 bits
+struct BF16 { typedef unsigned short T; typedef unsigned short Z; };  // bfloat16 bits
+struct F8 { typedef unsigned char T; typedef float Z; };              // OCP e4m3fn codes (hcspmm_forward_fp8)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -77,6 +79,10 @@ template <> struct RawT<BF16, 8> { typedef u32x4 type; };
 template <> struct RawT<BF16, 4> { typedef u32x2 type; };
 template <> struct RawT<BF16, 2> { typedef unsigned int type; };
 template <> struct RawT<BF16, 1> { typedef unsigned short type; };
+template <> struct RawT<F8, 8> { typedef u32x2 type; };
+template <> struct RawT<F8, 4> { typedef unsigned int type; };
+template <> struct RawT<F8, 2> { typedef unsigned short type; };
+template <> struct RawT<F8, 1> { typedef unsigned char type; };
 
 template <typename E> __device__ __forceinline__ float widen(unsigned short h);
 template <> __device__ __forceinline__ float widen<F16>(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
@@ -93,6 +99,14 @@ template <> __device__ __forceinline__ unsigned short narrow<BF16>(float f) {  /
 __device__ __forceinline__ unsigned rword(const u32x4& v, int i) { return v[i]; }
 __device__ __forceinline__ unsigned rword(const u32x2& v, int i) { return v[i]; }
 __device__ __forceinline__ unsigned rword(const unsigned& v, int) { return v; }
+__device__ __forceinline__ unsigned rword(const unsigned short& v, int) { return v; }
+__device__ __forceinline__ unsigned rword(const unsigned char& v, int) { return v; }
+// element q of the four e4m3fn codes in w, widened (exact): v_cvt_pk_f32_fp8 widens one half of the dword per instruction
+__device__ __forceinline__ float widen_f8(unsigned w, int q) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  return (q & 2) ? hi[q & 1] : lo[q & 1];
+}
 __device__ __forceinline__ void rset(u32x4& v, int i, unsigned w) { v[i] = w; }
 __device__ __forceinline__ void rset(u32x2& v, int i, unsigned w) { v[i] = w; }
 __device__ __forceinline__ void rset(unsigned& v, int, unsigned w) { v = w; }
@@ -111,11 +125,15 @@ template <> struct MemF32<1> { typedef float type; };
 template <int WORDS> struct MemU32 { typedef unsigned int type __attribute__((ext_vector_type(WORDS), aligned(4))); };
 template <> struct MemU32<1> { typedef unsigned int type; };
 
+// 8-bit rows are addressed like the 16-bit ones: dword-aligned vectors of four codes (widths and strides that are multiples of 4),
+// the last lane moved back onto the row's last VEC codes; the narrow dense-tile lanes (2 codes, 1 code) load them as they are.
+
 // first of the VEC feature columns a lane covers, given the aligned position c < cend of its slot in [.., cend)
 template <int VEC> __device__ __forceinline__ int lane_col(int c, int cend) { return VEC == 1 ? c : min(c, cend - VEC); }
 
 template <typename E, int VEC> struct Lane {
   typedef typename E::T T;
+  typedef typename E::Z ZT;
   typedef typename RawT<E, VEC>::type raw_t;
   typedef typename AccT<VEC>::type acc_t;
   static __device__ __forceinline__ raw_t zero() {
@@ -125,6 +143,8 @@ template <typename E, int VEC> struct Lane {
   }
   static __device__ __forceinline__ raw_t load(const T* p) {
     if constexpr (sizeof(T) == 4) return *reinterpret_cast<const typename MemF32<VEC>::type*>(p);
+    else if constexpr (sizeof(T) == 1 && VEC >= 4) return *reinterpret_cast<const typename MemU32<VEC / 4>::type*>(p);
+    else if constexpr (sizeof(T) == 1) return *reinterpret_cast<const raw_t*>(p);
     else if constexpr (VEC >= 2) return *reinterpret_cast<const typename MemU32<VEC / 2>::type*>(p);
     else return *reinterpret_cast<const raw_t*>(p);
   }
@@ -132,6 +152,7 @@ template <typename E, int VEC> struct Lane {
   // element q of a loaded vector, widened (exact)
   static __device__ __forceinline__ float elem(const raw_t& v, int q) {
     if constexpr (sizeof(T) == 4) return aget(v, q);
+    else if constexpr (sizeof(T) == 1) return widen_f8(rword(v, q >> 2), q & 3);
     else if constexpr (VEC == 1) return widen<E>(v);
     else {
       const unsigned w = rword(v, q >> 1);
@@ -157,8 +178,9 @@ template <typename E, int VEC> struct Lane {
     }
   }
   // Z rows are written once and not re-read by this launch: non-temporal stores (0-5 %, profiles/r01/ab_nt_store.log)
-  static __device__ __forceinline__ void store(T* p, const acc_t& acc) {
-    if constexpr (sizeof(T) == 4) __builtin_nontemporal_store(pack(acc), reinterpret_cast<typename MemF32<VEC>::type*>(p));
+  static __device__ __forceinline__ void store(ZT* p, const acc_t& acc) {
+    if constexpr (sizeof(T) == 1) store_partial(p, acc);  // fp32 sums of 8-bit codes
+    else if constexpr (sizeof(T) == 4) __builtin_nontemporal_store(pack(acc), reinterpret_cast<typename MemF32<VEC>::type*>(p));
     else if constexpr (VEC >= 2) __builtin_nontemporal_store(pack(acc), reinterpret_cast<typename MemU32<VEC / 2>::type*>(p));
     else __builtin_nontemporal_store(pack(acc), reinterpret_cast<raw_t*>(p));
   }
@@ -236,7 +258,7 @@ __device__ __forceinline__ void gather_batch(const typename E::T* __restrict__ X
 // dstZ (a row of Z, element type) or dstP (a partial-sum row of the fp32 workspace).
 // ------------------------------------------------------------------------------------------
 template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U>
-__device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X, typename E::T* __restrict__ dstZ,
+__device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
                                             float* __restrict__ dstP, const int* __restrict__ col, int e0, int n,
                                             size_t ldx, int c0, int cend, int lane) {
   typedef Lane<E, VEC> Ln;
@@ -313,7 +335,7 @@ __device__ __forceinline__ void tiny_tasks(const PlanArgs& a, int first, int c0,
   typedef Lane<E, VEC> Ln;
   typedef typename E::T elem_t;
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   constexpr int R = 64 / L;
   const int g = lane / L, s = lane & (L - 1);
   const int4* tasks = reinterpret_cast<const int4*>(a.plan + a.off_tasks);
@@ -367,7 +389,7 @@ __device__ __forceinline__ void tiny_tasks(const PlanArgs& a, int first, int c0,
 // instructions lane l holds Z[row 4*(l>>4)+r][panel + j*VEC .. +VEC) -- a contiguous vector.
 // ------------------------------------------------------------------------------------------
 template <typename E, int VEC>
-__device__ __forceinline__ void dense_store(typename E::T* __restrict__ Z, const f32x4 (&acc)[VEC], int window, int kq,
+__device__ __forceinline__ void dense_store(typename E::Z* __restrict__ Z, const f32x4 (&acc)[VEC], int window, int kq,
                                             int c, int N, size_t ldz) {
   typedef Lane<E, VEC> Ln;
 #pragma unroll
@@ -405,7 +427,8 @@ __device__ __forceinline__ void dense_chain(const typename E::T* __restrict__ X,
     const int myU = (kb * 4 + lane < K4 * 4) ? U[kb * 4 + lane] : -1;
     const int steps = min(16, K4 - kb);
     // same bytes in flight per lane whatever the panel width
-    constexpr int B = DB * 16 / (VEC * (int)sizeof(typename E::T));
+    constexpr int B0 = DB * 16 / (VEC * (int)sizeof(typename E::T));
+    constexpr int B = (sizeof(typename E::T) == 1 && B0 > DB) ? DB : B0;  // 8-bit rows: DB gathers in flight, as at 16 bytes per lane
     for (int t0 = 0; t0 < steps; t0 += B) {
       // Branch-free batch (see sparse_task): padded columns (U = -1) and steps past the end re-read
       // row 0 and are zeroed by the select; their A tile is zero as well.
@@ -435,7 +458,7 @@ __device__ __forceinline__ void dense_chain(const typename E::T* __restrict__ X,
 }
 
 template <typename E, int VEC>
-__device__ __forceinline__ void dense_unit(const typename E::T* __restrict__ X, typename E::T* __restrict__ Z,
+__device__ __forceinline__ void dense_unit(const typename E::T* __restrict__ X, typename E::Z* __restrict__ Z,
                                            const int* __restrict__ U, cu64_p masks, int K4, int window, int panel,
                                            int N, int D, size_t ldx, size_t ldz, int lane) {
   const int kq = lane >> 4, j = lane & 15;
@@ -528,7 +551,7 @@ __device__ __forceinline__ void compact_chain(const typename E::T* __restrict__ 
 }
 
 template <typename E, int VEC, int C>
-__device__ __forceinline__ void dense_compact_unit(const typename E::T* __restrict__ X, typename E::T* __restrict__ Z,
+__device__ __forceinline__ void dense_compact_unit(const typename E::T* __restrict__ X, typename E::Z* __restrict__ Z,
                                                    const int* __restrict__ recp, int panel, int N, int D, size_t ldx,
                                                    size_t ldz, int lane) {
   constexpr int KMAX = C == 1 ? HCSPMM_COMPACT_K : HCSPMM_COMPACT2_K;
@@ -704,7 +727,7 @@ template <typename E, int L, int VEC, int UNROLL, int MINW, bool FUSED = false>
 __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a) {
   typedef typename E::T elem_t;
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if ((int)blockIdx.x < a.sparse_wgs) {
@@ -724,7 +747,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
       const int tid = bf * kWaves + wave;
       if (tid >= a.n_wide) return;
       const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      elem_t* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
+      typename E::Z* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
       float* dp = (t.w < 0) ? nullptr : a.partial + (size_t)t.w * (size_t)a.D;
       sparse_task<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, __builtin_amdgcn_readfirstlane(t.y),
                                            __builtin_amdgcn_readfirstlane(t.z), a.ldx, c0, cend, lane);
@@ -760,7 +783,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
         if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
       }
       int e0 = 0, n = 0;
-      elem_t* dz = nullptr;
+      typename E::Z* dz = nullptr;
       float* dp = nullptr;
       if (tp != nullptr) {
         const int4 t = *tp;
@@ -861,7 +884,7 @@ template <typename E, int VEC>
 __global__ __launch_bounds__(kThreads) void fixup_kernel(PlanArgs a) {
   typedef Lane<E, VEC> Ln;
   typedef typename Ln::acc_t acc_t;
-  typename E::T* Z = reinterpret_cast<typename E::T*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   const int lane = threadIdx.x & 63;
   const int fi = (int)blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (fi >= a.n_split_rows) return;
@@ -909,7 +932,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_kernel(WindowArgs a) {
   typedef Lane<E, VEC> Ln;
   typedef typename E::T elem_t;
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   __shared__ int s_U[kChunkK];
   __shared__ unsigned int s_mask[kChunkK / 4 * 2];  // 64-bit lane masks as two 32-bit halves
   const int lane = threadIdx.x & 63;
@@ -925,7 +948,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_kernel(WindowArgs a) {
     for (int rb = r0; rb < r1; rb += G) {  // uniform
       const int r = rb + gi;
       int e0 = 0, n = 0;
-      elem_t* dst = nullptr;
+      typename E::Z* dst = nullptr;
       if (r < r1) {
         e0 = a.rowptr[r];
         n = a.rowptr[r + 1] - e0;

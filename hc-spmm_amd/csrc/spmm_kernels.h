@@ -38,7 +38,13 @@ struct PlanArgs {
   // out (N x H, row-major); Z is then the operator's out2.  W: D x H with element strides (w_ldr, w_ldc).
   int fused, H;
   int fused_dense_wgs;  // filled by the launcher: workgroups of the fused dense region (each strides over windows)
-  const float* W;
+  union {
+    const float* W;
+    // 8-bit weighted launches (spmm_weighted_f8.hip; they have no fused form): [x_rows] fp32 scales of the gathered rows, or null.
+    // Entry e of column c weighs values[e] * row_scale[c], one fp32 multiplication; a null values / row_scale is 1 (both null is
+    // the binary launch, launch_plan_f8)
+    const float* row_scale;
+  };
   long long w_ldr, w_ldc;
   float* out;
 };
@@ -78,6 +84,7 @@ struct WPlanArgs {
 struct WWindowArgs {
   WindowArgs w;
   const float* values;  // [E]
+  const float* row_scale;  // 8-bit launches only: PlanArgs::row_scale of the plan-free form
 };
 
 // vec = elements per lane access.  fp32: 4 for every D >= 4 (element-aligned vectors: any stride, any base address), 2 / 1 for
@@ -97,6 +104,14 @@ hipError_t launch_plan_w_f16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_f16(const WWindowArgs& a, int vec, hipStream_t stream);
 hipError_t launch_plan_w_bf16(const WPlanArgs& a, int vec, hipStream_t stream);
 hipError_t launch_window_w_bf16(const WWindowArgs& a, int vec, hipStream_t stream);
+// 8-bit e4m3fn codes in, fp32 out (vec: 8 for D >= 32, else 4; D, strides and bases on the dword grid)
+hipError_t launch_plan_f8(const PlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_f8(const WindowArgs& a, int vec, hipStream_t stream);
+hipError_t launch_plan_w_f8(const WPlanArgs& a, int vec, hipStream_t stream);
+hipError_t launch_window_w_f8(const WWindowArgs& a, int vec, hipStream_t stream);
+// per-row quantiser (quantize_fp8.hip): s[r] = amax_r / 448 (or scale_in[r]), q = rne_e4m3(clamp(x / s[r], -448, 448))
+hipError_t launch_quantize_fp8(const float* X, long long rows, long long ldx, int D, const float* scale_in, unsigned char* Xq,
+                               long long ldq, float* scale_out, hipStream_t stream);
 // the multi-head weighted forms (spmm_weighted_heads_impl.h): values [heads][E], column c takes head c / dh's.  Entry e of
 // head h weighs values[h * E + e] (direct: vindex == nullptr; spmm_weighted_heads.hip, hcspmm_forward_weighted_heads) or
 // values[h * E + vindex[e]] (indexed; spmm_weighted_indexed.hip, hcspmm_forward_weighted_indexed).  fp32 only

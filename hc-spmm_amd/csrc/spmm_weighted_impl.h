@@ -15,10 +15,40 @@
 //    row, so the j-th set bit of row i over the window's ascending columns is CSR entry rowptr[w*16 + i] + j: each lane
 //    keeps a running popcount of its row's bits over the k-steps and loads values[entry] in the batch of its X gathers.
 //    The A operand is that value instead of 1.0; v_mfma_f32_16x16x4_f32 stays a k-ordered fma chain.
+//
+// 8-bit features (spmm_weighted_f8.hip, hcspmm_forward_fp8): the same kernels with the entry weight read through
+// entry_weight() -- values[e] times the fp32 scale of the gathered row, row_scale[col[e]], either of which may be absent.  The lane
+// that loads col[e] loads the scale behind it (one dependent 4-byte gather) and multiplies before the broadcast, so the
+// gathering lanes see one weight per entry, as in the fp32 / 16-bit builds.
 #pragma once
 #include "spmm_impl.h"
 
 namespace hcspmm {
+
+// Weight of a CSR entry whose column is c (c >= 0), read through a cursor `p` that stands at the entry: p + k is the cursor k
+// entries on.  Plain values (the fp32 / 16-bit builds): the cursor is a pointer into values.
+__device__ __forceinline__ float entry_weight(const float* p, int) { return *p; }
+// The 8-bit build: w = values[e] * row_scale[c], one fp32 multiplication; a missing operand is 1.
+struct ScaledCursor {
+  const float* values;     // at the entry, or null
+  const float* row_scale;  // [x_rows], or null
+  __device__ __forceinline__ ScaledCursor operator+(int k) const { return ScaledCursor{values != nullptr ? values + k : nullptr, row_scale}; }
+};
+__device__ __forceinline__ float entry_weight(const ScaledCursor& p, int c) {
+  float w = p.values != nullptr ? *p.values : 1.0f;
+  if (p.row_scale != nullptr) w *= p.row_scale[c];
+  return w;
+}
+// a cursor as a function parameter: the plain pointer keeps its __restrict__ (W is then named at the call, not deduced)
+template <typename W> struct WParam { typedef W type; };
+template <> struct WParam<const float*> { typedef const float* __restrict__ type; };
+__device__ __forceinline__ const float* row_scale_of(const WPlanArgs& wa) { return wa.p.row_scale; }
+__device__ __forceinline__ const float* row_scale_of(const WWindowArgs& wa) { return wa.row_scale; }
+// the cursor at entry 0 of a launch (WA: WPlanArgs / WWindowArgs)
+template <typename E, typename WA> __device__ __forceinline__ auto weights_of(const WA& wa) {
+  if constexpr (sizeof(typename E::T) == 1) return ScaledCursor{wa.values, row_scale_of(wa)};
+  else return wa.values;
+}
 
 // acc[q] = fmaf(w, x[q], acc[q]) for the VEC (widened) elements of one loaded vector
 template <typename E, int VEC>
@@ -29,10 +59,10 @@ __device__ __forceinline__ void wfma(typename AccT<VEC>::type& acc, float w, con
 
 // gather_batch with the entry values broadcast alongside the column indices (lanes past a task's end hold idx -1 and
 // value 0: fmaf(0, 0, acc) adds +0 exactly as the binary batch does)
-template <typename E, int VEC, int UB>
+template <typename E, int VEC, int UB, typename W>
 __device__ __forceinline__ void gather_batch_w(const typename E::T* __restrict__ X, size_t ldx, int csafe, bool cok, int myidx,
                                                float myval, int src0, typename AccT<VEC>::type& acc, const int* pf_col,
-                                               const float* pf_val, int& next, float& nextv) {
+                                               W pf_val, int& next, float& nextv) {
   typedef Lane<E, VEC> Ln;
   int idx[UB];
   float w[UB];
@@ -44,7 +74,7 @@ __device__ __forceinline__ void gather_batch_w(const typename E::T* __restrict__
   }
   if (pf_col != nullptr) {
     next = *pf_col;
-    nextv = *pf_val;
+    nextv = entry_weight(pf_val, next);
   }
 #pragma unroll
   for (int u = 0; u < UB; ++u) v[u] = Ln::load(X + (size_t)max(idx[u], 0) * ldx + csafe);
@@ -55,12 +85,17 @@ __device__ __forceinline__ void gather_batch_w(const typename E::T* __restrict__
   }
 }
 
+// tiny tasks per lane group in the hybrid launch's tiny region: TinyT (spmm_impl.h), except that the 8-bit build -- values, scales
+// and the fp32 sums of 8 columns per lane -- keeps at most two in flight (four spill 20 bytes at L = 32)
+template <typename E, int L> struct TinyWT {
+  static constexpr int value = (sizeof(typename E::T) == 1 && TinyT<L>::value > 2) ? 2 : TinyT<L>::value;
+};
+
 // sparse_task (spmm_impl.h) with weights: the same chunking, batches and combine tree
-template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U>
-__device__ __forceinline__ void sparse_task_w(const typename E::T* __restrict__ X, typename E::T* __restrict__ dstZ,
-                                              float* __restrict__ dstP, const int* __restrict__ col,
-                                              const float* __restrict__ vals, int e0, int n, size_t ldx, int c0, int cend,
-                                              int lane) {
+template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U, typename W = const float*>
+__device__ __forceinline__ void sparse_task_w(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
+                                              float* __restrict__ dstP, const int* __restrict__ col, W vals, int e0,
+                                              int n, size_t ldx, int c0, int cend, int lane) {
   typedef Lane<E, VEC> Ln;
   typedef typename Ln::acc_t acc_t;
   constexpr int U = (L < UMAX) ? L : UMAX;
@@ -84,7 +119,7 @@ __device__ __forceinline__ void sparse_task_w(const typename E::T* __restrict__ 
     float nextv = 0.f;
     if (pos < n) {
       next = col[e0 + pos];
-      nextv = vals[e0 + pos];
+      nextv = entry_weight(vals + (e0 + pos), next);
     }
     for (int base = 0; base < nmax; base += STRIDE) {
       const int myidx = next;
@@ -94,7 +129,7 @@ __device__ __forceinline__ void sparse_task_w(const typename E::T* __restrict__ 
       nextv = 0.f;
       const int cnt = min(L, nmax - base);
       const int* pf = more ? col + e0 + base + STRIDE + pos : nullptr;
-      const float* pfv = vals + e0 + base + STRIDE + pos;  // read only when pf is set
+      const W pfv = vals + e0 + base + STRIDE + pos;  // read only when pf is set
       for (int j = 0; j < cnt;) {
         const int left = cnt - j;
         if (left > U / 2) {
@@ -149,7 +184,7 @@ __device__ __forceinline__ void tiny_tasks_w(const WPlanArgs& wa, int first, int
   typedef typename E::T elem_t;
   const PlanArgs& a = wa.p;
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   constexpr int R = 64 / L;
   const int g = lane / L, s = lane & (L - 1);
   const int4* tasks = reinterpret_cast<const int4*>(a.plan + a.off_tasks);
@@ -172,8 +207,8 @@ __device__ __forceinline__ void tiny_tasks_w(const WPlanArgs& wa, int first, int
   for (int t = 0; t < T; ++t) {
     int e = 0;
     if (d[t].y >= 0) e = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(wa, -(d[t].x + 1));
-    w0[t] = d[t].y >= 0 ? wa.values[e] : 0.f;
-    w1[t] = d[t].w >= 0 ? wa.values[e + 1] : 0.f;
+    w0[t] = d[t].y >= 0 ? entry_weight(weights_of<E>(wa) + e, d[t].y) : 0.f;
+    w1[t] = d[t].w >= 0 ? entry_weight(weights_of<E>(wa) + (e + 1), d[t].w) : 0.f;
   }
   for (int pbase = c0; pbase < cend; pbase += L * VEC) {
     const bool cok = pbase + s * VEC < cend;
@@ -230,10 +265,10 @@ __device__ __forceinline__ int window_row_first(const int* __restrict__ rowptr, 
   return row < N ? rowptr[row] : 0;
 }
 
-template <typename E, int VEC>
+template <typename E, int VEC, typename W>
 __device__ __forceinline__ void dense_chain_w(const typename E::T* __restrict__ X, const int* __restrict__ U, cu64_p masks,
                                               int K4, int csafe, bool cok, size_t ldx, int lane, f32x4 (&acc)[VEC],
-                                              const float* __restrict__ vals, EntryRun& er) {
+                                              typename WParam<W>::type vals, EntryRun& er) {
   typedef Lane<E, VEC> Ln;
   const int kq = lane >> 4;
   for (int kb = 0; kb < K4; kb += 16) {
@@ -241,7 +276,8 @@ __device__ __forceinline__ void dense_chain_w(const typename E::T* __restrict__ 
     const int steps = min(16, K4 - kb);
     // half the binary batch: with the value operand next to every gather, the full batch spilled 60-76 bytes per lane
     // at five waves per SIMD (the compact records keep their 8-step batches)
-    constexpr int B = HCSPMM_DENSE_B * 8 / (VEC * (int)sizeof(typename E::T));
+    constexpr int B0 = HCSPMM_DENSE_B * 8 / (VEC * (int)sizeof(typename E::T));
+    constexpr int B = (sizeof(typename E::T) == 1 && B0 > HCSPMM_DENSE_B / 2) ? HCSPMM_DENSE_B / 2 : B0;  // (8-bit rows: as at 16 bytes per lane)
     for (int t0 = 0; t0 < steps; t0 += B) {
       int idx[B];
       bool on[B];
@@ -252,7 +288,7 @@ __device__ __forceinline__ void dense_chain_w(const typename E::T* __restrict__ 
         const int t = t0 + u;
         idx[u] = __shfl(myU, (4 * t + kq) & 63, 64);
         const unsigned long long m = t < steps ? masks[min(kb + t, K4 - 1)] : 0ull;  // wave-uniform: scalar load
-        a[u] = vals[er.step(m, lane, &on[u])];  // the value loads lead the batch: the entry positions die at once
+        a[u] = entry_weight(vals + er.step(m, lane, &on[u]), max(idx[u], 0));  // the value loads lead the batch: the entry positions die at once
         if (t >= steps) idx[u] = -1;
       }
 #pragma unroll
@@ -270,10 +306,10 @@ __device__ __forceinline__ void dense_chain_w(const typename E::T* __restrict__ 
   }
 }
 
-template <typename E, int VEC>
-__device__ __forceinline__ void dense_unit_w(const typename E::T* __restrict__ X, typename E::T* __restrict__ Z,
+template <typename E, int VEC, typename W>
+__device__ __forceinline__ void dense_unit_w(const typename E::T* __restrict__ X, typename E::Z* __restrict__ Z,
                                              const int* __restrict__ U, cu64_p masks, int K4, int window, int panel, int N,
-                                             int D, size_t ldx, size_t ldz, int lane, const float* __restrict__ vals,
+                                             int D, size_t ldx, size_t ldz, int lane, typename WParam<W>::type vals,
                                              const int* __restrict__ rowptr) {
   const int kq = lane >> 4, j = lane & 15;
   const bool cok = panel * 16 * VEC + j * VEC < D;
@@ -282,36 +318,36 @@ __device__ __forceinline__ void dense_unit_w(const typename E::T* __restrict__ X
 #pragma unroll
   for (int q = 0; q < VEC; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
   EntryRun er(lane, window_row_first(rowptr, window, N, lane));
-  dense_chain_w<E, VEC>(X, U, masks, K4, c, cok, ldx, lane, acc, vals, er);
+  dense_chain_w<E, VEC, W>(X, U, masks, K4, c, cok, ldx, lane, acc, vals, er);
   if (cok) dense_store<E, VEC>(Z, acc, window, kq, c, N, ldz);
 }
 
 // CompactSteps (spmm_impl.h) with weights
 template <typename E, int VEC, int C, int KMAX, int STEPS, int T0>
 struct CompactStepsW {
-  template <int U>
+  template <int U, typename W>
   static __device__ __forceinline__ void meta(const Rec<C>& rec, int K4, int kq, int lane, int* idx, float* a, bool* on,
-                                              const float* __restrict__ vals, EntryRun& er) {
+                                              typename WParam<W>::type vals, EntryRun& er) {
     if constexpr (U < STEPS) {
       constexpr int t = T0 + U;
       idx[U] = rec.template gather4<2 + 4 * t>(kq);
       const unsigned lo = (unsigned)rec.template scalar<2 + KMAX + 2 * t>();
       const unsigned hi = (unsigned)rec.template scalar<3 + KMAX + 2 * t>();
       const unsigned long long m = t < K4 ? (((unsigned long long)hi << 32) | lo) : 0ull;
-      a[U] = vals[er.step(m, lane, &on[U])];
+      a[U] = entry_weight(vals + er.step(m, lane, &on[U]), max(idx[U], 0));
       if (t >= K4) idx[U] = -1;
-      meta<U + 1>(rec, K4, kq, lane, idx, a, on, vals, er);
+      meta<U + 1, W>(rec, K4, kq, lane, idx, a, on, vals, er);
     }
   }
+  template <typename W>
   static __device__ __forceinline__ void run(const typename E::T* __restrict__ X, const Rec<C>& rec, int K4, int csafe, bool cok,
-                                             size_t ldx, int lane, f32x4 (&acc)[VEC], const float* __restrict__ vals,
-                                             EntryRun& er) {
+                                             size_t ldx, int lane, f32x4 (&acc)[VEC], typename WParam<W>::type vals, EntryRun& er) {
     typedef Lane<E, VEC> Ln;
     int idx[STEPS];
     bool on[STEPS];
     typename Ln::raw_t x[STEPS];
     float a[STEPS];
-    meta<0>(rec, K4, lane >> 4, lane, idx, a, on, vals, er);
+    meta<0, W>(rec, K4, lane >> 4, lane, idx, a, on, vals, er);
 #pragma unroll
     for (int u = 0; u < STEPS; ++u) x[u] = Ln::load(X + (size_t)max(idx[u], 0) * ldx + csafe);
 #pragma unroll
@@ -326,10 +362,10 @@ struct CompactStepsW {
   }
 };
 
-template <typename E, int VEC, int C>
-__device__ __forceinline__ void dense_compact_unit_w(const typename E::T* __restrict__ X, typename E::T* __restrict__ Z,
+template <typename E, int VEC, int C, typename W>
+__device__ __forceinline__ void dense_compact_unit_w(const typename E::T* __restrict__ X, typename E::Z* __restrict__ Z,
                                                      const int* __restrict__ recp, int panel, int N, int D, size_t ldx,
-                                                     size_t ldz, int lane, const float* __restrict__ vals,
+                                                     size_t ldz, int lane, typename WParam<W>::type vals,
                                                      const int* __restrict__ rowptr) {
   constexpr int KMAX = C == 1 ? HCSPMM_COMPACT_K : HCSPMM_COMPACT2_K;
   Rec<C> rec;
@@ -346,18 +382,18 @@ __device__ __forceinline__ void dense_compact_unit_w(const typename E::T* __rest
   EntryRun er(lane, window_row_first(rowptr, window, N, lane));
   typedef CompactStepsW<E, VEC, C, KMAX, 8, 0> S8;
   if constexpr (C == 1) {  // K4 <= 10
-    if (K4 <= 2) CompactStepsW<E, VEC, C, KMAX, 2, 0>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
-    else if (K4 <= 4) CompactStepsW<E, VEC, C, KMAX, 4, 0>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+    if (K4 <= 2) CompactStepsW<E, VEC, C, KMAX, 2, 0>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+    else if (K4 <= 4) CompactStepsW<E, VEC, C, KMAX, 4, 0>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
     else {
-      S8::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
-      if (K4 > 8) CompactStepsW<E, VEC, C, KMAX, 2, 8>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+      S8::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+      if (K4 > 8) CompactStepsW<E, VEC, C, KMAX, 2, 8>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
     }
   } else {  // 12 <= K4 <= 20
-    S8::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
-    if (K4 <= 12) CompactStepsW<E, VEC, C, KMAX, 4, 8>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+    S8::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+    if (K4 <= 12) CompactStepsW<E, VEC, C, KMAX, 4, 8>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
     else {
-      CompactStepsW<E, VEC, C, KMAX, 8, 8>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
-      if (K4 > 16) CompactStepsW<E, VEC, C, KMAX, 4, 16>::run(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+      CompactStepsW<E, VEC, C, KMAX, 8, 8>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
+      if (K4 > 16) CompactStepsW<E, VEC, C, KMAX, 4, 16>::template run<W>(X, rec, K4, c, cok, ldx, lane, acc, vals, er);
     }
   }
   if (cok) dense_store<E, VEC>(Z, acc, window, kq, c, N, ldz);
@@ -372,9 +408,10 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
   typedef typename E::T elem_t;
   const PlanArgs& a = wa.p;
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  typedef decltype(weights_of<E>(wa)) W;
   if ((int)blockIdx.x < a.sparse_wgs) {
     const int p = (int)blockIdx.x / a.sparse_wgs_pp;
     const int b = (int)blockIdx.x - p * a.sparse_wgs_pp;
@@ -385,16 +422,16 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
       const int tid = bf * kWaves + wave;
       if (tid >= a.n_wide) return;
       const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      elem_t* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
+      typename E::Z* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
       float* dp = (t.w < 0) ? nullptr : a.partial + (size_t)t.w * (size_t)a.D;
-      sparse_task_w<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, wa.values, __builtin_amdgcn_readfirstlane(t.y),
+      sparse_task_w<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, weights_of<E>(wa), __builtin_amdgcn_readfirstlane(t.y),
                                              __builtin_amdgcn_readfirstlane(t.z), a.ldx, c0, cend, lane);
     } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
       if (bf >= a.free_wgs_pp) return;
       constexpr int R = 64 / L;
-      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * TinyT<L>::value);
+      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * TinyWT<E, L>::value);
       if (first >= a.n_tasks) return;
-      tiny_tasks_w<E, L, VEC, TinyT<L>::value>(wa, first, c0, cend, lane);
+      tiny_tasks_w<E, L, VEC, TinyWT<E, L>::value>(wa, first, c0, cend, lane);
     } else {
       constexpr int R = 64 / L;
       const int g = lane / L;
@@ -415,7 +452,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
         if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
       }
       int e0 = 0, n = 0;
-      elem_t* dz = nullptr;
+      typename E::Z* dz = nullptr;
       float* dp = nullptr;
       if (tp != nullptr) {
         const int4 t = *tp;
@@ -426,7 +463,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
           else dp = a.partial + (size_t)t.w * (size_t)a.D;
         }
       }
-      sparse_task_w<E, L, VEC, false, UNROLL>(X, dz, dp, a.col, wa.values, e0, n, a.ldx, c0, cend, lane);
+      sparse_task_w<E, L, VEC, false, UNROLL>(X, dz, dp, a.col, weights_of<E>(wa), e0, n, a.ldx, c0, cend, lane);
     }
   } else {
     constexpr int VM = DenseV<VEC>::mid;
@@ -438,17 +475,17 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
       if (unit < a.n_dense_compact2 * a.n_panels) {
         const int panel = unit / a.n_dense_compact2, ci = unit - panel * a.n_dense_compact2;
         const int* rec = a.plan + a.off_dense_compact2 + ci * HCSPMM_COMPACT2_WORDS;
-        if (a.dense_vec == VEC) dense_compact_unit_w<E, VEC, 2>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-        else if (a.dense_vec == VM) dense_compact_unit_w<E, VM, 2>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-        else dense_compact_unit_w<E, 1, 2>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
+        if (a.dense_vec == VEC) dense_compact_unit_w<E, VEC, 2, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+        else if (a.dense_vec == VM) dense_compact_unit_w<E, VM, 2, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+        else dense_compact_unit_w<E, 1, 2, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
         return;
       }
       unit -= a.n_dense_compact2 * a.n_panels;
       const int panel = unit / a.n_dense_compact, ci = unit - panel * a.n_dense_compact;
       const int* rec = a.plan + a.off_dense_compact + ci * HCSPMM_COMPACT_WORDS;
-      if (a.dense_vec == VEC) dense_compact_unit_w<E, VEC, 1>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-      else if (a.dense_vec == VM) dense_compact_unit_w<E, VM, 1>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-      else dense_compact_unit_w<E, 1, 1>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
+      if (a.dense_vec == VEC) dense_compact_unit_w<E, VEC, 1, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+      else if (a.dense_vec == VM) dense_compact_unit_w<E, VM, 1, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+      else dense_compact_unit_w<E, 1, 1, W>(X, Z, rec, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
       return;
     }
     const int panel = unit / n_reg, di = unit - panel * n_reg;
@@ -456,15 +493,17 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_w_kernel(WPlanArgs
     const int4 d = int4{dix[0], dix[1], dix[2], dix[3]};
     const int* U = a.plan + a.off_dense_pack + d.y;
     cu64_p masks = (cu64_p)(U + 4 * d.z);
-    if (a.dense_vec == VEC) dense_unit_w<E, VEC>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-    else if (a.dense_vec == VM) dense_unit_w<E, VM>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
-    else dense_unit_w<E, 1>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, wa.values, wa.rowptr);
+    if (a.dense_vec == VEC) dense_unit_w<E, VEC, W>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+    else if (a.dense_vec == VM) dense_unit_w<E, VM, W>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
+    else dense_unit_w<E, 1, W>(X, Z, U, masks, d.z, d.x, panel, a.N, a.D, a.ldx, a.ldz, lane, weights_of<E>(wa), wa.rowptr);
   }
 }
 
 // tiny_kernel (spmm_impl.h) with weights
+// (the 8-bit build holds values, scales and fp32 sums of 8 columns per lane: 6 waves per SIMD, nothing spilled; at 8 it spills 44 bytes)
+template <typename E> struct TinyWWaves { static constexpr int value = sizeof(typename E::T) == 1 ? 6 : HCSPMM_TINY_KERNEL_WAVES; };
 template <typename E, int L, int VEC>
-__global__ __launch_bounds__(kThreads, HCSPMM_TINY_KERNEL_WAVES) void tiny_w_kernel(WPlanArgs wa) {
+__global__ __launch_bounds__(kThreads, TinyWWaves<E>::value) void tiny_w_kernel(WPlanArgs wa) {
   const PlanArgs& a = wa.p;
   constexpr int R = 64 / L, T = HCSPMM_TINY_KERNEL_T;
   const int lane = threadIdx.x & 63;
@@ -487,9 +526,9 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_w_kernel(WWindowArgs w
   typedef Lane<E, VEC> Ln;
   typedef typename E::T elem_t;
   const WindowArgs& a = wa.w;
-  const float* __restrict__ vals = wa.values;
+  const typename WParam<decltype(weights_of<E>(wa))>::type vals = weights_of<E>(wa);
   const elem_t* X = reinterpret_cast<const elem_t*>(a.X);
-  elem_t* Z = reinterpret_cast<elem_t*>(a.Z);
+  typename E::Z* Z = reinterpret_cast<typename E::Z*>(a.Z);
   __shared__ int s_U[kChunkK];
   __shared__ unsigned int s_mask[kChunkK / 4 * 2];
   const int lane = threadIdx.x & 63;
@@ -504,7 +543,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_w_kernel(WWindowArgs w
     for (int rb = r0; rb < r1; rb += G) {
       const int r = rb + gi;
       int e0 = 0, n = 0;
-      elem_t* dst = nullptr;
+      typename E::Z* dst = nullptr;
       if (r < r1) {
         e0 = a.rowptr[r];
         n = a.rowptr[r + 1] - e0;
@@ -563,7 +602,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_w_kernel(WWindowArgs w
       for (int t0 = 0; t0 < steps; t0 += 4) {
         typename Ln::raw_t x[4];
         float av[4];
-        int ent[4];
+        int ent[4], ci[4];
         bool on[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -573,11 +612,12 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_w_kernel(WWindowArgs w
           const unsigned long long m =
               tv ? ((unsigned long long)s_mask[t * 2 + 1] << 32) | (unsigned long long)s_mask[t * 2] : 0ull;
           ent[u] = er.step(m, lane, &on[u]);
+          ci[u] = max(idx, 0);
           x[u] = Ln::zero();
           if (cok && idx >= 0) x[u] = Ln::load(X + (size_t)idx * a.ldx + c);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) av[u] = on[u] ? vals[ent[u]] : 0.0f;
+        for (int u = 0; u < 4; ++u) av[u] = on[u] ? entry_weight(vals + ent[u], ci[u]) : 0.0f;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
@@ -599,7 +639,7 @@ static hipError_t launch_plan_w_LV(const WPlanArgs& wa, hipStream_t stream) {
   WPlanArgs wb = wa;
   PlanArgs& b = wb.p;
   b.fused = 0;
-  const int n_col_panels = plan_launch_layout(b, L, VEC, DenseV<VEC>::mid, TinyT<L>::value, own_tiny_launch(b.n_tiny, 0), 0);
+  const int n_col_panels = plan_launch_layout(b, L, VEC, DenseV<VEC>::mid, TinyWT<E, L>::value, own_tiny_launch(b.n_tiny, 0), 0);
   constexpr int kMinWaves = sizeof(typename E::T) == 4 ? HCSPMM_MIN_WAVES_PER_SIMD : HCSPMM_MIN_WAVES_H16;
   const long long dense_wgs = ((long long)b.n_dense * b.n_panels + kWaves - 1) / kWaves;
   const long long grid = (long long)b.sparse_wgs + dense_wgs;

@@ -29,6 +29,7 @@ __all__ = [
     "gatv2_scores", "gatv2_scores_backward",
     "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward",
+    "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
 ]
@@ -158,6 +159,12 @@ def wide_threshold(row_nzr, embedding_dim, dtype=torch.float32):
     h = plan_header(row_nzr)
     return int(lib().hcspmm_wide_threshold_typed(ctypes.byref(h) if h is not None else None, int(embedding_dim),
                                                  _DTYPES[dtype]))
+
+
+def wide_threshold_fp8(row_nzr, embedding_dim):
+    """wide_threshold for forward_fp8 / forward_weighted_fp8 (hcspmm_wide_threshold_fp8, include/hcspmm.h)."""
+    h = plan_header(row_nzr)
+    return int(lib().hcspmm_wide_threshold_fp8(ctypes.byref(h) if h is not None else None, int(embedding_dim)))
 
 
 def workspace_bytes(row_nzr, embedding_dim):
@@ -504,6 +511,82 @@ def forward_weighted(X, values, row_pointers, column_index, blockPartition, edge
                                         ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
                                         _ptr(values if E else torch.zeros(1, device=X.device))))  # (NULL values: EINVAL)
     return [Z]
+
+
+_FP8_E4M3 = 0  # HCSPMM_FP8_E4M3
+
+
+def quantize_fp8(X, scale=None):
+    """Per-row quantiser -> (Xq, scale): Xq torch.float8_e4m3fn [rows, D], scale float32 [rows] with
+    Xq[r] = rne_e4m3(clamp(X[r] / scale[r], -448, 448)) and scale[r] = amax_r / 448 over the row's finite entries (1 for a row
+    without any, or all zeros).  A caller's `scale` (float32 [rows]) replaces the computed one.  D % 4 == 0
+    (hcspmm.h hcspmm_quantize_fp8)."""
+    _check_input(X, "input")
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise RuntimeError("input must be a 2-D float32 tensor")
+    rows, D = X.size(0), X.size(1)
+    if D == 0 or D % 4 != 0:
+        raise RuntimeError("the 8-bit kernels take embedding widths that are multiples of 4, got %d" % D)
+    if scale is not None:
+        _check_input(scale, "scale")
+        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != rows or scale.device != X.device:
+            raise RuntimeError("scale must hold one float32 per row of the input, on its device")
+    Xq = torch.empty((rows, D), dtype=torch.uint8, device=X.device)
+    out = torch.empty(rows, dtype=torch.float32, device=X.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(lib().hcspmm_quantize_fp8(_ptr(X), rows, D, D, _FP8_E4M3, _ptr(scale), _ptr(Xq), D, _ptr(out), stream))
+    return Xq.view(torch.float8_e4m3fn), out
+
+
+def _spmm_fp8(Xq, scale, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr):
+    L = lib()
+    for t, n in ((Xq, "input"), (row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
+                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
+        _check_input(t, n)
+    if Xq.dtype not in (torch.float8_e4m3fn, torch.uint8) or Xq.dim() != 2:
+        raise RuntimeError("input must be a 2-D float8_e4m3fn (or uint8) tensor")
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), Xq.size(1)
+    if Xq.size(0) != N:
+        raise RuntimeError("input has %d rows but the graph has %d nodes" % (Xq.size(0), N))
+    if D == 0 or D % 4 != 0:
+        raise RuntimeError("the 8-bit kernels take embedding widths that are multiples of 4, got %d" % D)
+    if scale is not None:
+        _check_input(scale, "scale")
+        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != Xq.size(0) or scale.device != Xq.device:
+            raise RuntimeError("scale must hold one float32 per row of the input, on its device")
+    if values is not None:
+        _check_values(values, E, Xq.device)
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, Xq.size(0))
+    Z = torch.empty((N, D), dtype=torch.float32, device=Xq.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=Xq.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(Xq.device).cuda_stream)
+    with _on_device(Xq.device):
+        check(L.hcspmm_forward_fp8(_ptr(Xq), Xq.size(0), D, _FP8_E4M3, _ptr(scale), _ptr(values), _ptr(Z), D, _ptr(row_pointers),
+                                   _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                   _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                   ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    return Z
+
+
+def forward_fp8(Xq, scale, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr):
+    """Aggregation of 8-bit features -> [A * (scale[:, None] * Xq)], float32: Xq float8_e4m3fn (or uint8 codes) [N, D] as
+    quantize_fp8 gives it, scale float32 [N] or None (= 1).  Codes are gathered as stored, widened exactly and accumulated in
+    fp32 (hcspmm.h hcspmm_forward_fp8)."""
+    return [_spmm_fp8(Xq, scale, None, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr)]
+
+
+def forward_weighted_fp8(Xq, scale, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                         row_nzr, col_nzr):
+    """forward_fp8 with edge values -> [A_w * (scale[:, None] * Xq)]: entry e of column c weighs values[e] * scale[c] (one fp32
+    multiplication), every step an fp32 fma in forward_weighted's order (hcspmm.h hcspmm_forward_fp8)."""
+    if values is None:
+        raise RuntimeError("values must be a CUDA tensor")
+    return [_spmm_fp8(Xq, scale, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr)]
 
 
 def _check_heads_width(D, heads, dtype):

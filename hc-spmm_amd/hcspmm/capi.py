@@ -64,6 +64,10 @@ SYMBOLS = {
     "hcspmm_wide_threshold": (ctypes.c_int32, [_hp, _int]),
     "hcspmm_wide_threshold_typed": (ctypes.c_int32, [_hp, _int, _int]),
     "hcspmm_own_tiny_launch": (ctypes.c_int32, [_hp, _int]),
+    "hcspmm_wide_threshold_fp8": (ctypes.c_int32, [_hp, _int]),
+    "hcspmm_quantize_fp8": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp, _i64, _vp, _vp]),
+    "hcspmm_forward_fp8": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
+                                  _int, _vp, _sz, _vp]),
     "hcspmm_forward_typed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp,
                                     _sz, _vp]),
     "hcspmm_forward_weighted": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,

@@ -150,7 +150,7 @@ int feature_dtype(const torch::Tensor& t) {
 Call prepare(const torch::Tensor& input, const torch::Tensor& nodePointer, const torch::Tensor& edgeList,
              const torch::Tensor& blockPartition, const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
              const torch::Tensor& row_nzr, bool allow_16bit = false, bool rect = false, bool strided = false,
-             const torch::Tensor* workspace = nullptr) {
+             const torch::Tensor* workspace = nullptr, bool fp8 = false) {
   if (strided) {
     CHECK_CUDA(input);
   } else {
@@ -161,8 +161,13 @@ Call prepare(const torch::Tensor& input, const torch::Tensor& nodePointer, const
   CHECK_INPUT(blockPartition);
   CHECK_INPUT(edgeToColumn);
   CHECK_INPUT(edgeToRow);
-  TORCH_CHECK(input.dim() == 2 && (allow_16bit ? feature_dtype(input) >= 0 : input.scalar_type() == torch::kFloat),
-              allow_16bit ? "input must be a 2-D float32 / float16 / bfloat16 tensor" : "input must be a 2-D float32 tensor");
+  if (fp8) {  // 8-bit codes (forward_fp8 / forward_weighted_fp8)
+    TORCH_CHECK(input.dim() == 2 && (input.scalar_type() == torch::kFloat8_e4m3fn || input.scalar_type() == torch::kByte),
+                "input must be a 2-D float8_e4m3fn (or uint8) tensor");
+  } else {
+    TORCH_CHECK(input.dim() == 2 && (allow_16bit ? feature_dtype(input) >= 0 : input.scalar_type() == torch::kFloat),
+                allow_16bit ? "input must be a 2-D float32 / float16 / bfloat16 tensor" : "input must be a 2-D float32 tensor");
+  }
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt,
               "nodePointer / edgeList must be int32");
   Call c;
@@ -227,6 +232,62 @@ std::vector<torch::Tensor> spmm_forward_weighted(torch::Tensor input, torch::Ten
       c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>());
   check_rc(rc, "forward_weighted");
   return {output};
+}
+
+// 8-bit feature storage (hcspmm_quantize_fp8 / hcspmm_forward_fp8): codes float8_e4m3fn (or uint8), one float32 scale per row
+void check_fp8_width(int64_t D) {
+  TORCH_CHECK(D > 0 && D % 4 == 0, "the 8-bit kernels take embedding widths that are multiples of 4, got ", D);
+}
+void check_row_scale(const torch::Tensor& scale, const torch::Tensor& input) {
+  CHECK_INPUT(scale);
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat && scale.dim() == 1 && scale.numel() == input.size(0) &&
+                  scale.device() == input.device(),
+              "scale must hold one float32 per row of the input, on its device");
+}
+
+std::vector<torch::Tensor> quantize_fp8(torch::Tensor input, c10::optional<torch::Tensor> scale) {
+  CHECK_INPUT(input);
+  TORCH_CHECK(input.dim() == 2 && input.scalar_type() == torch::kFloat, "input must be a 2-D float32 tensor");
+  const int64_t rows = input.size(0), D = input.size(1);
+  check_fp8_width(D);
+  if (scale.has_value()) check_row_scale(*scale, input);
+  auto codes = torch::empty({rows, D}, input.options().dtype(torch::kByte));
+  auto out = torch::empty({rows}, input.options());
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_quantize_fp8(rows > 0 ? input.data_ptr<float>() : nullptr, rows, D, (int)D, HCSPMM_FP8_E4M3,
+                                     scale.has_value() && rows > 0 ? scale->data_ptr<float>() : nullptr,
+                                     rows > 0 ? codes.data_ptr() : nullptr, D, rows > 0 ? out.data_ptr<float>() : nullptr,
+                                     (void*)c10::hip::getCurrentHIPStream(input.device().index()).stream());
+  check_rc(rc, "quantize_fp8");
+  return {codes.view(torch::kFloat8_e4m3fn), out};
+}
+
+// values: nullptr = the product without edge values (forward_fp8)
+torch::Tensor run_spmm_fp8(const torch::Tensor& input, const c10::optional<torch::Tensor>& scale, const torch::Tensor* values,
+                           const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
+                           const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow, const torch::Tensor& hybrid_type,
+                           const torch::Tensor& row_nzr) {
+  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, false, false, nullptr, true);
+  check_fp8_width(c.D);
+  if (scale.has_value()) check_row_scale(*scale, input);
+  if (values) {
+    CHECK_INPUT((*values));
+    TORCH_CHECK(values->scalar_type() == torch::kFloat, "values must be a float32 tensor");
+    TORCH_CHECK(values->dim() == 1 && values->numel() == c.E, "values must hold one float32 per stored entry: ", c.E, ", got ",
+                values->sizes());
+    TORCH_CHECK(values->device() == input.device(), "values must be on the device of the input");
+  }
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kFloat));
+  const c10::DeviceGuard guard(input.device());
+  const int rc = hcspmm_forward_fp8(
+      c.N > 0 ? input.data_ptr() : nullptr, input.size(0), c.D, HCSPMM_FP8_E4M3,
+      scale.has_value() && scale->numel() > 0 ? scale->data_ptr<float>() : nullptr,
+      values && values->numel() > 0 ? values->data_ptr<float>() : nullptr, c.N > 0 ? output.data_ptr<float>() : nullptr, c.D,
+      iptr(nodePointer), iptr(edgeList), iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type),
+      c.has_plan ? iptr(row_nzr) : nullptr, c.has_plan ? &c.header : nullptr, c.N, c.E, c.D,
+      c.workspace.defined() ? c.workspace.data_ptr() : nullptr, c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  check_rc(rc, "forward_fp8");
+  return output;
 }
 
 // multi-head limits of hcspmm_forward_weighted_heads / hcspmm_sddmm_heads
@@ -893,6 +954,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "form forward_*_fused takes with this plan and shape: 0 = two launches, 1 = dense-tile windows update inside the hybrid "
      "launch, 2 = the sparse-row path as well (row-tile form)");
   m.def("forward_weighted", &spmm_forward_weighted, "edge-weighted aggregation [A_w * X] (gfx950)");
+  m.def("quantize_fp8", &quantize_fp8,
+        "per-row quantiser: float32 [rows, D] -> (float8_e4m3fn codes [rows, D], float32 scale [rows]), code = rne(clamp(x / scale, "
+        "-448, 448)), scale = amax / 448 unless given (gfx950)",
+        pybind11::arg("input"), pybind11::arg("scale") = c10::optional<torch::Tensor>());
+  m.def("forward_fp8", [](torch::Tensor input, c10::optional<torch::Tensor> scale, torch::Tensor nodePointer, torch::Tensor edgeList,
+                          torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                          torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr) {
+    return std::vector<torch::Tensor>{run_spmm_fp8(input, scale, nullptr, nodePointer, edgeList, blockPartition, edgeToColumn,
+                                                   edgeToRow, hybrid_type, row_nzr)};
+  }, "aggregation of 8-bit features: float32 [A * (scale[:, None] * Xq)], scale float32 [N] or None (gfx950)");
+  m.def("forward_weighted_fp8", [](torch::Tensor input, c10::optional<torch::Tensor> scale, torch::Tensor values,
+                                   torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
+                                   torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
+                                   torch::Tensor row_nzr, torch::Tensor col_nzr) {
+    return std::vector<torch::Tensor>{run_spmm_fp8(input, scale, &values, nodePointer, edgeList, blockPartition, edgeToColumn,
+                                                   edgeToRow, hybrid_type, row_nzr)};
+  }, "edge-weighted aggregation of 8-bit features: float32 [A_w * (scale[:, None] * Xq)] (gfx950)");
+  m.def("wide_threshold_fp8", [](torch::Tensor row_nzr, int embedding_dim) {
+    hcspmm_plan_header h;
+    bool has = false;
+    if (row_nzr.defined() && row_nzr.numel() >= HCSPMM_PLAN_HEADER_WORDS && row_nzr.scalar_type() == torch::kInt) {
+      auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
+      std::memcpy(&h, host.data_ptr<int>(), sizeof(h));
+      has = h.magic == HCSPMM_PLAN_MAGIC;
+    }
+    return (int64_t)hcspmm_wide_threshold_fp8(has ? &h : nullptr, embedding_dim);
+  }, "wide_threshold for forward_fp8 / forward_weighted_fp8 (hcspmm.h hcspmm_wide_threshold_fp8)");
   m.def("edge_norm", [](torch::Tensor row_pointers, torch::Tensor column_index, std::string kind) {
     TORCH_CHECK(kind == "sym" || kind == "mean", "kind must be 'sym' or 'mean', got '", kind, "'");
     CHECK_INPUT(row_pointers);

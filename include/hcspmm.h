@@ -31,7 +31,8 @@ extern "C" {
  * hcspmm_transpose_permutation (round 5); hcspmm_sddmm, hcspmm_edge_softmax, hcspmm_edge_softmax_backward (round 6); hcspmm_gat_attention,
  * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8); hcspmm_extremum_workspace_bytes,
  * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9); hcspmm_gatv2_scores, hcspmm_gatv2_backward_workspace_bytes,
- * hcspmm_gatv2_scores_backward (round 10).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_gatv2_scores_backward (round 10); hcspmm_quantize_fp8, hcspmm_forward_fp8,
+ * hcspmm_wide_threshold_fp8 (round 13).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -319,6 +320,52 @@ int hcspmm_forward_weighted(const void* X_d, int64_t x_rows, int64_t ldx, void* 
                             const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                             int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                             const float* values_d);
+
+/* ------------------------------------------------------------------------------------------
+ * 8-bit feature storage: node features kept as OCP e4m3fn codes with one fp32 scale per row, a quarter of the fp32 bytes
+ * (a 128-column row is ONE 128-byte cache line), and the products that read them directly.
+ *
+ * Format.  `format` = HCSPMM_FP8_E4M3 only: OCP e4m3fn -- bias 7, largest finite value 448, no infinities, NaN codes 0x7f /
+ * 0xff (torch.float8_e4m3fn; what gfx950's v_cvt_pk_f32_fp8 / v_cvt_pk_fp8_f32 convert).  Any other value is HCSPMM_EINVAL;
+ * e5m2 and the MI300 `fnuz` encodings are not served.
+ *
+ * Shapes.  embedding_dim % 4 == 0, the row strides of the code matrix % 4 == 0 (elements are bytes) and a 4-byte aligned
+ * code base: every row starts on a dword, the kernels read dword-aligned vectors and a lane whose columns would run past the
+ * row is moved back onto its last ones.  Anything else is HCSPMM_EINVAL before any device call.
+ *
+ * hcspmm_quantize_fp8: X_d fp32 [rows][ldx] (ldx >= embedding_dim) -> Xq_d codes [rows][ldq] (ldq >= embedding_dim), scale_out_d
+ * fp32 [rows].  For each row r:
+ *   amax = max |x| over the row's finite entries;
+ *   s[r] = amax / 448.0f (IEEE fp32 division); 1.0f when amax == 0 or the row has no finite entry; raised to 2^-126 when the
+ *          quotient is not a normal number;
+ *   code = rne_e4m3(clamp(x / s[r], -448, 448)) with an IEEE fp32 division: +-inf saturates to +-448, NaN gives the NaN code
+ *          (0x7f with x's sign bit).
+ * scale_in_d != NULL (fp32 [rows]) replaces the computed scales -- the clamp then does real work -- and is copied to
+ * scale_out_d, which may then be NULL.  rows == 0 returns HCSPMM_OK without a launch.
+ *
+ * hcspmm_forward_fp8: Z = A_w * (diag(row_scale) * widen(Xq)), Z fp32 [num_nodes][ldz]:
+ *   Z[i][:] = sum over e in row i of  w_e * widen(Xq[column_index[e]][:]),  w_e = values[e] * row_scale[column_index[e]]
+ * w_e is ONE fp32 multiplication, rounded once; every step is acc = fmaf(w_e, x, acc) in fp32; widening e4m3 -> fp32 is exact.
+ * On each sub-path the order is the one hcspmm_forward_weighted uses there: CSR order on ordinary and tiny tasks, ascending
+ * window columns on dense tiles (v_mfma_f32_16x16x4_f32 on widened operands), the same shuffle tree and fix-up order.  A NULL
+ * values_d or row_scale_d counts as 1; with both NULL the binary kernels' plain adds are used.  row_scale_d has x_rows entries.
+ * The launch layout (column panels -- a cache line is 128 columns --, wide threshold: hcspmm_wide_threshold_fp8) depends on
+ * the element size, so bit equality with hcspmm_forward_weighted on dequantised input is NOT promised in general; sums that
+ * are exact in fp32 in any order are, of course, the same bits.  The graph, plan and header arguments, their checks and error
+ * codes are hcspmm_forward_weighted's (with a plan or plan-free); the workspace is hcspmm_workspace_bytes (partials are fp32).
+ * ---------------------------------------------------------------------------------------- */
+#define HCSPMM_FP8_E4M3 0
+int hcspmm_quantize_fp8(const float* X_d, int64_t rows, int64_t ldx, int embedding_dim, int format,
+                        const float* scale_in_d /* nullable */, void* Xq_d, int64_t ldq, float* scale_out_d, void* stream);
+int hcspmm_forward_fp8(const void* Xq_d, int64_t x_rows, int64_t ldx, int format, const float* row_scale_d /* nullable */,
+                       const float* values_d /* nullable */, float* Z_d, int64_t ldz, const int32_t* row_pointers_d,
+                       const int32_t* column_index_d, const int32_t* blockPartition_d, const int32_t* edgeToColumn_d,
+                       const int32_t* edgeToRow_d, const int32_t* hybrid_type_d, const int32_t* plan_d,
+                       const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                       void* workspace_d, size_t workspace_bytes, void* stream);
+/* hcspmm_wide_threshold for the 8-bit launch (8 codes per lane from 32 columns up, else 4); INT32_MAX for a width off the
+ * 4-column grid */
+int32_t hcspmm_wide_threshold_fp8(const hcspmm_plan_header* header_h, int embedding_dim);
 
 /* Multi-head edge-weighted forward: hcspmm_forward_weighted for `heads` heads of Dh = embedding_dim / heads columns each,
  * in one launch.  values_d is head-major fp32 [heads][E] (head h's values are the slice [h * E, (h + 1) * E)):
