@@ -843,3 +843,91 @@ class SAGEConv(torch.nn.Module):
         else:
             agg = extremum_aggregate(X, graph, self.aggr, self.directed)
         return _Update.apply(X, self.weights_root) + _Update.apply(agg, self.weights_neigh)
+
+
+class EdgeMessageAggregate(torch.autograd.Function):
+    """Z[i] = sum over the entries e = (i, j) of m(X[j], F[e]) (HCSPMM.forward_edge_messages; op "mul" x * f, "add_relu"
+    relu(x + f), "copy" f) with gradients for X and F [E, D].  dF is HCSPMM.edge_messages_grad; dX is the same forward on A^T:
+    "mul" with dZ in the place of X, "add_relu" as the "copy" of dF, F read through the index.  tail = the eight graph tensors of
+    A, the eight of the graph the backward walks (A itself when the pattern is symmetric, else transposed_graph's) and the int32
+    index of its entries into A's (the transpose permutation, or entry_index_t)."""
+
+    @staticmethod
+    def forward(ctx, X, F, op, *tail):
+        X = None if X is None else X.contiguous()
+        F = F.contiguous()
+        ctx.op = op
+        ctx.save_for_backward(X, F, *tail)
+        return HCSPMM.forward_edge_messages(X, F, *tail[:N_GRAPH], op)[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, F, *tail = ctx.saved_tensors
+        graph, graph_b, index = tail[:N_GRAPH], tail[N_GRAPH:2 * N_GRAPH], tail[2 * N_GRAPH]
+        need_x, need_f = ctx.needs_input_grad[0] and ctx.op != "copy", ctx.needs_input_grad[1]
+        d_out = d_out.contiguous()
+        d_x = d_f = None
+        if ctx.op == "mul":
+            if need_f:
+                d_f = HCSPMM.edge_messages_grad(d_out, X, None, graph[0], graph[1], "mul")
+            if need_x:
+                d_x = HCSPMM.forward_edge_messages(d_out, F, *graph_b, "mul", index)[0]
+        elif need_x or need_f:  # one pass serves both: dX sums dF over A^T's rows
+            d_f = HCSPMM.edge_messages_grad(d_out, X, F, graph[0], graph[1], ctx.op)
+            if need_x:
+                d_x = HCSPMM.forward_edge_messages(None, d_f, *graph_b, "copy", index)[0]
+            if not need_f:
+                d_f = None
+        return (d_x, d_f, None) + (None,) * len(tail)
+
+
+def edge_message_aggregate(X, F, graph, op="add_relu", directed=False):
+    """Sum over each row's entries of a message of the neighbour's row and the entry's own feature vector, with autograd for
+    X [N, D] and F [E, D] (float32; F aligned with column_index): op "mul" X[j] * F[e] (continuous-filter convolutions),
+    "add_relu" relu(X[j] + F[e]) (GINE), "copy" F[e] (X may be None).  graph = the eight graph tensors, whose pattern must be
+    symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then runs on
+    transposed_graph(graph).  Rows without entries give 0."""
+    if op not in ("mul", "add_relu", "copy"):
+        raise ValueError("op must be 'mul', 'add_relu' or 'copy', got %r" % (op,))
+    if F.dim() != 2 or F.size(0) != graph[1].numel():
+        raise ValueError("F must hold one row per stored entry: [%d, D], got %s" % (graph[1].numel(), tuple(F.shape)))
+    if directed:
+        gt = transposed_graph(graph)
+        return EdgeMessageAggregate.apply(X, F, op, *graph, *gt)
+    perm32 = transpose_permutation_i32(graph[0], graph[1])
+    return EdgeMessageAggregate.apply(X, F, op, *graph, *graph, perm32)
+
+
+class GINEConv(torch.nn.Module):
+    """GIN with edge attributes (GINE):  out = ((1 + eps) X + sum_j relu(X_j + edge_attr W_e)) W, the sum one
+    edge_message_aggregate over the projected edge attributes, both products on _Update.  edge_attr is float32 [E, edge_dim],
+    aligned with column_index; W_e [edge_dim, input_dim]; eps is learnt with train_eps=True.  _Conv's call signature with
+    edge_attr in the place of edge_weight.  The pattern must be symmetric unless directed=True."""
+
+    def __init__(self, input_dim, output_dim, edge_dim, eps=0.0, train_eps=False, fixed=0, directed=False):
+        super().__init__()
+        self.fixed, self.directed = fixed, bool(directed)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self.weights_edge = torch.nn.Parameter(torch.empty(edge_dim, input_dim))
+        self.initial_eps = float(eps)
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.empty(()))
+        else:
+            self.register_buffer("eps", torch.empty(()))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for p in (self.weights, self.weights_edge):
+            stdv = 1.0 / math.sqrt(p.size(1))
+            p.data.uniform_(-stdv, stdv)
+        self.eps.data.fill_(self.initial_eps)
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_attr=None):
+        if edge_attr is None:
+            raise ValueError("GINEConv needs edge_attr [E, edge_dim]")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if not self.directed:
+            transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        agg = edge_message_aggregate(X, _Update.apply(edge_attr, self.weights_edge), graph, "add_relu", self.directed)
+        return _Update.apply((1.0 + self.eps) * X + agg, self.weights)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GCN / GIN / GAT / GATv2 / SAGE training driver and single-kernel profiler over the HCSPMM operators -- counterpart
+"""GCN / GIN / GINE / GAT / GATv2 / SAGE training driver and single-kernel profiler over the HCSPMM operators -- counterpart
 of the reference's HC-SpMM_main.py (same eight flags, HC-SpMM_main.py:18-27, same printed lines
 "Prep. (ms)" :54 and "=> SAG profiling avg (ms)" GNN_model.py:261, same model shape :66-110, same
 schedule: 9 untimed warm-up epochs then --epochs timed ones, Adam lr 0.01, nll_loss :114-158).
@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, SAGEConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, SAGEConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gat", "gatv2", "sage"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -68,7 +68,14 @@ def parse_args(argv=None):
     # addition: 8-bit feature storage in the aggregation (GNN_model.aggregate_fp8: e4m3 codes + one fp32 scale per row in the
     # forward, the exact fp32 backward); after training the model is evaluated once with each storage type
     p.add_argument("--fp8", action="store_true", help="aggregate 8-bit (e4m3) features in the forward (--model gcn / gin with --norm)")
+    # addition: --model gine (GNN_model.GINEConv: sum_j relu(x_j + e_ij W_e)); the datasets carry no edge attributes, so --edge-dim
+    # of them per stored entry are drawn once from a seeded generator
+    p.add_argument("--edge-dim", type=int, default=8, help="edge attributes per entry (--model gine; synthesised, seeded)")
     args = p.parse_args(argv)
+    if args.edge_dim < 1:
+        p.error("--edge-dim must be at least 1")
+    if args.model == "gine" and args.norm != "none":
+        p.error("--norm does not apply to --model gine: its messages carry the edge attributes")
     if args.fp8:
         if args.model not in ("gcn", "gin") or args.norm == "none":
             p.error("--fp8 needs --model gcn or gin and --norm sym or mean: the binary layer functions and the other models stay fp32")
@@ -117,10 +124,12 @@ class Net(nn.Module):
     """conv1 (first) -> ReLU -> dropout -> (num_layers - 2) x [hidden conv -> ReLU] -> conv2 (last)
     -> log_softmax   (reference HC-SpMM_main.py:66-110)."""
 
-    def __init__(self, conv_cls, dataset, graph, output, hidden, num_layers, edge_weight=None):
+    def __init__(self, conv_cls, dataset, graph, output, hidden, num_layers, edge_weight=None, edge_attr=None):
         super().__init__()
         self.dataset, self.graph, self.output = dataset, graph, output
         self.ew = {} if edge_weight is None else {"edge_weight": edge_weight}
+        if edge_attr is not None:
+            self.ew["edge_attr"] = edge_attr
         self.conv1 = conv_cls(dataset.num_features, hidden, 1)
         self.hidden_layers = nn.ModuleList(conv_cls(hidden, hidden, 0) for _ in range(num_layers - 2))
         self.conv2 = conv_cls(hidden, dataset.num_classes, 2)
@@ -208,7 +217,14 @@ def main(argv=None):
                 return _FirstColumns(GATv2Conv(input_dim, (output_dim + 3) // 4 * 4, fixed, heads=args.heads, directed=directed),
                                      output_dim)
             return GATv2Conv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
-    model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight).to(device)
+    edge_attr = None
+    if args.model == "gine":
+        gen = torch.Generator().manual_seed(0)
+        edge_attr = torch.rand(num_edges, args.edge_dim, generator=gen).to(device)
+
+        def conv_cls(input_dim, output_dim, fixed):
+            return GINEConv(input_dim, output_dim, args.edge_dim, fixed=fixed, directed=directed)
+    model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight, edge_attr).to(device)
     if args.fp8:
         set_feature_storage(model, "fp8")
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)

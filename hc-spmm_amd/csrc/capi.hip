@@ -545,6 +545,85 @@ extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg
                        ldarg, transpose_perm);
 }
 
+// Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
+// every call.
+extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64_t ldx, const float* F, int64_t f_rows, int64_t ldf,
+                                            const int32_t* f_index, int op, void* Z, int64_t ldz, const int32_t* rowptr,
+                                            const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
+                                            const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
+                                            const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
+                                            size_t workspace_bytes, void* stream_v) {
+  if (op != HCSPMM_EDGE_OP_MUL && op != HCSPMM_EDGE_OP_ADD_RELU && op != HCSPMM_EDGE_OP_COPY) return HCSPMM_EINVAL;
+  const bool reads_x = op != HCSPMM_EDGE_OP_COPY;
+  if (N < 0 || E < 0 || D <= 0 || f_rows < 0 || ldf < D || ldz < D || (reads_x && ldx < D)) return HCSPMM_EINVAL;
+  if (E > 0 && (!F || f_rows == 0 || (!f_index && f_rows < E))) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if ((reads_x && !X) || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || f_rows > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::EdgeMsgArgs a{};
+  if (plan_d && ph) {
+    const int rc = hcspmm_plan_check(ph, N, E, 0);
+    if (rc != HCSPMM_OK) return rc;
+    if (reads_x && x_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows X does not have
+    const size_t need = hcspmm_workspace_bytes(ph, D);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
+    fill_plan_args(a.p, plan_d, ph, N, D, HCSPMM_DTYPE_F32);
+    a.p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
+    a.segment_len = ph->segment_len;
+  } else {
+    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
+    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
+    a.p.N = (int)N;
+    a.p.D = D;
+  }
+  a.p.X = reads_x ? X : nullptr;
+  a.p.Z = Z;
+  a.p.ldx = (size_t)ldx;
+  a.p.ldz = (size_t)ldz;
+  a.p.col = col;
+  a.rowptr = rowptr;
+  a.op = op;
+  a.F = F;
+  a.ldf = (size_t)ldf;
+  a.findex = f_index;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldx, ldz, X, Z, nullptr);
+  const hipError_t e = hcspmm::launch_edge_messages_f32(a, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+// Gradient of the edge-feature messages with respect to F (edge_messages_grad.hip): column_index is trusted, as in the plan-free
+// hcspmm_sddmm.
+extern "C" int hcspmm_edge_messages_grad(const float* grad_Z, int64_t ldg, const float* X, int64_t x_rows, int64_t ldx, const float* F,
+                                         int64_t ldf, float* grad_F, int64_t ldgf, int op, const int32_t* rowptr, const int32_t* col,
+                                         int64_t N, int64_t E, int D, void* stream_v) {
+  if (op != HCSPMM_EDGE_OP_MUL && op != HCSPMM_EDGE_OP_ADD_RELU && op != HCSPMM_EDGE_OP_COPY) return HCSPMM_EINVAL;
+  const bool reads_x = op != HCSPMM_EDGE_OP_COPY, reads_f = op == HCSPMM_EDGE_OP_ADD_RELU;
+  if (N < 0 || E < 0 || D <= 0 || ldg < D || ldgf < D || (reads_x && (ldx < D || x_rows < 0)) || (reads_f && ldf < D))
+    return HCSPMM_EINVAL;
+  if (!rowptr || (E > 0 && (!grad_Z || !grad_F || !col || N == 0 || (reads_x && (!X || x_rows == 0)) || (reads_f && !F))))
+    return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::EdgeMsgGradArgs a{};
+  a.gZ = grad_Z;
+  a.X = X;
+  a.F = F;
+  a.gF = grad_F;
+  a.ldg = (size_t)ldg;
+  a.ldx = (size_t)ldx;
+  a.ldf = (size_t)ldf;
+  a.ldgf = (size_t)ldgf;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.N = (int)N;
+  a.D = D;
+  a.op = op;
+  a.E = (long long)E;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldg, ldgf, grad_Z, grad_F, nullptr);
+  const hipError_t e = hcspmm::launch_edge_messages_grad_f32(a, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int kind,
                                        float* values_out, void* stream_v) {
   if (N < 0 || E < 0 || (kind != HCSPMM_NORM_SYM && kind != HCSPMM_NORM_MEAN)) return HCSPMM_EINVAL;

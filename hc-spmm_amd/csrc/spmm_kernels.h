@@ -270,5 +270,32 @@ struct XArgs {
 hipError_t launch_extremum_f32(const XArgs& a, int vec, hipStream_t stream);
 hipError_t launch_extremum_backward_f32(const XArgs& a, int vec, hipStream_t stream);
 
+// Edge-feature messages (spmm_edge_messages.hip; include/hcspmm.h hcspmm_forward_edge_messages), fp32: Z[r] = sum over the entries
+// e of row r of m(X[col(e)], F[fi(e)]), fi(e) = findex ? findex[e] : e.  p as for launch_extremum_f32 (p.plan == nullptr: plan-free;
+// p.X may be null for the copy op); partial = fp32 sums of the split rows.
+struct EdgeMsgArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  int op;             // HCSPMM_EDGE_OP_*
+  const float* F;     // [f_rows][ldf]
+  size_t ldf;
+  const int* findex;  // [E], or nullptr for the direct form
+};
+hipError_t launch_edge_messages_f32(const EdgeMsgArgs& a, int vec, hipStream_t stream);
+// its gradient with respect to F (edge_messages_grad.hip, hcspmm_edge_messages_grad): gF[e] from gZ[row(e)], X[col(e)] and F[e]
+struct EdgeMsgGradArgs {
+  const float* gZ;  // [N][ldg]
+  const float* X;   // [x_rows][ldx] (copy: unused)
+  const float* F;   // [E][ldf] (add_relu only)
+  float* gF;        // [E][ldgf]
+  size_t ldg, ldx, ldf, ldgf;
+  const int* rowptr;  // [N + 1]
+  const int* col;     // [E]
+  int N, D, op;
+  long long E;
+};
+hipError_t launch_edge_messages_grad_f32(const EdgeMsgGradArgs& a, int vec, hipStream_t stream);
+
 
 }  // namespace hcspmm

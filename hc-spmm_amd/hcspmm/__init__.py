@@ -29,6 +29,7 @@ __all__ = [
     "gatv2_scores", "gatv2_scores_backward",
     "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward",
+    "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
@@ -753,6 +754,104 @@ def forward_extremum_backward(grad_Z, arg, perm, row_pointers, column_index, blo
                                                  ctypes.byref(h) if h is not None else None, N, E, D, _ptr(perm), _ptr(ws),
                                                  ws_bytes, stream))
     return grad_X
+
+
+EDGE_OPS = {"mul": 0, "add_relu": 1, "copy": 2}  # include/hcspmm.h HCSPMM_EDGE_OP_*
+
+
+def _edge_op(op):
+    if op not in EDGE_OPS:
+        raise ValueError("op must be one of %s, got %r" % (", ".join(repr(k) for k in EDGE_OPS), op))
+    return EDGE_OPS[op]
+
+
+def _check_f32_view(t, name):
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+        raise RuntimeError("%s must be a 2-D float32 view with unit inner stride" % name)
+
+
+def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                          op="add_relu", index=None):
+    """Edge-feature messages -> [Z]: Z[r] = sum over the entries e of row r of m(X[col(e)], F[fi(e)]), fi(e) = index[e] (int32
+    [E]) or e.  op: "mul" x * f, "add_relu" relu(x + f), "copy" f (X may be None).  X [rows, D] and F [f_rows, D] are float32
+    views with unit inner stride; F is read on every call.  Deterministic, no atomics (hcspmm.h hcspmm_forward_edge_messages).
+    The gradient with respect to X is this call on A^T's graph with index = entry_index_t (or, on a pattern-symmetric graph,
+    the int32 transpose permutation): "mul" with X := dZ, "add_relu" as "copy" of edge_messages_grad's result."""
+    L = lib()
+    code = _edge_op(op)
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
+                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
+        _check_input(t, n)
+    _check_f32_view(F, "F")
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), F.size(1)
+    if X is None and op != "copy":
+        raise RuntimeError("input may be None for op='copy' only")
+    if X is not None:
+        _check_f32_view(X, "input")
+        if X.size(1) != D or X.device != F.device:
+            raise RuntimeError("input and F must have the same width and device, got %s and %s" % (tuple(X.shape), tuple(F.shape)))
+    if index is not None:
+        _check_input(index, "index")
+        if index.dtype != torch.int32 or index.dim() != 1 or index.numel() != E or index.device != F.device:
+            raise RuntimeError("index must be an int32 [E] tensor with E = %d on the device of F, got %s %s"
+                               % (E, index.dtype, tuple(index.shape)))
+    elif F.size(0) < E:
+        raise RuntimeError("F has %d rows but the graph has %d entries" % (F.size(0), E))
+    if D == 0:
+        raise RuntimeError("F must have at least one column")
+    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0) if X is not None else 1 << 62)
+    Z = torch.empty((N, D), dtype=torch.float32, device=F.device)
+    ws, ws_bytes = None, 0
+    if h is not None:
+        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
+        if ws_bytes:
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=F.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(F.device).cuda_stream)
+    with _on_device(F.device):
+        check(L.hcspmm_forward_edge_messages(_ptr(X), X.size(0) if X is not None else 0, X.stride(0) if X is not None else D,
+                                             _ptr(F), F.size(0), F.stride(0), _ptr(index), code, _ptr(Z), D, _ptr(row_pointers),
+                                             _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
+                                             _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
+                                             ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    return [Z]
+
+
+def edge_messages_grad(dZ, X, F, row_pointers, column_index, op="add_relu"):
+    """Gradient of forward_edge_messages (direct form) with respect to F -> float32 [E, D]: "mul" dZ[row(e)] * X[col(e)],
+    "add_relu" dZ[row(e)] where X[col(e)] + F[e] > 0 and +0 elsewhere, "copy" dZ[row(e)] (X and F may be None).  Edge-parallel,
+    every element written once (hcspmm.h hcspmm_edge_messages_grad)."""
+    code = _edge_op(op)
+    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
+        _check_input(t, n)
+    _check_f32_view(dZ, "dZ")
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), dZ.size(1)
+    if dZ.size(0) != N:
+        raise RuntimeError("dZ has %d rows but the graph has %d nodes" % (dZ.size(0), N))
+    if op != "copy":
+        if X is None:
+            raise RuntimeError("input may be None for op='copy' only")
+        _check_f32_view(X, "input")
+        if X.size(1) != D or X.device != dZ.device:
+            raise RuntimeError("input must have the width and device of dZ")
+    if op == "add_relu":
+        if F is None:
+            raise RuntimeError("F is required for op='add_relu'")
+        _check_f32_view(F, "F")
+        if F.size(1) != D or F.size(0) < E or F.device != dZ.device:
+            raise RuntimeError("F must be [E, D] with E = %d, D = %d on the device of dZ, got %s" % (E, D, tuple(F.shape)))
+    reads_x, reads_f = op != "copy", op == "add_relu"
+    out = torch.empty((E, D), dtype=torch.float32, device=dZ.device)
+    if D == 0:
+        return out
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dZ.device).cuda_stream)
+    with _on_device(dZ.device):
+        check(lib().hcspmm_edge_messages_grad(_ptr(dZ), dZ.stride(0), _ptr(X) if reads_x else ctypes.c_void_p(0),
+                                              X.size(0) if reads_x else 0, X.stride(0) if reads_x else D,
+                                              _ptr(F) if reads_f else ctypes.c_void_p(0), F.stride(0) if reads_f else D, _ptr(out), D,
+                                              code, _ptr(row_pointers), _ptr(column_index), N, E, D, stream))
+    return out
 
 
 _NORMS = {"sym": 0, "mean": 1}

@@ -411,6 +411,104 @@ torch::Tensor spmm_forward_extremum_backward(torch::Tensor grad_Z, torch::Tensor
   return grad_X;
 }
 
+// Edge-feature messages (hcspmm_forward_edge_messages / hcspmm_edge_messages_grad): float32 views with unit inner stride
+int edge_op_code(const std::string& op) {
+  if (op == "mul") return HCSPMM_EDGE_OP_MUL;
+  if (op == "add_relu") return HCSPMM_EDGE_OP_ADD_RELU;
+  TORCH_CHECK(op == "copy", "op must be one of 'mul', 'add_relu', 'copy', got '", op, "'");
+  return HCSPMM_EDGE_OP_COPY;
+}
+void check_f32_view(const torch::Tensor& t, const char* name) {
+  CHECK_CUDA(t);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1), name,
+              " must be a 2-D float32 view with unit inner stride");
+}
+
+std::vector<torch::Tensor> spmm_forward_edge_messages(c10::optional<torch::Tensor> input, torch::Tensor F, torch::Tensor nodePointer,
+                                                      torch::Tensor edgeList, torch::Tensor blockPartition,
+                                                      torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
+                                                      torch::Tensor row_nzr, torch::Tensor col_nzr, const std::string& op,
+                                                      c10::optional<torch::Tensor> index) {
+  const int code = edge_op_code(op);
+  check_f32_view(F, "F");
+  TORCH_CHECK(input.has_value() || code == HCSPMM_EDGE_OP_COPY, "input may be None for op='copy' only");
+  TORCH_CHECK(F.size(1) > 0, "F must have at least one column");
+  Call c;
+  if (input.has_value()) {
+    check_f32_view(*input, "input");
+    TORCH_CHECK(input->size(1) == F.size(1) && input->device() == F.device(), "input and F must have the same width and device, got ",
+                input->sizes(), " and ", F.sizes());
+    c = prepare(*input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, true, true);
+  } else {  // no rows are gathered: the plan is checked against the graph alone
+    CHECK_INPUT(nodePointer);
+    CHECK_INPUT(edgeList);
+    CHECK_INPUT(blockPartition);
+    CHECK_INPUT(edgeToColumn);
+    CHECK_INPUT(edgeToRow);
+    TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt,
+                "nodePointer / edgeList must be int32");
+    c.N = nodePointer.size(0) - 1;
+    c.E = edgeList.size(0);
+    c.D = (int)F.size(1);
+    c.has_plan = lookup(row_nzr, nodePointer, edgeList, c.N, c.E, &c.header);
+    const size_t need = c.has_plan ? hcspmm_workspace_bytes(&c.header, c.D) : 0;
+    if (need) c.workspace = torch::empty({(int64_t)(need / 4)}, F.options());
+    c.stream = (void*)c10::hip::getCurrentHIPStream(F.device().index()).stream();
+  }
+  if (index.has_value()) {
+    CHECK_INPUT((*index));
+    TORCH_CHECK(index->scalar_type() == torch::kInt && index->dim() == 1 && index->numel() == c.E && index->device() == F.device(),
+                "index must be an int32 [E] tensor with E = ", c.E, " on the device of F, got ", index->scalar_type(), " ",
+                index->sizes());
+  } else {
+    TORCH_CHECK(F.size(0) >= c.E, "F has ", F.size(0), " rows but the graph has ", c.E, " entries");
+  }
+  auto output = torch::empty({c.N, (int64_t)c.D}, F.options());
+  const c10::DeviceGuard guard(F.device());
+  const int rc = hcspmm_forward_edge_messages(
+      input.has_value() && input->numel() > 0 ? input->data_ptr() : nullptr, input.has_value() ? input->size(0) : 0,
+      input.has_value() ? input->stride(0) : c.D, F.numel() > 0 ? F.data_ptr<float>() : nullptr, F.size(0), F.stride(0),
+      index.has_value() ? iptr(*index) : nullptr, code, c.N > 0 ? output.data_ptr() : nullptr, c.D, iptr(nodePointer), iptr(edgeList),
+      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
+      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
+      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  check_rc(rc, "forward_edge_messages");
+  return {output};
+}
+
+torch::Tensor spmm_edge_messages_grad(torch::Tensor dZ, c10::optional<torch::Tensor> input, c10::optional<torch::Tensor> F,
+                                      torch::Tensor nodePointer, torch::Tensor edgeList, const std::string& op) {
+  const int code = edge_op_code(op);
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  check_f32_view(dZ, "dZ");
+  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0), D = dZ.size(1);
+  TORCH_CHECK(dZ.size(0) == N, "dZ has ", dZ.size(0), " rows but the graph has ", N, " nodes");
+  const bool reads_x = code != HCSPMM_EDGE_OP_COPY, reads_f = code == HCSPMM_EDGE_OP_ADD_RELU;
+  if (reads_x) {
+    TORCH_CHECK(input.has_value(), "input may be None for op='copy' only");
+    check_f32_view(*input, "input");
+    TORCH_CHECK(input->size(1) == D && input->device() == dZ.device(), "input must have the width and device of dZ");
+  }
+  if (reads_f) {
+    TORCH_CHECK(F.has_value(), "F is required for op='add_relu'");
+    check_f32_view(*F, "F");
+    TORCH_CHECK(F->size(1) == D && F->size(0) >= E && F->device() == dZ.device(), "F must be [E, D] with E = ", E, ", D = ", D,
+                " on the device of dZ, got ", F->sizes());
+  }
+  auto out = torch::empty({E, D}, dZ.options());
+  if (D == 0) return out;
+  const c10::DeviceGuard guard(dZ.device());
+  const int rc = hcspmm_edge_messages_grad(
+      dZ.numel() > 0 ? dZ.data_ptr<float>() : nullptr, dZ.stride(0), reads_x && input->numel() > 0 ? input->data_ptr<float>() : nullptr,
+      reads_x ? input->size(0) : 0, reads_x ? input->stride(0) : D, reads_f && F->numel() > 0 ? F->data_ptr<float>() : nullptr,
+      reads_f ? F->stride(0) : D, E > 0 ? out.data_ptr<float>() : nullptr, D, code, iptr(nodePointer), iptr(edgeList), N, E, (int)D,
+      (void*)c10::hip::getCurrentHIPStream(dZ.device().index()).stream());
+  check_rc(rc, "edge_messages_grad");
+  return out;
+}
+
 // Multi-head SDDMM (hcspmm_sddmm_heads): float32 [heads, E], out[h][e] = <A[row(e)][h-th Dh slice], B[col(e)][same slice]>
 torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
                                torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
@@ -1074,6 +1172,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
         "backward of forward_max / forward_min -> grad_X: a square, pattern-symmetric graph with perm = int32 transpose_permutation, "
         "or any square graph's A^T (transpose_graph's tensors and their preprocessing) with perm = entry_index_t (gfx950)");
+  m.def("forward_edge_messages", &spmm_forward_edge_messages,
+        "edge-feature messages [Z]: Z[r] = sum over the entries e of row r of m(X[col(e)], F[index[e] or e]); op 'mul' x * f, "
+        "'add_relu' relu(x + f), 'copy' f (input may be None) (gfx950)",
+        pybind11::arg("input"), pybind11::arg("F"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("op") = "add_relu", pybind11::arg("index") = pybind11::none());
+  m.def("edge_messages_grad", &spmm_edge_messages_grad,
+        "gradient of forward_edge_messages with respect to F: float32 [E, D] (input / F may be None where the op does not read them) "
+        "(gfx950)",
+        pybind11::arg("dZ"), pybind11::arg("input"), pybind11::arg("F"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("op") = "add_relu");
   m.def("sddmm", &spmm_sddmm, "sampled dense-dense product on the stored entries: float32 [E], out[e] = <A[row(e)], B[col(e)]> (gfx950)");
   m.def("edge_softmax", &edge_softmax, "softmax of float32 [E] / [heads, E] logits over each row's stored entries (gfx950)");
   m.def("edge_softmax_backward", &edge_softmax_backward,

@@ -32,7 +32,7 @@ extern "C" {
  * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8); hcspmm_extremum_workspace_bytes,
  * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9); hcspmm_gatv2_scores, hcspmm_gatv2_backward_workspace_bytes,
  * hcspmm_gatv2_scores_backward (round 10); hcspmm_quantize_fp8, hcspmm_forward_fp8,
- * hcspmm_wide_threshold_fp8 (round 13).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -454,6 +454,61 @@ int hcspmm_forward_extremum_backward(const float* grad_Z_d, int64_t ldg, const i
                                      const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                                      int64_t num_edges, int embedding_dim, const int32_t* transpose_perm_d, void* workspace_d,
                                      size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Edge-feature messages (GINE, SchNet / CFConv continuous filters, edge-gated convolutions, "sum the incident edge vectors"):
+ * a neighbour's row combined with a feature VECTOR of the edge, one value per column instead of one per entry or head:
+ *   Z[r][d] = sum over e in [row_pointers[r], row_pointers[r+1])  m(X[column_index[e]][d], F[fi(e)][d])
+ *   fi(e)   = f_index[e] if f_index_d != NULL else e
+ *   HCSPMM_EDGE_OP_MUL      : acc = fmaf(f, x, acc)
+ *   HCSPMM_EDGE_OP_ADD_RELU : t = x + f (one fp32 add); m = (t < 0) ? +0 : t (a NaN propagates); acc = acc + m
+ *   HCSPMM_EDGE_OP_COPY     : acc = acc + f                       (X_d is ignored and may be NULL)
+ * fp32.  It runs on the binary product's preprocessing and plan, or plan-free, with hcspmm_forward_weighted's fp32 schedule
+ * at the same width (ordinary, wide, column-sliced, segmented and tiny tasks; hcspmm_wide_threshold).  A matrix core takes no
+ * per-column value: dense-tile windows are served from CSR by the sparse-row gather, as in hcspmm_forward_extremum.  Each
+ * (r, d) is summed in CSR order on ordinary and tiny tasks and on the rows of dense-tile windows, by the wide tasks' shuffle
+ * tree on wide tasks, and through fp32 partials in the workspace (hcspmm_workspace_bytes) and a fix-up pass in fixed order
+ * for sliced and segmented rows.  No atomics: two calls give the same bits.  Rows without entries get +0.0.
+ *   X_d      fp32 [x_rows][ldx], indexed by column ids (x_rows may differ from num_nodes: a rectangular block)
+ *   F_d      fp32 [f_rows][ldf], ldf >= embedding_dim; read on every call.  F, Z and the partials are addressed in 64 bits
+ *            (num_edges * ldf may pass 2^31)
+ *   f_index_d  int32 [num_edges] or NULL; every index must lie in [0, f_rows) and is trusted on the device, as value_index is
+ *            in hcspmm_forward_weighted_indexed (many-to-one indices and f_rows != num_edges are fine).  Without an index
+ *            f_rows >= num_edges
+ *   Z_d      fp32 [num_nodes][ldz]
+ * Every embedding_dim hcspmm_forward_extremum serves (1, 3, 22, ... through the element-aligned 16-byte lanes, for X and F
+ * alike).  A bad op, NULL F_d with num_edges > 0, NULL X_d for MUL / ADD_RELU, short strides, f_rows < num_edges without an
+ * index, f_rows == 0 with num_edges > 0 and the argument errors of hcspmm_forward_weighted are HCSPMM_EINVAL before any
+ * device call.  Separate kernels (spmm_edge_messages.hip).  Asynchronous on `stream`.
+ * The gradient with respect to X needs no kernel of its own: it is this forward on A^T's graph and plan
+ * (hcspmm_transpose_graph) with f_index = entry_index_t -- or, on a pattern-symmetric graph, on the same graph with f_index =
+ * hcspmm_transpose_permutation's perm:
+ *   MUL      : dX = forward(op = MUL, X := grad_Z, F, f_index)
+ *   ADD_RELU : dX = forward(op = COPY, F := grad_F, f_index)       (grad_F from hcspmm_edge_messages_grad)
+ * ---------------------------------------------------------------------------------------- */
+#define HCSPMM_EDGE_OP_MUL 0
+#define HCSPMM_EDGE_OP_ADD_RELU 1
+#define HCSPMM_EDGE_OP_COPY 2
+int hcspmm_forward_edge_messages(const void* X_d, int64_t x_rows, int64_t ldx, const float* F_d, int64_t f_rows, int64_t ldf,
+                                 const int32_t* f_index_d /* [E] or NULL */, int op, void* Z_d, int64_t ldz,
+                                 const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                                 const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                                 const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                                 int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* Gradient of hcspmm_forward_edge_messages with respect to F (direct form, F [num_edges][ldf]), fp32:
+ *   MUL      : grad_F[e][d] = grad_Z[row(e)][d] * X[column_index[e]][d]                      (one fp32 multiplication)
+ *   ADD_RELU : grad_F[e][d] = (X[column_index[e]][d] + F[e][d] > 0) ? grad_Z[row(e)][d] : +0  (the forward's own fp32 add)
+ *   COPY     : grad_F[e][d] = grad_Z[row(e)][d]                                              (X_d and F_d may be NULL)
+ * Edge-parallel over contiguous CSR chunks like hcspmm_sddmm (a row cursor, no search per entry), so a hub row is cut wherever
+ * the chunks fall; every element of grad_F_out_d [num_edges][ldgf] is written exactly once; no atomics.  grad_Z_d is
+ * [num_nodes][ldg], X_d [x_rows][ldx] (column ids are trusted), F_d [num_edges][ldf] (read by ADD_RELU only); all addressing
+ * of F and grad_F is 64-bit.  A bad op, NULL pointers an op reads (num_edges > 0), short strides and negative sizes are
+ * HCSPMM_EINVAL before any device call; num_edges = 0 launches nothing.  Asynchronous on `stream`. */
+int hcspmm_edge_messages_grad(const float* grad_Z_d, int64_t ldg, const float* X_d, int64_t x_rows, int64_t ldx, const float* F_d,
+                              int64_t ldf, float* grad_F_out_d, int64_t ldgf, int op, const int32_t* row_pointers_d,
+                              const int32_t* column_index_d, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                              void* stream);
 
 /* Edge normalisations of a square graph, on the device (asynchronous on `stream`); deg(r) = stored entries of row r, so
  * self-loops count only when the graph stores them.  Rows of degree 0 own no entries.
