@@ -224,64 +224,107 @@ struct FusedOperands {
   int mode;  // bit 0: dense-tile windows update inside the hybrid launch; bit 1: ordinary / tiny sparse rows in the row-tile launch
 };
 
-// the plan fields of a hybrid launch, from the host copy of the plan's header (the launcher-owned fields stay zero:
-// plan_layout.h fills them); dtype: the element type wide_choice decides for
-void fill_plan_args(hcspmm::PlanArgs& a, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int D, int dtype) {
-  a = hcspmm::PlanArgs{};
-  a.plan = plan_d;
-  a.off_tasks = ph->off_tasks;
-  a.n_tasks = ph->n_tasks;
-  a.n_tiny = ph->n_tiny;
-  a.off_slice_table = ph->off_slice_table;
-  a.off_slice_tasks = ph->off_slice_tasks;
-  a.n_slices = ph->n_slices;
-  a.slice_xcd_tasks = ph->slice_xcd_tasks;
-  a.off_dense_index = ph->off_dense_index;
-  a.off_dense_pack = ph->off_dense_pack;
-  a.n_dense = ph->n_dense;
-  a.off_dense_compact = ph->off_dense_compact;
-  a.n_dense_compact = ph->n_dense_compact;
-  a.off_dense_compact2 = ph->off_dense_compact2;
-  a.n_dense_compact2 = ph->n_dense_compact2;
-  a.off_fixups = ph->off_fixups;
-  a.n_split_rows = ph->n_split_rows;
-  wide_choice(ph, D, dtype, &a.n_wide, &a.panel_cols);
-  a.N = (int)N;
-  a.D = D;
+// the graph arguments every planned-or-plan-free entry point receives
+struct GraphIn {
+  const int32_t *rowptr, *col, *blockPartition, *edgeToColumn, *edgeToRow, *hybrid_type, *plan_d;
+  const hcspmm_plan_header* ph;
+  int64_t N, E;
+};
+
+// an entry point's graph parameters (every one names them alike)
+#define GRAPH_IN GraphIn{rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d, ph, N, E}
+
+constexpr int64_t kNoSource = INT64_MAX;  // bind_graph's src_rows of a launch that gathers no rows (the copy op)
+
+// The one "plan or plan-free" binding, after the entry point's own size / null / range checks.
+// Planned (plan_d and ph): hcspmm_plan_check, then src_rows against the rows the plan gathers (EINVAL), then the workspace against
+// ws_mult partial-sum areas (EWORKSPACE); p gets the plan fields from the host copy of the header, the n_wide / panel_cols that
+// wide_choice decides for element type `dtype`, partial (null when the plan has no split rows), col and N / D.  The launcher-owned
+// fields stay zero: plan_layout.h fills them.
+// Plan-free: one of plan_d / ph alone, or a missing window array, is EINVAL; p gets col and N / D, and p.plan stays null.
+int bind_graph(hcspmm::PlanArgs& p, const GraphIn& g, int D, int64_t src_rows, void* workspace, size_t workspace_bytes, int ws_mult,
+               int dtype) {
+  p = hcspmm::PlanArgs{};
+  p.col = g.col;
+  p.N = (int)g.N;
+  p.D = D;
+  const hcspmm_plan_header* ph = g.ph;
+  if (!(g.plan_d && ph)) {
+    if (g.plan_d || ph) return HCSPMM_EINVAL;  // both or neither
+    if (!g.blockPartition || !g.hybrid_type || (g.E > 0 && (!g.edgeToColumn || !g.edgeToRow))) return HCSPMM_EINVAL;
+    return HCSPMM_OK;
+  }
+  const int rc = hcspmm_plan_check(ph, g.N, g.E, 0);
+  if (rc != HCSPMM_OK) return rc;
+  if (src_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows the source does not have
+  const size_t need = (size_t)ws_mult * hcspmm_workspace_bytes(ph, D);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
+  p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
+  p.plan = g.plan_d;
+  p.off_tasks = ph->off_tasks;
+  p.n_tasks = ph->n_tasks;
+  p.n_tiny = ph->n_tiny;
+  p.off_slice_table = ph->off_slice_table;
+  p.off_slice_tasks = ph->off_slice_tasks;
+  p.n_slices = ph->n_slices;
+  p.slice_xcd_tasks = ph->slice_xcd_tasks;
+  p.off_dense_index = ph->off_dense_index;
+  p.off_dense_pack = ph->off_dense_pack;
+  p.n_dense = ph->n_dense;
+  p.off_dense_compact = ph->off_dense_compact;
+  p.n_dense_compact = ph->n_dense_compact;
+  p.off_dense_compact2 = ph->off_dense_compact2;
+  p.n_dense_compact2 = ph->n_dense_compact2;
+  p.off_fixups = ph->off_fixups;
+  p.n_split_rows = ph->n_split_rows;
+  wide_choice(ph, D, dtype, &p.n_wide, &p.panel_cols);
+  return HCSPMM_OK;
 }
 
-int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype, const int32_t* rowptr,
-                 const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
-                 const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
-                 const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
-                 size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr,
+inline void set_operands(hcspmm::PlanArgs& p, const void* X, void* Z, int64_t ldx, int64_t ldz) {
+  p.X = X;
+  p.Z = Z;
+  p.ldx = (size_t)ldx;
+  p.ldz = (size_t)ldz;
+}
+
+// the plan-free launch's arguments, from a PlanArgs that bind_graph left plan-free and set_operands filled
+inline hcspmm::WindowArgs window_args(const GraphIn& g, const hcspmm::PlanArgs& p) {
+  return hcspmm::WindowArgs{p.X, p.Z, g.rowptr, g.col, g.blockPartition, g.edgeToColumn, g.edgeToRow, g.hybrid_type, p.ldx, p.ldz,
+                            p.N, p.D};
+}
+
+// one launcher family's builds for the three typed element types
+template <class A>
+using Launcher = hipError_t (*)(const A&, int, hipStream_t);
+template <class A>
+hipError_t launch_typed(int dtype, Launcher<A> f32, Launcher<A> f16, Launcher<A> bf16, const A& a, int vec, hipStream_t stream) {
+  return (dtype == HCSPMM_DTYPE_F32 ? f32 : dtype == HCSPMM_DTYPE_F16 ? f16 : bf16)(a, vec, stream);
+}
+
+int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype, const GraphIn& g, int D,
+                 void* workspace, size_t workspace_bytes, void* stream_v, const FusedOperands* fused, const float* values = nullptr,
                  int heads = 0, const int32_t* vindex = nullptr, int64_t num_values = 0) {
+  using namespace hcspmm;
   if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
-  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
+  if (g.N < 0 || g.E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
   // heads > 0: the multi-head weighted product (fp32, Dh = D / heads columns per head, Dh % 4 == 0)
   // vindex: the indexed form (entry e weighs values[h * num_values + vindex[e]]); one head then takes any D
   if (heads > 0 && (dtype != HCSPMM_DTYPE_F32 || !values || fused || D % heads != 0 ||
                     ((D / heads) % 4 != 0 && !(vindex && heads == 1))))
     return HCSPMM_EINVAL;
-  if (N == 0) return HCSPMM_OK;
-  if (!X || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
-  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if (g.N == 0) return HCSPMM_OK;
+  if (!X || !Z || !g.rowptr || (g.E > 0 && !g.col)) return HCSPMM_EINVAL;
+  if (g.N > INT32_MAX - 16 || g.E > INT32_MAX) return HCSPMM_ERANGE;
+  if (fused && !(g.plan_d && g.ph)) return HCSPMM_EINVAL;  // the fused forms are planned launches
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+  PlanArgs a;
+  const int rc = bind_graph(a, g, D, x_rows, workspace, workspace_bytes, 1, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  set_operands(a, X, Z, ldx, ldz);
+  const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, a.partial);
   hipError_t e;
-  if (plan_d && ph) {
-    const int rc = hcspmm_plan_check(ph, N, E, 0);
-    if (rc != HCSPMM_OK) return rc;
-    if (x_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows X does not have
-    const size_t need = hcspmm_workspace_bytes(ph, D);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
-    hcspmm::PlanArgs a;
-    fill_plan_args(a, plan_d, ph, N, D, dtype);
-    a.X = X;
-    a.Z = Z;
-    a.ldx = (size_t)ldx;
-    a.ldz = (size_t)ldz;
-    a.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
-    a.col = col;
+  if (a.plan) {
     if (fused) {
       a.fused = fused->mode;
       a.H = fused->H;
@@ -290,57 +333,32 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
       a.w_ldc = fused->ldc;
       a.out = fused->out;
     }
-    const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, need ? workspace : nullptr);
     if (fused && (vec != 4 || dtype != HCSPMM_DTYPE_F32)) return HCSPMM_EINVAL;  // (fused_form said otherwise)
     if (fused && (fused->mode & 2)) {
       // row-tile form: the ordinary / tiny tasks and the dense windows are summed AND multiplied by the tile launches
       // (fused_rows.hip); the hybrid launch below then runs the sliced and wide tasks only and ends with the fix-up pass,
       // which also adds the segments of split rows that sit among the ordinary tasks
-      e = hcspmm::launch_fused_tiles(a, stream);
+      e = launch_fused_tiles(a, stream);
       if (e != hipSuccess) return fail_hip(e);
     }
     if (values) {
       if (fused) return HCSPMM_EINVAL;
-      const hcspmm::WPlanArgs wa{a, values, rowptr, ph->segment_len};
-      if (vindex) e = hcspmm::launch_plan_wi_f32(hcspmm::WHPlanArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
-      else if (heads > 0) e = hcspmm::launch_plan_wh_f32(hcspmm::WHPlanArgs{wa, (long long)E, D / heads, nullptr}, vec, stream);
-      else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_w_f32(wa, vec, stream)
-          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_w_f16(wa, vec, stream)
-                                      : hcspmm::launch_plan_w_bf16(wa, vec, stream);
+      const WPlanArgs wa{a, values, g.rowptr, g.ph->segment_len};
+      if (vindex) e = launch_plan_wi_f32(WHPlanArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
+      else if (heads > 0) e = launch_plan_wh_f32(WHPlanArgs{wa, (long long)g.E, D / heads, nullptr}, vec, stream);
+      else e = launch_typed(dtype, launch_plan_w_f32, launch_plan_w_f16, launch_plan_w_bf16, wa, vec, stream);
     } else {
-      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_plan_f32(a, vec, stream)
-          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_plan_f16(a, vec, stream)
-                                      : hcspmm::launch_plan_bf16(a, vec, stream);
+      e = launch_typed(dtype, launch_plan_f32, launch_plan_f16, launch_plan_bf16, a, vec, stream);
     }
   } else {
-    if (fused) return HCSPMM_EINVAL;
-    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
-    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
-    hcspmm::WindowArgs a;
-    a.X = X;
-    a.Z = Z;
-    a.ldx = (size_t)ldx;
-    a.ldz = (size_t)ldz;
-    a.rowptr = rowptr;
-    a.col = col;
-    a.blockPartition = blockPartition;
-    a.edgeToColumn = edgeToColumn;
-    a.edgeToRow = edgeToRow;
-    a.hybrid_type = hybrid_type;
-    a.N = (int)N;
-    a.D = D;
-    const int vec = pick_vec(dtype, D, ldx, ldz, X, Z, nullptr);
+    const WindowArgs w = window_args(g, a);
     if (values) {
-      const hcspmm::WWindowArgs wa{a, values};
-      if (vindex) e = hcspmm::launch_window_wi_f32(hcspmm::WHWindowArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
-      else if (heads > 0) e = hcspmm::launch_window_wh_f32(hcspmm::WHWindowArgs{wa, (long long)E, D / heads, nullptr}, vec, stream);
-      else e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_w_f32(wa, vec, stream)
-          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_w_f16(wa, vec, stream)
-                                      : hcspmm::launch_window_w_bf16(wa, vec, stream);
+      const WWindowArgs wa{w, values};
+      if (vindex) e = launch_window_wi_f32(WHWindowArgs{wa, (long long)num_values, D / heads, vindex}, vec, stream);
+      else if (heads > 0) e = launch_window_wh_f32(WHWindowArgs{wa, (long long)g.E, D / heads, nullptr}, vec, stream);
+      else e = launch_typed(dtype, launch_window_w_f32, launch_window_w_f16, launch_window_w_bf16, wa, vec, stream);
     } else {
-      e = dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_window_f32(a, vec, stream)
-          : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_window_f16(a, vec, stream)
-                                      : hcspmm::launch_window_bf16(a, vec, stream);
+      e = launch_typed(dtype, launch_window_f32, launch_window_f16, launch_window_bf16, w, vec, stream);
     }
   }
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
@@ -352,8 +370,7 @@ extern "C" int hcspmm_forward_typed(const void* X, int64_t x_rows, int64_t ldx, 
                                     const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
                                     const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
                                     size_t workspace_bytes, void* stream_v) {
-  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                      plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr);
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, GRAPH_IN, D, workspace, workspace_bytes, stream_v, nullptr);
 }
 
 // Edge-weighted product (spmm_weighted*.hip): the plan and launch decisions of hcspmm_forward_typed, values read on every call.
@@ -363,8 +380,7 @@ extern "C" int hcspmm_forward_weighted(const void* X, int64_t x_rows, int64_t ld
                                        const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
                                        void* workspace, size_t workspace_bytes, void* stream_v, const float* values) {
   if (!values) return HCSPMM_EINVAL;  // never a silent binary product
-  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                      plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values);
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, GRAPH_IN, D, workspace, workspace_bytes, stream_v, nullptr, values);
 }
 
 // Multi-head edge-weighted product (spmm_weighted_heads.hip): hcspmm_forward_weighted's checks and launch decisions, values
@@ -377,8 +393,7 @@ extern "C" int hcspmm_forward_weighted_heads(const void* X, int64_t x_rows, int6
                                              int heads) {
   if (!values || heads <= 0) return HCSPMM_EINVAL;
   if ((long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
-  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                      plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads);
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, GRAPH_IN, D, workspace, workspace_bytes, stream_v, nullptr, values, heads);
 }
 
 // Multi-head edge-weighted product with indexed values (spmm_weighted_indexed.hip): hcspmm_forward_weighted_heads's checks and
@@ -392,8 +407,7 @@ extern "C" int hcspmm_forward_weighted_indexed(const void* X, int64_t x_rows, in
   if (!values || heads <= 0 || num_values < 0 || (E > 0 && (!value_index || num_values == 0))) return HCSPMM_EINVAL;
   if (num_values > INT32_MAX || num_values > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
   static const int32_t no_entries = 0;  // E = 0: nothing is read through the index, which may be NULL
-  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d,
-                      ph, N, E, D, workspace, workspace_bytes, stream_v, nullptr, values, heads,
+  return forward_impl(X, x_rows, ldx, Z, ldz, dtype, GRAPH_IN, D, workspace, workspace_bytes, stream_v, nullptr, values, heads,
                       value_index ? value_index : &no_entries, num_values);
 }
 
@@ -424,22 +438,14 @@ extern "C" int hcspmm_forward_fp8(const void* Xq, int64_t x_rows, int64_t ldx, i
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
   const int vec = nominal_vec(kDtypeF8, D);
   const bool binary = !values && !row_scale;
+  const GraphIn g = GRAPH_IN;
+  hcspmm::PlanArgs a;
+  const int rc = bind_graph(a, g, D, x_rows, workspace, workspace_bytes, 1, kDtypeF8);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.partial && !aligned(a.partial, 4)) return HCSPMM_EINVAL;
+  set_operands(a, Xq, Z, ldx, ldz);
   hipError_t e;
-  if (plan_d && ph) {
-    const int rc = hcspmm_plan_check(ph, N, E, 0);
-    if (rc != HCSPMM_OK) return rc;
-    if (x_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows Xq does not have
-    const size_t need = hcspmm_workspace_bytes(ph, D);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
-    if (need > 0 && !aligned(workspace, 4)) return HCSPMM_EINVAL;
-    hcspmm::PlanArgs a;
-    fill_plan_args(a, plan_d, ph, N, D, kDtypeF8);
-    a.X = Xq;
-    a.Z = Z;
-    a.ldx = (size_t)ldx;
-    a.ldz = (size_t)ldz;
-    a.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
-    a.col = col;
+  if (a.plan) {
     if (binary) {
       e = hcspmm::launch_plan_f8(a, vec, stream);
     } else {
@@ -447,64 +453,35 @@ extern "C" int hcspmm_forward_fp8(const void* Xq, int64_t x_rows, int64_t ldx, i
       e = hcspmm::launch_plan_w_f8(hcspmm::WPlanArgs{a, values, rowptr, ph->segment_len}, vec, stream);
     }
   } else {
-    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
-    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
-    hcspmm::WindowArgs a;
-    a.X = Xq;
-    a.Z = Z;
-    a.ldx = (size_t)ldx;
-    a.ldz = (size_t)ldz;
-    a.rowptr = rowptr;
-    a.col = col;
-    a.blockPartition = blockPartition;
-    a.edgeToColumn = edgeToColumn;
-    a.edgeToRow = edgeToRow;
-    a.hybrid_type = hybrid_type;
-    a.N = (int)N;
-    a.D = D;
-    e = binary ? hcspmm::launch_window_f8(a, vec, stream) : hcspmm::launch_window_w_f8(hcspmm::WWindowArgs{a, values, row_scale}, vec, stream);
+    const hcspmm::WindowArgs w = window_args(g, a);
+    e = binary ? hcspmm::launch_window_f8(w, vec, stream) : hcspmm::launch_window_w_f8(hcspmm::WWindowArgs{w, values, row_scale}, vec, stream);
   }
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
 namespace {
 // backward = false: hcspmm_forward_extremum (src = X, dst = Z); true: its backward (src = grad_Z, dst = grad_X, square)
-int extremum_impl(bool backward, const float* src, int64_t src_rows, int64_t lds, float* dst, int64_t ldd, int dtype,
-                  const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
-                  const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d, const hcspmm_plan_header* ph,
-                  int64_t N, int64_t E, int D, void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out,
-                  const int32_t* arg_in, int64_t ldarg, const int32_t* perm) {
+int extremum_impl(bool backward, const float* src, int64_t src_rows, int64_t lds, float* dst, int64_t ldd, int dtype, const GraphIn& g,
+                  int D, void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out, const int32_t* arg_in,
+                  int64_t ldarg, const int32_t* perm) {
   if (dtype != HCSPMM_DTYPE_F32 || (reduce != HCSPMM_REDUCE_MAX && reduce != HCSPMM_REDUCE_MIN)) return HCSPMM_EINVAL;
-  if (N < 0 || E < 0 || D <= 0 || lds < D || ldd < D) return HCSPMM_EINVAL;
+  if (g.N < 0 || g.E < 0 || D <= 0 || lds < D || ldd < D) return HCSPMM_EINVAL;
   if ((backward || arg_out) && ldarg < D) return HCSPMM_EINVAL;
-  if (N == 0) return HCSPMM_OK;
-  if (!src || !dst || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
-  if (backward && (!arg_in || (E > 0 && !perm))) return HCSPMM_EINVAL;
-  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if (g.N == 0) return HCSPMM_OK;
+  if (!src || !dst || !g.rowptr || (g.E > 0 && !g.col)) return HCSPMM_EINVAL;
+  if (backward && (!arg_in || (g.E > 0 && !perm))) return HCSPMM_EINVAL;
+  if (g.N > INT32_MAX - 16 || g.E > INT32_MAX) return HCSPMM_ERANGE;
   hcspmm::XArgs x{};
-  if (plan_d && ph) {
-    const int rc = hcspmm_plan_check(ph, N, E, 0);
-    if (rc != HCSPMM_OK) return rc;
-    if (src_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows the source does not have
-    const size_t part = hcspmm_workspace_bytes(ph, D);      // fp32 values (forward: positions behind them)
-    const size_t need = backward ? part : 2 * part;
-    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
-    fill_plan_args(x.p, plan_d, ph, N, D, HCSPMM_DTYPE_F32);
-    x.p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
-    x.ppos = (need && !backward) ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + part) : nullptr;
-    x.segment_len = ph->segment_len;
-  } else {
-    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
-    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
-    x.p.N = (int)N;
-    x.p.D = D;
+  // workspace: the fp32 values of the split rows' partial slots; forward: their positions in a second area behind them
+  const int rc = bind_graph(x.p, g, D, src_rows, workspace, workspace_bytes, backward ? 1 : 2, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (x.p.plan) {
+    x.ppos = (x.p.partial && !backward) ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + hcspmm_workspace_bytes(g.ph, D))
+                                        : nullptr;
+    x.segment_len = g.ph->segment_len;
   }
-  x.p.X = src;
-  x.p.Z = dst;
-  x.p.ldx = (size_t)lds;
-  x.p.ldz = (size_t)ldd;
-  x.p.col = col;
-  x.rowptr = rowptr;
+  set_operands(x.p, src, dst, lds, ldd);
+  x.rowptr = g.rowptr;
   x.flip = reduce == HCSPMM_REDUCE_MIN ? 0x80000000u : 0u;
   x.arg = arg_out;
   x.garg = arg_in;
@@ -528,9 +505,8 @@ extern "C" int hcspmm_forward_extremum(const void* X, int64_t x_rows, int64_t ld
                                        const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
                                        void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out,
                                        int64_t ldarg) {
-  return extremum_impl(false, reinterpret_cast<const float*>(X), x_rows, ldx, reinterpret_cast<float*>(Z), ldz, dtype, rowptr, col,
-                       blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes,
-                       stream_v, reduce, arg_out, nullptr, ldarg, nullptr);
+  return extremum_impl(false, reinterpret_cast<const float*>(X), x_rows, ldx, reinterpret_cast<float*>(Z), ldz, dtype, GRAPH_IN, D,
+                       workspace, workspace_bytes, stream_v, reduce, arg_out, nullptr, ldarg, nullptr);
 }
 
 extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg, const int32_t* arg, int64_t ldarg, float* grad_X,
@@ -540,9 +516,8 @@ extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg
                                                 const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
                                                 const int32_t* transpose_perm, void* workspace, size_t workspace_bytes,
                                                 void* stream_v) {
-  return extremum_impl(true, grad_Z, N, ldg, grad_X, ldgx, HCSPMM_DTYPE_F32, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
-                       hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, HCSPMM_REDUCE_MAX, nullptr, arg,
-                       ldarg, transpose_perm);
+  return extremum_impl(true, grad_Z, N, ldg, grad_X, ldgx, HCSPMM_DTYPE_F32, GRAPH_IN, D, workspace, workspace_bytes, stream_v,
+                       HCSPMM_REDUCE_MAX, nullptr, arg, ldarg, transpose_perm);
 }
 
 // Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
@@ -561,26 +536,10 @@ extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64
   if ((reads_x && !X) || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
   if (N > INT32_MAX - 16 || E > INT32_MAX || f_rows > INT32_MAX) return HCSPMM_ERANGE;
   hcspmm::EdgeMsgArgs a{};
-  if (plan_d && ph) {
-    const int rc = hcspmm_plan_check(ph, N, E, 0);
-    if (rc != HCSPMM_OK) return rc;
-    if (reads_x && x_rows < ph->num_columns) return HCSPMM_EINVAL;  // the plan gathers rows X does not have
-    const size_t need = hcspmm_workspace_bytes(ph, D);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
-    fill_plan_args(a.p, plan_d, ph, N, D, HCSPMM_DTYPE_F32);
-    a.p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
-    a.segment_len = ph->segment_len;
-  } else {
-    if (plan_d || ph) return HCSPMM_EINVAL;  // both or neither
-    if (!blockPartition || !hybrid_type || (E > 0 && (!edgeToColumn || !edgeToRow))) return HCSPMM_EINVAL;
-    a.p.N = (int)N;
-    a.p.D = D;
-  }
-  a.p.X = reads_x ? X : nullptr;
-  a.p.Z = Z;
-  a.p.ldx = (size_t)ldx;
-  a.p.ldz = (size_t)ldz;
-  a.p.col = col;
+  const int rc = bind_graph(a.p, GRAPH_IN, D, reads_x ? x_rows : kNoSource, workspace, workspace_bytes, 1, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.plan) a.segment_len = ph->segment_len;
+  set_operands(a.p, reads_x ? X : nullptr, Z, ldx, ldz);
   a.rowptr = rowptr;
   a.op = op;
   a.F = F;
@@ -657,9 +616,8 @@ int sddmm_impl(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_
   const int vec = pick_vec(dtype, dh, lda, ldb, A, B, nullptr);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
   const hipError_t e = heads > 0 ? hcspmm::launch_sddmm_heads_f32(a, heads, vec, stream)
-                       : dtype == HCSPMM_DTYPE_F32 ? hcspmm::launch_sddmm_f32(a, vec, stream)
-                       : dtype == HCSPMM_DTYPE_F16 ? hcspmm::launch_sddmm_f16(a, vec, stream)
-                                                   : hcspmm::launch_sddmm_bf16(a, vec, stream);
+                                 : launch_typed(dtype, hcspmm::launch_sddmm_f32, hcspmm::launch_sddmm_f16, hcspmm::launch_sddmm_bf16, a,
+                                                vec, stream);
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 }  // namespace
@@ -914,11 +872,11 @@ extern "C" int hcspmm_forward_fused(const float* X, float* out, float* out2, con
                                     size_t workspace_bytes, void* stream_v) {
   if (!out || !out2 || !weights || H <= 0) return HCSPMM_EINVAL;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+  const GraphIn g = GRAPH_IN;
   const int form = (plan_d && ph) ? fused_form(ph, X, out2, out, D, H, hcspmm_workspace_bytes(ph, D) ? workspace : nullptr) : 0;
   if (form == 2) {
     const FusedOperands f{weights, (long long)ldr, (long long)ldc, out, H, 2};
-    const int rc = forward_impl(X, N, D, out2, D, HCSPMM_DTYPE_F32, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
-                                hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, &f);
+    const int rc = forward_impl(X, N, D, out2, D, HCSPMM_DTYPE_F32, g, D, workspace, workspace_bytes, stream_v, &f);
     if (rc != HCSPMM_OK) return rc;
     int n_wide = 0;
     wide_choice(ph, D, HCSPMM_DTYPE_F32, &n_wide);
@@ -929,8 +887,7 @@ extern "C" int hcspmm_forward_fused(const float* X, float* out, float* out2, con
   }
   if (form == 1) {
     const FusedOperands f{weights, (long long)ldr, (long long)ldc, out, H, 1};
-    const int rc = forward_impl(X, N, D, out2, D, HCSPMM_DTYPE_F32, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
-                                hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, &f);
+    const int rc = forward_impl(X, N, D, out2, D, HCSPMM_DTYPE_F32, g, D, workspace, workspace_bytes, stream_v, &f);
     if (rc != HCSPMM_OK) return rc;
     if (ph->n_sparse_windows == 0) return HCSPMM_OK;
     const hipError_t e = hcspmm::launch_dense_update(out2, weights, (long long)ldr, (long long)ldc, out, (int)N, D, H,
@@ -969,3 +926,5 @@ extern "C" int hcspmm_weight_grad(const float* A, int64_t lda, const float* B, i
                                                   reinterpret_cast<hipStream_t>(stream_v));
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
+
+#undef GRAPH_IN

@@ -374,20 +374,31 @@ def _check_input(t, name):
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
-                rect=False, dtypes=(torch.float32,)):
-    for t, n in ((X, "input"), (row_pointers, "nodePointer"), (column_index, "edgeList"),
-                 (blockPartition, "blockPartition"), (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
+_GRAPH_NAMES = ("nodePointer", "edgeList", "blockPartition", "edgeToColumn", "edgeToRow")
+
+
+def _check_graph(*arrays, input_error=None):
+    """CHECK_INPUT of the graph arrays in the reference's order -- (row_pointers, column_index) or all five -- then the int32
+    contract of the CSR pair: the kernels read both as int32, so any other dtype would be an out-of-bounds read.
+    input_error: the message of a contiguous input that fails its dtype contract, which the extension reports between the
+    two (None: the input is sound, or the entry point checks it elsewhere)."""
+    for t, n in zip(arrays, _GRAPH_NAMES):
         _check_input(t, n)
-    if X.dtype not in dtypes or X.dim() != 2:
-        raise RuntimeError("input must be a 2-D %s tensor" % " / ".join(str(d).replace("torch.", "") for d in dtypes))
-    N = row_pointers.size(0) - 1
-    E = column_index.size(0)
-    D = X.size(1)
+    if input_error is not None:
+        raise RuntimeError(input_error)
+    if arrays[0].dtype != torch.int32 or arrays[1].dtype != torch.int32:
+        raise RuntimeError("nodePointer / edgeList must be int32")
+
+
+def _graph_args(X, graph, row_nzr, rect=False, dtypes=(torch.float32,)):
+    """The checks of an entry point that gathers the rows of a contiguous X -> its _planned_call"""
+    _check_input(X, "input")
+    _check_graph(*graph[:5], input_error=None if X.dtype in dtypes and X.dim() == 2 else
+                 "input must be a 2-D %s tensor" % " / ".join(str(d).replace("torch.", "") for d in dtypes))
+    N = graph[0].size(0) - 1
     if X.size(0) != N and not rect:
         raise RuntimeError("input has %d rows but the graph has %d nodes" % (X.size(0), N))
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0))
-    return N, E, D, h
+    return _planned_call(graph, row_nzr, X.size(1), X.size(0), X.device)
 
 
 def _checked_header(row_nzr, row_pointers, column_index, N, E, x_rows):
@@ -405,24 +416,56 @@ def _checked_header(row_nzr, row_pointers, column_index, N, E, x_rows):
     return e.header
 
 
+def _ws_bytes(h, D):
+    return int(lib().hcspmm_workspace_bytes(ctypes.byref(h), D))
+
+
+def _ws_bytes_extremum(h, D):
+    return int(lib().hcspmm_extremum_workspace_bytes(ctypes.byref(h), D))
+
+
+class _planned_call(_on_device):
+    """One launch on a graph with or without a plan.  `graph`: the tensors whose pointers open the C ABI's graph arguments -- the
+    six of the SpMM entry points, or (row_pointers, column_index) for the SDDMM.  Runs _checked_header (the plan in `row_nzr`
+    belongs to this graph, and the gathered operand has src_rows >= the rows the plan gathers), then takes the caller's
+    `workspace` if it is large enough or allocates what ws_fn(header, D) -- _ws_bytes, _ws_bytes_extremum; None for an entry
+    point without a workspace -- asks for.  Supplies, spelled here and nowhere else:
+      graph  the run (graph pointers..., plan, header, N, E, D) of every planned entry point
+      ws     the run (workspace, workspace_bytes, stream) that closes it
+    and is the call's _on_device context.  Flat on purpose (slots, no closures): the kernel of a Cora-scale call is shorter
+    than this constructor."""
+    __slots__ = ("N", "E", "D", "graph", "ws", "stream", "buf")
+
+    def __init__(self, graph, row_nzr, D, src_rows, device, workspace=None, ws_fn=_ws_bytes):
+        _on_device.__init__(self, device)
+        self.N, self.E, self.D = N, E, D = graph[0].size(0) - 1, graph[1].size(0), D
+        h = _checked_header(row_nzr, graph[0], graph[1], N, E, src_rows)
+        buf, ws_bytes = None, 0
+        if h is not None and ws_fn is not None:
+            ws_bytes = ws_fn(h, D)
+            if ws_bytes:
+                if workspace is not None and workspace.numel() * workspace.element_size() >= ws_bytes:
+                    buf = workspace  # a caller-kept buffer: nothing is allocated in the step (hcspmm.sharded)
+                else:
+                    buf = torch.empty(ws_bytes // 4, dtype=torch.float32, device=device)
+        self.buf = buf  # (alive until the launch is enqueued)
+        self.stream = stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if h is not None:
+            self.graph = (*map(_ptr, graph), _ptr(row_nzr), ctypes.byref(h), N, E, D)
+        else:
+            self.graph = (*map(_ptr, graph), ctypes.c_void_p(0), None, N, E, D)
+        self.ws = (_ptr(buf), ws_bytes, stream)
+
+
 def _spmm(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
           Z=None, rect=False):
-    L = lib()
-    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                             row_nzr, rect, dtypes=tuple(_DTYPES))
+    c = _graph_args(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                       row_nzr, rect, dtypes=tuple(_DTYPES))
+    D = c.D
     if Z is None:
-        Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_typed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers), _ptr(column_index),
-                                     _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow), _ptr(hybrid_type),
-                                     _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                     ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+        Z = torch.empty((c.N, D), dtype=X.dtype, device=X.device)
+    with c:
+        check(lib().hcspmm_forward_typed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], *c.graph, *c.ws))
     return Z
 
 
@@ -447,33 +490,20 @@ def forward_into(X, Z, row_pointers, column_index, blockPartition, edgeToColumn,
     stride, any row stride) and X may have any number of rows (column ids index them).  Used by the
     multi-GPU shard to multiply one gathered column panel at a time straight into its slice of Z.
     `workspace`: optional caller-kept fp32 buffer of at least workspace_bytes(row_nzr, D) bytes."""
-    L = lib()
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
-                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
-        _check_input(t, n)
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
     for t, n in ((X, "input"), (Z, "output")):
         if not t.is_cuda:
             raise RuntimeError("%s must be a CUDA tensor" % n)
         if t.dtype not in _DTYPES or t.dtype != X.dtype or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
             raise RuntimeError("%s must be a 2-D float32 / float16 / bfloat16 view with unit inner stride" % n)
-    N, E, D = row_pointers.size(0) - 1, column_index.size(0), X.size(1)
+    N, D = row_pointers.size(0) - 1, X.size(1)
     if Z.size(0) != N or Z.size(1) != D:
         raise RuntimeError("output must be [num_nodes, embedding_dim]")
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0))
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            if workspace is not None and workspace.numel() * workspace.element_size() >= ws_bytes:
-                ws = workspace  # a caller-kept buffer: nothing is allocated in the step (hcspmm.sharded)
-            else:
-                ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_typed(_ptr(X), X.size(0), X.stride(0), _ptr(Z), Z.stride(0), _DTYPES[X.dtype], _ptr(row_pointers),
-                                     _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                     _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                     ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                      row_nzr, D, X.size(0), X.device, workspace)
+    with c:
+        check(lib().hcspmm_forward_typed(_ptr(X), X.size(0), X.stride(0), _ptr(Z), Z.stride(0), _DTYPES[X.dtype], *c.graph,
+                                         *c.ws))
     return Z
 
 
@@ -494,27 +524,24 @@ def forward_weighted(X, values, row_pointers, column_index, blockPartition, edge
     plan, registry, fingerprint check and workspace handling as forward; X may be float32 / float16 / bfloat16 (Z has its
     dtype, values stay float32).  values == 1 gives forward's bits.  The values are read on every call (hcspmm.h
     hcspmm_forward_weighted)."""
-    L = lib()
-    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                             row_nzr, False, dtypes=tuple(_DTYPES))
+    c = _graph_args(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                       row_nzr, dtypes=tuple(_DTYPES))
+    N, E, D = c.N, c.E, c.D
     _check_values(values, E, X.device)
     Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_weighted(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
-                                        _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                        _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                        ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
-                                        _ptr(values if E else torch.zeros(1, device=X.device))))  # (NULL values: EINVAL)
+    with c:
+        check(lib().hcspmm_forward_weighted(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], *c.graph, *c.ws,
+                                            _ptr(values if E else torch.zeros(1, device=X.device))))  # (NULL values: EINVAL)
     return [Z]
 
 
 _FP8_E4M3 = 0  # HCSPMM_FP8_E4M3
+
+
+def _check_row_scale(scale, X):
+    _check_input(scale, "scale")
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != X.size(0) or scale.device != X.device:
+        raise RuntimeError("scale must hold one float32 per row of the input, on its device")
 
 
 def quantize_fp8(X, scale=None):
@@ -529,9 +556,7 @@ def quantize_fp8(X, scale=None):
     if D == 0 or D % 4 != 0:
         raise RuntimeError("the 8-bit kernels take embedding widths that are multiples of 4, got %d" % D)
     if scale is not None:
-        _check_input(scale, "scale")
-        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != rows or scale.device != X.device:
-            raise RuntimeError("scale must hold one float32 per row of the input, on its device")
+        _check_row_scale(scale, X)
     Xq = torch.empty((rows, D), dtype=torch.uint8, device=X.device)
     out = torch.empty(rows, dtype=torch.float32, device=X.device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
@@ -541,36 +566,25 @@ def quantize_fp8(X, scale=None):
 
 
 def _spmm_fp8(Xq, scale, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr):
-    L = lib()
-    for t, n in ((Xq, "input"), (row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
-                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
-        _check_input(t, n)
-    if Xq.dtype not in (torch.float8_e4m3fn, torch.uint8) or Xq.dim() != 2:
-        raise RuntimeError("input must be a 2-D float8_e4m3fn (or uint8) tensor")
+    _check_input(Xq, "input")
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow,
+                 input_error=None if Xq.dtype in (torch.float8_e4m3fn, torch.uint8) and Xq.dim() == 2 else
+                 "input must be a 2-D float8_e4m3fn (or uint8) tensor")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), Xq.size(1)
     if Xq.size(0) != N:
         raise RuntimeError("input has %d rows but the graph has %d nodes" % (Xq.size(0), N))
     if D == 0 or D % 4 != 0:
         raise RuntimeError("the 8-bit kernels take embedding widths that are multiples of 4, got %d" % D)
     if scale is not None:
-        _check_input(scale, "scale")
-        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != Xq.size(0) or scale.device != Xq.device:
-            raise RuntimeError("scale must hold one float32 per row of the input, on its device")
+        _check_row_scale(scale, Xq)
     if values is not None:
         _check_values(values, E, Xq.device)
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, Xq.size(0))
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                      row_nzr, D, Xq.size(0), Xq.device)
     Z = torch.empty((N, D), dtype=torch.float32, device=Xq.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=Xq.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(Xq.device).cuda_stream)
-    with _on_device(Xq.device):
-        check(L.hcspmm_forward_fp8(_ptr(Xq), Xq.size(0), D, _FP8_E4M3, _ptr(scale), _ptr(values), _ptr(Z), D, _ptr(row_pointers),
-                                   _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                   _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                   ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    with c:
+        check(lib().hcspmm_forward_fp8(_ptr(Xq), Xq.size(0), D, _FP8_E4M3, _ptr(scale), _ptr(values), _ptr(Z), D, *c.graph,
+                                       *c.ws))
     return Z
 
 
@@ -604,9 +618,9 @@ def forward_weighted_heads(X, values, row_pointers, column_index, blockPartition
     """Multi-head edge-weighted aggregation -> [Z]: values [heads, E] (float32, head-major), X [rows, D] float32 with
     D = heads * Dh, Dh % 4 == 0; Z[:, h*Dh:(h+1)*Dh] = A_{values[h]} X[:, h*Dh:(h+1)*Dh], all heads in one launch.  Each
     head's columns are bit for bit forward_weighted(X, values[h]) at full width (hcspmm.h hcspmm_forward_weighted_heads)."""
-    L = lib()
-    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                             row_nzr, False, dtypes=tuple(_DTYPES))
+    c = _graph_args(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                       row_nzr, dtypes=tuple(_DTYPES))
+    N, E, D = c.N, c.E, c.D
     _check_input(values, "values")
     if values.dtype != torch.float32:
         raise RuntimeError("values must be a float32 tensor")
@@ -617,18 +631,9 @@ def forward_weighted_heads(X, values, row_pointers, column_index, blockPartition
     heads = values.size(0)
     _check_heads_width(D, heads, X.dtype)
     Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_weighted_heads(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
-                                              _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                              _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                              ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
-                                              _ptr(values if E else torch.zeros(1, device=X.device)), heads))
+    with c:
+        check(lib().hcspmm_forward_weighted_heads(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], *c.graph, *c.ws,
+                                                  _ptr(values if E else torch.zeros(1, device=X.device)), heads))
     return [Z]
 
 
@@ -637,9 +642,9 @@ def forward_weighted_indexed(X, values, value_index, row_pointers, column_index,
     """forward_weighted_heads whose weight for entry e is values[h, value_index[e]] -> [Z]: values [heads, V] (or [V]: one
     head, any D forward_weighted takes), value_index int32 [E] with every index in [0, V).  Bit for bit
     forward_weighted_heads(X, values[:, value_index]) without the gathered copy (hcspmm.h hcspmm_forward_weighted_indexed)."""
-    L = lib()
-    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                             row_nzr, False, dtypes=tuple(_DTYPES))
+    c = _graph_args(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                       row_nzr, dtypes=tuple(_DTYPES))
+    N, E, D = c.N, c.E, c.D
     _check_input(values, "values")
     _check_input(value_index, "value_index")
     if values.dtype != torch.float32:
@@ -657,48 +662,27 @@ def forward_weighted_indexed(X, values, value_index, row_pointers, column_index,
     if heads > 1:
         _check_heads_width(D, heads, X.dtype)
     Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_weighted_indexed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], _ptr(row_pointers),
-                                                _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                                _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                                ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream,
-                                                _ptr(values if V else torch.zeros(1, device=X.device)), heads,
-                                                _ptr(value_index), V))
+    with c:
+        check(lib().hcspmm_forward_weighted_indexed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], *c.graph, *c.ws,
+                                                    _ptr(values if V else torch.zeros(1, device=X.device)), heads,
+                                                    _ptr(value_index), V))
     return [Z]
 
 
 def _extremum(X, graph, reduce, return_arg):
-    L = lib()
-    row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr = graph
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
-                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
-        _check_input(t, n)
+    row_nzr = graph[6]
+    _check_graph(*graph[:5])
     if not X.is_cuda:
         raise RuntimeError("input must be a CUDA tensor")
     if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
         raise RuntimeError("input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)")
-    N, E, D = row_pointers.size(0) - 1, column_index.size(0), X.size(1)
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0))
+    N, D = graph[0].size(0) - 1, X.size(1)
+    c = _planned_call(graph[:6], row_nzr, D, X.size(0), X.device, ws_fn=_ws_bytes_extremum)
     Z = torch.empty((N, D), dtype=torch.float32, device=X.device)
     arg = torch.empty((N, D), dtype=torch.int32, device=X.device) if return_arg else None
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_extremum_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_extremum(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, 0, _ptr(row_pointers), _ptr(column_index),
-                                        _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow), _ptr(hybrid_type),
-                                        _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                        ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream, reduce,
-                                        _ptr(arg) if arg is not None else ctypes.c_void_p(0), D))
+    with c:
+        check(lib().hcspmm_forward_extremum(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, 0, *c.graph, *c.ws, reduce,
+                                            _ptr(arg) if arg is not None else ctypes.c_void_p(0), D))
     return [Z, arg] if return_arg else [Z]
 
 
@@ -724,9 +708,8 @@ def forward_extremum_backward(grad_Z, arg, perm, row_pointers, column_index, blo
     """Backward of forward_max / forward_min on a square, pattern-symmetric graph -> grad_X [N, D]:
     grad_X[j][d] = sum of grad_Z[i][d] over the entries e = (i, j) with arg[i][d] == e.  perm: the int32 transpose
     permutation (transpose_permutation(...).int()).  Deterministic, no atomics (hcspmm.h hcspmm_forward_extremum_backward)."""
-    L = lib()
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
-                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow"), (grad_Z, "grad_Z"), (arg, "arg"), (perm, "perm")):
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    for t, n in ((grad_Z, "grad_Z"), (arg, "arg"), (perm, "perm")):
         _check_input(t, n)
     N, E = row_pointers.size(0) - 1, column_index.size(0)
     if grad_Z.dtype != torch.float32 or grad_Z.dim() != 2 or grad_Z.size(0) != N:
@@ -739,20 +722,12 @@ def forward_extremum_backward(grad_Z, arg, perm, row_pointers, column_index, blo
     for t, n in ((arg, "arg"), (perm, "perm")):
         if t.device != grad_Z.device:
             raise RuntimeError("%s must be on the device of grad_Z" % n)
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, N)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                      row_nzr, D, N, grad_Z.device)
     grad_X = torch.empty((N, D), dtype=torch.float32, device=grad_Z.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=grad_Z.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(grad_Z.device).cuda_stream)
-    with _on_device(grad_Z.device):
-        check(L.hcspmm_forward_extremum_backward(_ptr(grad_Z), D, _ptr(arg), D, _ptr(grad_X), D, _ptr(row_pointers),
-                                                 _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                                 _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                                 ctypes.byref(h) if h is not None else None, N, E, D, _ptr(perm), _ptr(ws),
-                                                 ws_bytes, stream))
+    with c:
+        check(lib().hcspmm_forward_extremum_backward(_ptr(grad_Z), D, _ptr(arg), D, _ptr(grad_X), D, *c.graph, _ptr(perm),
+                                                     *c.ws))
     return grad_X
 
 
@@ -779,11 +754,8 @@ def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edge
     views with unit inner stride; F is read on every call.  Deterministic, no atomics (hcspmm.h hcspmm_forward_edge_messages).
     The gradient with respect to X is this call on A^T's graph with index = entry_index_t (or, on a pattern-symmetric graph,
     the int32 transpose permutation): "mul" with X := dZ, "add_relu" as "copy" of edge_messages_grad's result."""
-    L = lib()
     code = _edge_op(op)
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList"), (blockPartition, "blockPartition"),
-                 (edgeToColumn, "edgeToColumn"), (edgeToRow, "edgeToRow")):
-        _check_input(t, n)
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
     _check_f32_view(F, "F")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), F.size(1)
     if X is None and op != "copy":
@@ -801,20 +773,13 @@ def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edge
         raise RuntimeError("F has %d rows but the graph has %d entries" % (F.size(0), E))
     if D == 0:
         raise RuntimeError("F must have at least one column")
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, X.size(0) if X is not None else 1 << 62)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type),
+                      row_nzr, D, X.size(0) if X is not None else 1 << 62, F.device)  # (copy: no gathered rows)
     Z = torch.empty((N, D), dtype=torch.float32, device=F.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=F.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(F.device).cuda_stream)
-    with _on_device(F.device):
-        check(L.hcspmm_forward_edge_messages(_ptr(X), X.size(0) if X is not None else 0, X.stride(0) if X is not None else D,
-                                             _ptr(F), F.size(0), F.stride(0), _ptr(index), code, _ptr(Z), D, _ptr(row_pointers),
-                                             _ptr(column_index), _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow),
-                                             _ptr(hybrid_type), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                             ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    with c:
+        check(lib().hcspmm_forward_edge_messages(_ptr(X), X.size(0) if X is not None else 0,
+                                                 X.stride(0) if X is not None else D, _ptr(F), F.size(0), F.stride(0),
+                                                 _ptr(index), code, _ptr(Z), D, *c.graph, *c.ws))
     return [Z]
 
 
@@ -823,8 +788,7 @@ def edge_messages_grad(dZ, X, F, row_pointers, column_index, op="add_relu"):
     "add_relu" dZ[row(e)] where X[col(e)] + F[e] > 0 and +0 elsewhere, "copy" dZ[row(e)] (X and F may be None).  Edge-parallel,
     every element written once (hcspmm.h hcspmm_edge_messages_grad)."""
     code = _edge_op(op)
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
+    _check_graph(row_pointers, column_index)
     _check_f32_view(dZ, "dZ")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), dZ.size(1)
     if dZ.size(0) != N:
@@ -862,8 +826,7 @@ def edge_norm(row_pointers, column_index, kind):
     "sym" = 1/sqrt(deg_r * deg_c) (GCN), "mean" = 1/deg_r (GraphSAGE-mean); deg = row length."""
     if kind not in _NORMS:
         raise ValueError("kind must be 'sym' or 'mean', got %r" % (kind,))
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
+    _check_graph(row_pointers, column_index)
     N, E = row_pointers.numel() - 1, column_index.numel()
     out = torch.empty(E, dtype=torch.float32, device=row_pointers.device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(row_pointers.device).cuda_stream)
@@ -910,14 +873,9 @@ def _check_view(t, name, dtype=None):
                            % (name, "" if dtype is None else ", of the dtype of A"))
 
 
-def sddmm(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr):
-    """Sampled dense-dense product on the stored entries -> float32 [E]: out[e] = <A[row(e)], B[column_index[e]]>
-    (include/hcspmm.h hcspmm_sddmm).  A [N, D] and B [b_rows, D] are float32 / float16 / bfloat16 of one dtype, 2-D views
-    with unit inner stride (column slices need no copy); 16-bit inputs are summed in fp32.  The graph tensors are those of
-    forward_weighted: with a plan in row_nzr it is checked against this graph and B must have every row it gathers.  The
-    gradient of forward_weighted with respect to its values is sddmm(dZ, X)."""
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
+def _sddmm(A, B, row_pointers, column_index, row_nzr, heads):
+    """heads None: sddmm -> [E]; an int: sddmm_heads -> [heads, E]"""
+    _check_graph(row_pointers, column_index)
     _check_view(A, "A")
     _check_view(B, "B", A.dtype)
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), A.size(1)
@@ -927,14 +885,26 @@ def sddmm(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeTo
         raise RuntimeError("B has %d columns but A has %d" % (B.size(1), D))
     if B.device != A.device:
         raise RuntimeError("B must be on the device of A")
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, B.size(0))
-    out = torch.empty(E, dtype=torch.float32, device=A.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-    with _on_device(A.device):
-        check(lib().hcspmm_sddmm(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
-                                 _ptr(row_pointers), _ptr(column_index), _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                 ctypes.byref(h) if h is not None else None, N, E, D, stream))
+    if heads is not None:
+        _check_heads_width(D, heads, A.dtype)
+    c = _planned_call((row_pointers, column_index), row_nzr, D, B.size(0), A.device, ws_fn=None)
+    out = torch.empty(E if heads is None else (heads, E), dtype=torch.float32, device=A.device)
+    operands = (_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out))
+    with c:
+        if heads is None:
+            check(lib().hcspmm_sddmm(*operands, *c.graph, c.stream))
+        else:
+            check(lib().hcspmm_sddmm_heads(*operands, *c.graph, c.stream, heads))
     return out
+
+
+def sddmm(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr):
+    """Sampled dense-dense product on the stored entries -> float32 [E]: out[e] = <A[row(e)], B[column_index[e]]>
+    (include/hcspmm.h hcspmm_sddmm).  A [N, D] and B [b_rows, D] are float32 / float16 / bfloat16 of one dtype, 2-D views
+    with unit inner stride (column slices need no copy); 16-bit inputs are summed in fp32.  The graph tensors are those of
+    forward_weighted: with a plan in row_nzr it is checked against this graph and B must have every row it gathers.  The
+    gradient of forward_weighted with respect to its values is sddmm(dZ, X)."""
+    return _sddmm(A, B, row_pointers, column_index, row_nzr, None)
 
 
 def sddmm_heads(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
@@ -943,28 +913,7 @@ def sddmm_heads(A, B, row_pointers, column_index, blockPartition, edgeToColumn, 
     all heads in one launch (hcspmm.h hcspmm_sddmm_heads).  A [N, D] and B [b_rows, D] float32 views with unit inner stride,
     D = heads * Dh, Dh % 4 == 0.  Each head is bit for bit sddmm on the column slices.  The gradient of
     forward_weighted_heads with respect to its values is sddmm_heads(dZ, X)."""
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
-    _check_view(A, "A")
-    _check_view(B, "B", A.dtype)
-    N, E, D = row_pointers.size(0) - 1, column_index.size(0), A.size(1)
-    if A.size(0) != N:
-        raise RuntimeError("A has %d rows but the graph has %d nodes" % (A.size(0), N))
-    if B.size(1) != D:
-        raise RuntimeError("B has %d columns but A has %d" % (B.size(1), D))
-    if B.device != A.device:
-        raise RuntimeError("B must be on the device of A")
-    heads = int(heads)
-    _check_heads_width(D, heads, A.dtype)
-    h = _checked_header(row_nzr, row_pointers, column_index, N, E, B.size(0))
-    out = torch.empty((heads, E), dtype=torch.float32, device=A.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-    with _on_device(A.device):
-        check(lib().hcspmm_sddmm_heads(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
-                                       _ptr(row_pointers), _ptr(column_index),
-                                       _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                       ctypes.byref(h) if h is not None else None, N, E, D, stream, heads))
-    return out
+    return _sddmm(A, B, row_pointers, column_index, row_nzr, int(heads))
 
 
 def _softmax_operand(t, name, E, device):
@@ -1022,10 +971,7 @@ def _scores_operand(t, name, device):
 
 
 def _gat_graph(row_pointers, column_index, s_dst, s_src):
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
-    if row_pointers.dtype != torch.int32 or column_index.dtype != torch.int32:
-        raise RuntimeError("nodePointer / edgeList must be int32")
+    _check_graph(row_pointers, column_index)
     N, E = row_pointers.numel() - 1, column_index.numel()
     n_dst, heads = _scores_operand(s_dst, "s_dst", row_pointers.device)
     src_rows, heads_src = _scores_operand(s_src, "s_src", row_pointers.device)
@@ -1060,10 +1006,9 @@ def _perm_i32(perm, E, device):
     return perm if perm.dtype == torch.int32 else perm.to(torch.int32)
 
 
-def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, perm, negative_slope=0.2):
-    """Backward of gat_attention on a square, pattern-symmetric graph -> (grad_s_dst, grad_s_src, grad_scores), shaped as
-    s_dst, s_src and alpha; grad_scores is the gradient of z = s_dst[row] + s_src[col].  perm is transpose_permutation's
-    (int64 as it returns it, or an int32 copy; the kernel reads int32).  Two launches (hcspmm_gat_attention_backward)."""
+def _gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t, perm, negative_slope):
+    """row_pointers_t None: the pattern-symmetric form (perm = transpose_permutation's); else the directed form (perm =
+    entry_index_t)"""
     N, E, src_rows, heads = _gat_graph(row_pointers, column_index, s_dst, s_src)
     if src_rows != N:
         raise RuntimeError("s_src has %d rows but the backward needs one per node (%d)" % (src_rows, N))
@@ -1074,15 +1019,30 @@ def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column
             raise RuntimeError("%s must be float32 of shape %s, got %s %s" % (n, shape, t.dtype, tuple(t.shape)))
         if t.device != row_pointers.device:
             raise RuntimeError("%s must be on the device of row_pointers" % n)
-    perm = _perm_i32(perm, E, row_pointers.device)
+    if row_pointers_t is None:
+        perm = _perm_i32(perm, E, row_pointers.device)
+    else:
+        _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
+        _transposed_i32(perm, "entry_index_t", E, row_pointers.device)
     grad_s_dst, grad_s_src = torch.empty_like(s_dst), torch.empty_like(s_src)
     grad_scores = torch.empty(shape, dtype=torch.float32, device=alpha.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream)
+    operands = (_ptr(alpha), _ptr(grad_alpha), _ptr(s_dst), _ptr(s_src), float(negative_slope), _ptr(row_pointers),
+                _ptr(column_index))
+    outputs = (E, heads, _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src),
+               ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream))
     with _on_device(alpha.device):
-        check(lib().hcspmm_gat_attention_backward(_ptr(alpha), _ptr(grad_alpha), _ptr(s_dst), _ptr(s_src), float(negative_slope),
-                                                  _ptr(row_pointers), _ptr(column_index), _ptr(perm), N, E, heads,
-                                                  _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src), stream))
+        if row_pointers_t is None:
+            check(lib().hcspmm_gat_attention_backward(*operands, _ptr(perm), N, *outputs))
+        else:
+            check(lib().hcspmm_gat_attention_backward_directed(*operands, _ptr(row_pointers_t), _ptr(perm), N, N, *outputs))
     return grad_s_dst, grad_s_src, grad_scores
+
+
+def gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, perm, negative_slope=0.2):
+    """Backward of gat_attention on a square, pattern-symmetric graph -> (grad_s_dst, grad_s_src, grad_scores), shaped as
+    s_dst, s_src and alpha; grad_scores is the gradient of z = s_dst[row] + s_src[col].  perm is transpose_permutation's
+    (int64 as it returns it, or an int32 copy; the kernel reads int32).  Two launches (hcspmm_gat_attention_backward)."""
+    return _gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, None, perm, negative_slope)
 
 
 def _transposed_i32(t, name, n, device):
@@ -1099,36 +1059,14 @@ def gat_attention_backward_directed(alpha, grad_alpha, s_dst, s_src, row_pointer
     """gat_attention_backward on any square graph: (row_pointers_t, entry_index_t) are transpose_graph's, and grad_s_src sums
     over the rows of A^T (hcspmm_gat_attention_backward_directed).  With (row_pointers, perm as int32) of a pattern-symmetric
     graph it returns gat_attention_backward's bits."""
-    N, E, src_rows, heads = _gat_graph(row_pointers, column_index, s_dst, s_src)
-    if src_rows != N:
-        raise RuntimeError("s_src has %d rows but the backward needs one per node (%d)" % (src_rows, N))
-    shape = (E,) if s_dst.dim() == 1 else (heads, E)
-    for t, n in ((alpha, "alpha"), (grad_alpha, "grad_alpha")):
-        _check_input(t, n)
-        if t.dtype != torch.float32 or tuple(t.shape) != shape:
-            raise RuntimeError("%s must be float32 of shape %s, got %s %s" % (n, shape, t.dtype, tuple(t.shape)))
-        if t.device != row_pointers.device:
-            raise RuntimeError("%s must be on the device of row_pointers" % n)
-    _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
-    _transposed_i32(entry_index_t, "entry_index_t", E, row_pointers.device)
-    grad_s_dst, grad_s_src = torch.empty_like(s_dst), torch.empty_like(s_src)
-    grad_scores = torch.empty(shape, dtype=torch.float32, device=alpha.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(alpha.device).cuda_stream)
-    with _on_device(alpha.device):
-        check(lib().hcspmm_gat_attention_backward_directed(_ptr(alpha), _ptr(grad_alpha), _ptr(s_dst), _ptr(s_src),
-                                                           float(negative_slope), _ptr(row_pointers), _ptr(column_index),
-                                                           _ptr(row_pointers_t), _ptr(entry_index_t), N, N, E, heads,
-                                                           _ptr(grad_scores), _ptr(grad_s_dst), _ptr(grad_s_src), stream))
-    return grad_s_dst, grad_s_src, grad_scores
+    return _gat_attention_backward(alpha, grad_alpha, s_dst, s_src, row_pointers, column_index, row_pointers_t, entry_index_t,
+                                   negative_slope)
 
 
 def _gatv2_operands(H_dst, H_src, att, row_pointers, column_index):
     """-> (N, E, D, heads) of a GATv2 call: H_dst [N, D] and H_src [src_rows, D] float32 views with unit inner stride, att
     [heads, Dh] (or [Dh] for one head) contiguous, D = heads * Dh, Dh % 4 == 0"""
-    for t, n in ((row_pointers, "nodePointer"), (column_index, "edgeList")):
-        _check_input(t, n)
-    if row_pointers.dtype != torch.int32 or column_index.dtype != torch.int32:
-        raise RuntimeError("nodePointer / edgeList must be int32")
+    _check_graph(row_pointers, column_index)
     _check_view(H_dst, "H_dst", torch.float32)
     _check_view(H_src, "H_src", torch.float32)
     _check_input(att, "att")
@@ -1164,11 +1102,10 @@ def gatv2_scores(H_dst, H_src, att, row_pointers, column_index, negative_slope=0
     return out
 
 
-def gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, perm, negative_slope=0.2):
-    """Backward of gatv2_scores on a square, pattern-symmetric graph -> (grad_H_dst, grad_H_src, grad_att), contiguous and
-    shaped as H_dst, H_src and att.  grad_logits is float32 of gatv2_scores' shape; perm is transpose_permutation's (int64
-    as it returns it, or an int32 copy; the kernel reads int32).  Three launches, no atomics: two calls give the same bits
-    (hcspmm_gatv2_scores_backward; the workspace is allocated here)."""
+def _gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, perm,
+                           negative_slope):
+    """row_pointers_t None: the pattern-symmetric form (perm = transpose_permutation's); else the directed form (A^T's arrays,
+    perm = entry_index_t)"""
     N, E, D, heads = _gatv2_operands(H_dst, H_src, att, row_pointers, column_index)
     if H_src.size(0) != N:
         raise RuntimeError("H_src has %d rows but the backward needs one per node (%d)" % (H_src.size(0), N))
@@ -1178,20 +1115,37 @@ def gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_i
         raise RuntimeError("grad_logits must be float32 of shape %s, got %s %s" % (shape, grad_logits.dtype, tuple(grad_logits.shape)))
     if grad_logits.device != H_dst.device:
         raise RuntimeError("grad_logits must be on the device of H_dst")
-    perm = _perm_i32(perm, E, row_pointers.device)
+    if row_pointers_t is None:
+        perm = _perm_i32(perm, E, row_pointers.device)
+    else:
+        _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
+        _transposed_i32(column_index_t, "column_index_t", E, row_pointers.device)
+        _transposed_i32(perm, "entry_index_t", E, row_pointers.device)
     L = lib()
     grad_dst = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
     grad_src = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
     grad_att = torch.empty_like(att)
     ws_bytes = int(L.hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads))
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=H_dst.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
+    operands = (_ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.stride(0), _ptr(att), float(negative_slope),
+                _ptr(row_pointers), _ptr(column_index))
+    outputs = (E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D, _ptr(grad_att), _ptr(ws), ws_bytes,
+               ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream))
     with _on_device(H_dst.device):
-        check(L.hcspmm_gatv2_scores_backward(_ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.stride(0),
-                                             _ptr(att), float(negative_slope), _ptr(row_pointers), _ptr(column_index), _ptr(perm),
-                                             N, E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D, _ptr(grad_att), _ptr(ws),
-                                             ws_bytes, stream))
+        if row_pointers_t is None:
+            check(L.hcspmm_gatv2_scores_backward(*operands, _ptr(perm), N, *outputs))
+        else:
+            check(L.hcspmm_gatv2_scores_backward_directed(*operands, _ptr(row_pointers_t), _ptr(column_index_t), _ptr(perm), N, N,
+                                                          *outputs))
     return grad_dst, grad_src, grad_att
+
+
+def gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, perm, negative_slope=0.2):
+    """Backward of gatv2_scores on a square, pattern-symmetric graph -> (grad_H_dst, grad_H_src, grad_att), contiguous and
+    shaped as H_dst, H_src and att.  grad_logits is float32 of gatv2_scores' shape; perm is transpose_permutation's (int64
+    as it returns it, or an int32 copy; the kernel reads int32).  Three launches, no atomics: two calls give the same bits
+    (hcspmm_gatv2_scores_backward; the workspace is allocated here)."""
+    return _gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, None, None, perm, negative_slope)
 
 
 def gatv2_scores_backward_directed(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
@@ -1199,32 +1153,8 @@ def gatv2_scores_backward_directed(grad_logits, H_dst, H_src, att, row_pointers,
     """gatv2_scores_backward on any square graph: (row_pointers_t, column_index_t, entry_index_t) are transpose_graph's, and
     grad_H_src walks the rows of A^T (hcspmm_gatv2_scores_backward_directed).  With (row_pointers, column_index, perm as
     int32) of a pattern-symmetric graph it returns gatv2_scores_backward's bits."""
-    N, E, D, heads = _gatv2_operands(H_dst, H_src, att, row_pointers, column_index)
-    if H_src.size(0) != N:
-        raise RuntimeError("H_src has %d rows but the backward needs one per node (%d)" % (H_src.size(0), N))
-    shape = (E,) if att.dim() == 1 else (heads, E)
-    _check_input(grad_logits, "grad_logits")
-    if grad_logits.dtype != torch.float32 or tuple(grad_logits.shape) != shape:
-        raise RuntimeError("grad_logits must be float32 of shape %s, got %s %s" % (shape, grad_logits.dtype, tuple(grad_logits.shape)))
-    if grad_logits.device != H_dst.device:
-        raise RuntimeError("grad_logits must be on the device of H_dst")
-    _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
-    _transposed_i32(column_index_t, "column_index_t", E, row_pointers.device)
-    _transposed_i32(entry_index_t, "entry_index_t", E, row_pointers.device)
-    L = lib()
-    grad_dst = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
-    grad_src = torch.empty((N, D), dtype=torch.float32, device=H_dst.device)
-    grad_att = torch.empty_like(att)
-    ws_bytes = int(L.hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads))
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=H_dst.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
-    with _on_device(H_dst.device):
-        check(L.hcspmm_gatv2_scores_backward_directed(_ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src),
-                                                      H_src.stride(0), _ptr(att), float(negative_slope), _ptr(row_pointers),
-                                                      _ptr(column_index), _ptr(row_pointers_t), _ptr(column_index_t),
-                                                      _ptr(entry_index_t), N, N, E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D,
-                                                      _ptr(grad_att), _ptr(ws), ws_bytes, stream))
-    return grad_dst, grad_src, grad_att
+    return _gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
+                                  entry_index_t, negative_slope)
 
 
 def update(X, W):
@@ -1271,9 +1201,8 @@ forward_fixed64 = forward
 
 def _fused(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
            weights, output=None):
-    L = lib()
-    N, E, D, h = _graph_args(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
-                             row_nzr)
+    c = _graph_args(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr)
+    N, D = c.N, c.D
     if not weights.is_cuda or weights.dtype != torch.float32 or weights.dim() != 2 or weights.size(0) != D:
         raise RuntimeError("weights must be a CUDA float32 tensor of shape [embedding_dim, hidden_dim]")
     H = weights.size(1)
@@ -1284,18 +1213,9 @@ def _fused(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRo
         if output.dtype != torch.float32 or output.numel() != N * H:
             raise RuntimeError("output must be float32 with num_nodes*hidden_dim elements")
     out2 = torch.empty((N, D), dtype=torch.float32, device=X.device)
-    ws, ws_bytes = None, 0
-    if h is not None:
-        ws_bytes = int(L.hcspmm_workspace_bytes(ctypes.byref(h), D))
-        if ws_bytes:
-            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=X.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
-    with _on_device(X.device):
-        check(L.hcspmm_forward_fused(_ptr(X), _ptr(output), _ptr(out2), _ptr(weights), weights.stride(0),
-                                     weights.stride(1), H, _ptr(row_pointers), _ptr(column_index),
-                                     _ptr(blockPartition), _ptr(edgeToColumn), _ptr(edgeToRow), _ptr(hybrid_type),
-                                     _ptr(row_nzr) if h is not None else ctypes.c_void_p(0),
-                                     ctypes.byref(h) if h is not None else None, N, E, D, _ptr(ws), ws_bytes, stream))
+    with c:
+        check(lib().hcspmm_forward_fused(_ptr(X), _ptr(output), _ptr(out2), _ptr(weights), weights.stride(0), weights.stride(1), H,
+                                         *c.graph, *c.ws))
     return [output, out2]
 
 

@@ -10,6 +10,7 @@
 
 #include <cstring>
 #include <mutex>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -58,6 +59,25 @@ std::unordered_map<const void*, PlanEntry> g_plans;
 uint64_t g_tick = 0;
 constexpr size_t kMaxPlans = 256, kMaxGraphsPerPlan = 8;
 
+const int* iptr(const torch::Tensor& t) { return (t.defined() && t.numel() > 0) ? t.data_ptr<int>() : nullptr; }
+int* mptr(torch::Tensor& t) { return t.numel() > 0 ? t.data_ptr<int>() : nullptr; }
+
+// the stream the library enqueues on: the current one of the tensor's device
+void* current_stream(const torch::Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
+
+// Reads the first HCSPMM_PLAN_HEADER_WORDS of `row_nzr` back (one small device read); false unless they are a plan header
+bool read_plan_header(const torch::Tensor& row_nzr, hcspmm_plan_header* h) {
+  if (!row_nzr.defined() || row_nzr.numel() < HCSPMM_PLAN_HEADER_WORDS || row_nzr.scalar_type() != torch::kInt) return false;
+  auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
+  std::memcpy(h, host.data_ptr<int>(), sizeof(*h));
+  return h->magic == HCSPMM_PLAN_MAGIC;
+}
+
+void check_i32_graph(const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt,
+              "nodePointer / edgeList must be int32");
+}
+
 void remember(const torch::Tensor& plan, const hcspmm_plan_header& h, const torch::Tensor* rp, const torch::Tensor* col) {
   std::lock_guard<std::mutex> lk(g_mu);
   for (auto it = g_plans.begin(); it != g_plans.end();) it = it->second.plan.expired() ? g_plans.erase(it) : std::next(it);
@@ -96,18 +116,13 @@ bool lookup(const torch::Tensor& row_nzr, const torch::Tensor& nodePointer, cons
           graph_ok = true;
     }
   }
-  if (!known) {  // first sight of this tensor (e.g. a clone): one small device read
-    auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
-    std::memcpy(h, host.data_ptr<int>(), sizeof(*h));
-    if (h->magic != HCSPMM_PLAN_MAGIC) return false;
-  }
+  if (!known && !read_plan_header(row_nzr, h)) return false;  // first sight of this tensor (e.g. a clone)
   check_rc(hcspmm_plan_check(h, N, E, row_nzr.numel()), "forward(plan check)");
   if (!graph_ok) {
     auto fp = torch::empty({1}, row_nzr.options().dtype(torch::kLong));
     const c10::DeviceGuard guard(row_nzr.device());
     check_rc(hcspmm_graph_fingerprint_device(nodePointer.data_ptr<int>(), edgeList.numel() ? edgeList.data_ptr<int>() : nullptr, N,
-                                             E, reinterpret_cast<uint64_t*>(fp.data_ptr<int64_t>()),
-                                             (void*)c10::hip::getCurrentHIPStream(row_nzr.device().index()).stream()),
+                                             E, reinterpret_cast<uint64_t*>(fp.data_ptr<int64_t>()), current_stream(row_nzr)),
              "forward(graph fingerprint)");
     const uint64_t got = (uint64_t)fp.item<int64_t>();
     const uint64_t want = ((uint64_t)h->fingerprint_hi << 32) | h->fingerprint_lo;
@@ -126,15 +141,6 @@ bool lookup(const torch::Tensor& row_nzr, const torch::Tensor& nodePointer, cons
   return true;
 }
 
-struct Call {
-  int64_t N, E;
-  int D;
-  bool has_plan;
-  hcspmm_plan_header header;
-  torch::Tensor workspace;
-  void* stream;
-};
-
 // HCSPMM_DTYPE_* of a feature tensor, -1 if unsupported
 int feature_dtype(const torch::Tensor& t) {
   switch (t.scalar_type()) {
@@ -145,68 +151,138 @@ int feature_dtype(const torch::Tensor& t) {
   }
 }
 
-// rect: the graph is a row block whose column ids index the rows of a taller `input` (additions forward_rect /
-// forward_into); otherwise input must have exactly num_nodes rows, as in the reference.
-Call prepare(const torch::Tensor& input, const torch::Tensor& nodePointer, const torch::Tensor& edgeList,
-             const torch::Tensor& blockPartition, const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
-             const torch::Tensor& row_nzr, bool allow_16bit = false, bool rect = false, bool strided = false,
-             const torch::Tensor* workspace = nullptr, bool fp8 = false) {
-  if (strided) {
-    CHECK_CUDA(input);
-  } else {
-    CHECK_INPUT(input);
-  }
-  CHECK_INPUT(nodePointer);
-  CHECK_INPUT(edgeList);
-  CHECK_INPUT(blockPartition);
-  CHECK_INPUT(edgeToColumn);
-  CHECK_INPUT(edgeToRow);
-  if (fp8) {  // 8-bit codes (forward_fp8 / forward_weighted_fp8)
-    TORCH_CHECK(input.dim() == 2 && (input.scalar_type() == torch::kFloat8_e4m3fn || input.scalar_type() == torch::kByte),
-                "input must be a 2-D float8_e4m3fn (or uint8) tensor");
-  } else {
-    TORCH_CHECK(input.dim() == 2 && (allow_16bit ? feature_dtype(input) >= 0 : input.scalar_type() == torch::kFloat),
-                allow_16bit ? "input must be a 2-D float32 / float16 / bfloat16 tensor" : "input must be a 2-D float32 tensor");
-  }
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt,
-              "nodePointer / edgeList must be int32");
-  Call c;
-  c.N = nodePointer.size(0) - 1;  // reference :212-214
-  c.E = edgeList.size(0);
-  c.D = (int)input.size(1);
-  TORCH_CHECK(rect || input.size(0) == c.N, "input has ", input.size(0), " rows but the graph has ", c.N, " nodes");
-  c.has_plan = lookup(row_nzr, nodePointer, edgeList, c.N, c.E, &c.header);
-  if (c.has_plan) {
-    TORCH_CHECK(input.size(0) >= c.header.num_columns, "input has ", input.size(0), " rows but the plan gathers from ",
-                c.header.num_columns);
-    const size_t need = hcspmm_workspace_bytes(&c.header, c.D);
-    if (need) {
-      if (workspace && workspace->defined() && workspace->is_cuda() && (size_t)workspace->nbytes() >= need)
-        c.workspace = *workspace;  // a caller-kept buffer: nothing is allocated in the step
-      else
-        c.workspace = torch::empty({(int64_t)(need / 4)}, input.options().dtype(torch::kFloat));
-    }
-  }
-  c.stream = (void*)c10::hip::getCurrentHIPStream(input.device().index()).stream();
-  return c;
+// fn(parts...): a C-ABI call put together from runs of arguments -- the entry point's own operands and PlannedCall's
+// graph() / plan() / ws().  Every argument is still converted to the prototype in hcspmm.h at compile time.
+template <class Fn, class... Parts>
+int invoke(Fn fn, const Parts&... parts) {
+  return std::apply(fn, std::tuple_cat(parts...));
 }
 
-const int* iptr(const torch::Tensor& t) { return (t.defined() && t.numel() > 0) ? t.data_ptr<int>() : nullptr; }
-int* mptr(torch::Tensor& t) { return t.numel() > 0 ? t.data_ptr<int>() : nullptr; }
+// what an entry point asks of its PlannedCall
+struct CallOptions {
+  enum Dtypes { kF32, kTyped, kFp8 };
+  CallOptions(Dtypes d = kF32) : dtypes(d) {}
+  Dtypes dtypes;          // input is float32 / float32, float16 or bfloat16 / 8-bit codes (float8_e4m3fn or uint8)
+  bool rect = false;      // the graph is a row block whose column ids index the rows of a taller input (forward_rect /
+                          // forward_into); otherwise input must have exactly num_nodes rows, as in the reference
+  bool strided = false;   // input may be a view with unit inner stride (the entry point has checked it)
+  const torch::Tensor* workspace = nullptr;  // a caller-kept buffer, taken when it is large enough
+  size_t (*workspace_bytes)(const hcspmm_plan_header*, int) = hcspmm_workspace_bytes;  // nullptr: no workspace
+};
+
+// One call on a graph with or without a plan.  Owns N / E / D, the plan lookup (registry, graph fingerprint, the rows the plan
+// gathers), the workspace, the stream and the device guard, and spells the graph-and-plan arguments of the C ABI once:
+// graph() = (six graph arrays, plan, header, N, E, D), ws() = (workspace, workspace_bytes, stream).
+struct PlannedCall {
+  int64_t N, E;
+  int D;
+  bool has_plan;
+  hcspmm_plan_header header;
+  torch::Tensor workspace;
+  void* stream;
+
+  // The SpMM entry points: the reference's CHECK_INPUT run over the operands, then the lookup.  gathered: the matrix whose
+  // rows the column ids index (`input` in every message), or nullptr when nothing is gathered (only the graph is checked);
+  // like: the tensor that gives the width, the device and the stream (the input, or the edge features of a call without one)
+  PlannedCall(const torch::Tensor* gathered, const torch::Tensor& like, const torch::Tensor& nodePointer,
+              const torch::Tensor& edgeList, const torch::Tensor& blockPartition, const torch::Tensor& edgeToColumn,
+              const torch::Tensor& edgeToRow, const torch::Tensor& hybrid_type, const torch::Tensor& row_nzr,
+              const CallOptions& o = CallOptions()) {
+    if (gathered) {
+      const torch::Tensor& input = *gathered;
+      CHECK_CUDA(input);
+      if (!o.strided) CHECK_CONTIGUOUS(input);
+    }
+    CHECK_INPUT(nodePointer);
+    CHECK_INPUT(edgeList);
+    CHECK_INPUT(blockPartition);
+    CHECK_INPUT(edgeToColumn);
+    CHECK_INPUT(edgeToRow);
+    if (gathered) {
+      const auto st = gathered->scalar_type();
+      const bool fp8 = o.dtypes == CallOptions::kFp8, typed = o.dtypes == CallOptions::kTyped;
+      TORCH_CHECK(gathered->dim() == 2 && (fp8 ? st == torch::kFloat8_e4m3fn || st == torch::kByte
+                                               : typed ? feature_dtype(*gathered) >= 0 : st == torch::kFloat),
+                  fp8 ? "input must be a 2-D float8_e4m3fn (or uint8) tensor"
+                      : typed ? "input must be a 2-D float32 / float16 / bfloat16 tensor" : "input must be a 2-D float32 tensor");
+    }
+    check_i32_graph(nodePointer, edgeList);
+    N = nodePointer.size(0) - 1;  // reference :212-214
+    E = edgeList.size(0);
+    D = (int)like.size(1);
+    if (gathered)
+      TORCH_CHECK(o.rect || gathered->size(0) == N, "input has ", gathered->size(0), " rows but the graph has ", N, " nodes");
+    graph_[0] = iptr(nodePointer), graph_[1] = iptr(edgeList), graph_[2] = iptr(blockPartition);
+    graph_[3] = iptr(edgeToColumn), graph_[4] = iptr(edgeToRow), graph_[5] = iptr(hybrid_type);
+    bind(nodePointer, edgeList, row_nzr, gathered, "input", like, o);
+  }
+
+  // The SDDMM entry points, which check their operands themselves: gathered (named `name` in messages) is the matrix the
+  // column ids index
+  PlannedCall(const torch::Tensor& gathered, const char* name, const torch::Tensor& nodePointer, const torch::Tensor& edgeList,
+              const torch::Tensor& row_nzr, const CallOptions& o)
+      : N(nodePointer.size(0) - 1), E(edgeList.size(0)), D((int)gathered.size(1)) {
+    graph_[0] = iptr(nodePointer), graph_[1] = iptr(edgeList);
+    bind(nodePointer, edgeList, row_nzr, &gathered, name, gathered, o);
+  }
+
+  std::tuple<const int*, const hcspmm_plan_header*> plan() const {
+    return {has_plan ? plan_ : nullptr, has_plan ? &header : nullptr};
+  }
+  auto graph() const {
+    return std::tuple_cat(std::make_tuple(graph_[0], graph_[1], graph_[2], graph_[3], graph_[4], graph_[5]), plan(),
+                          std::make_tuple(N, E, D));
+  }
+  std::tuple<void*, size_t, void*> ws() const {
+    return {workspace.defined() ? workspace.data_ptr() : nullptr, workspace.defined() ? (size_t)workspace.nbytes() : 0, stream};
+  }
+
+ private:
+  void bind(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& row_nzr,
+            const torch::Tensor* gathered, const char* name, const torch::Tensor& like, const CallOptions& o) {
+    has_plan = lookup(row_nzr, nodePointer, edgeList, N, E, &header);
+    if (has_plan) {
+      plan_ = iptr(row_nzr);
+      if (gathered)
+        TORCH_CHECK(gathered->size(0) >= header.num_columns, name, " has ", gathered->size(0), " rows but the plan gathers from ",
+                    header.num_columns);
+      const size_t need = o.workspace_bytes ? o.workspace_bytes(&header, D) : 0;
+      if (need) {
+        if (o.workspace && o.workspace->defined() && o.workspace->is_cuda() && (size_t)o.workspace->nbytes() >= need)
+          workspace = *o.workspace;  // a caller-kept buffer: nothing is allocated in the step
+        else
+          workspace = torch::empty({(int64_t)(need / 4)}, like.options().dtype(torch::kFloat));
+      }
+    }
+    stream = current_stream(like);
+    guard_.emplace(like.device());
+  }
+
+  const int* graph_[6] = {};
+  const int* plan_ = nullptr;
+  c10::optional<c10::DeviceGuard> guard_;  // (set once the operands are known to be device tensors)
+};
+
+// the edge values of the weighted products: one float32 per stored entry, on the input's device
+void check_values(const torch::Tensor& values, int64_t E, const torch::Tensor& input) {
+  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
+  TORCH_CHECK(values.dim() == 1 && values.numel() == E, "values must hold one float32 per stored entry: ", E, ", got ",
+              values.sizes());
+  TORCH_CHECK(values.device() == input.device(), "values must be on the device of the input");
+}
 
 torch::Tensor run_spmm(const torch::Tensor& input, const torch::Tensor& nodePointer, const torch::Tensor& edgeList,
                        const torch::Tensor& blockPartition, const torch::Tensor& edgeToColumn,
                        const torch::Tensor& edgeToRow, const torch::Tensor& hybrid_type,
                        const torch::Tensor& row_nzr, bool rect = false) {
   // fp16 / bf16 features too (the paper's half-precision variants, Table VII): Z has the input's dtype
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true, rect);
+  CallOptions o(CallOptions::kTyped);
+  o.rect = rect;
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());  // reference K.cu:431-433
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_typed(
-      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  const int rc = invoke(hcspmm_forward_typed,
+                        std::make_tuple(input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input)), c.graph(),
+                        c.ws());
   check_rc(rc, "forward");
   return output;
 }
@@ -216,20 +292,14 @@ std::vector<torch::Tensor> spmm_forward_weighted(torch::Tensor input, torch::Ten
                                                  torch::Tensor edgeList, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
                                                  torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
                                                  torch::Tensor col_nzr) {
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, CallOptions::kTyped);
   CHECK_INPUT(values);
-  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
-  TORCH_CHECK(values.dim() == 1 && values.numel() == c.E, "values must hold one float32 per stored entry: ", c.E, ", got ",
-              values.sizes());
-  TORCH_CHECK(values.device() == input.device(), "values must be on the device of the input");
+  check_values(values, c.E, input);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
   auto vals = c.E > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_weighted(
-      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>());
+  const int rc = invoke(hcspmm_forward_weighted,
+                        std::make_tuple(input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input)), c.graph(),
+                        c.ws(), std::make_tuple(vals.data_ptr<float>()));
   check_rc(rc, "forward_weighted");
   return {output};
 }
@@ -257,7 +327,7 @@ std::vector<torch::Tensor> quantize_fp8(torch::Tensor input, c10::optional<torch
   const int rc = hcspmm_quantize_fp8(rows > 0 ? input.data_ptr<float>() : nullptr, rows, D, (int)D, HCSPMM_FP8_E4M3,
                                      scale.has_value() && rows > 0 ? scale->data_ptr<float>() : nullptr,
                                      rows > 0 ? codes.data_ptr() : nullptr, D, rows > 0 ? out.data_ptr<float>() : nullptr,
-                                     (void*)c10::hip::getCurrentHIPStream(input.device().index()).stream());
+                                     current_stream(input));
   check_rc(rc, "quantize_fp8");
   return {codes.view(torch::kFloat8_e4m3fn), out};
 }
@@ -267,25 +337,20 @@ torch::Tensor run_spmm_fp8(const torch::Tensor& input, const c10::optional<torch
                            const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                            const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow, const torch::Tensor& hybrid_type,
                            const torch::Tensor& row_nzr) {
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, false, false, nullptr, true);
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, CallOptions::kFp8);
   check_fp8_width(c.D);
   if (scale.has_value()) check_row_scale(*scale, input);
   if (values) {
     CHECK_INPUT((*values));
-    TORCH_CHECK(values->scalar_type() == torch::kFloat, "values must be a float32 tensor");
-    TORCH_CHECK(values->dim() == 1 && values->numel() == c.E, "values must hold one float32 per stored entry: ", c.E, ", got ",
-                values->sizes());
-    TORCH_CHECK(values->device() == input.device(), "values must be on the device of the input");
+    check_values(*values, c.E, input);
   }
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kFloat));
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_fp8(
-      c.N > 0 ? input.data_ptr() : nullptr, input.size(0), c.D, HCSPMM_FP8_E4M3,
-      scale.has_value() && scale->numel() > 0 ? scale->data_ptr<float>() : nullptr,
-      values && values->numel() > 0 ? values->data_ptr<float>() : nullptr, c.N > 0 ? output.data_ptr<float>() : nullptr, c.D,
-      iptr(nodePointer), iptr(edgeList), iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type),
-      c.has_plan ? iptr(row_nzr) : nullptr, c.has_plan ? &c.header : nullptr, c.N, c.E, c.D,
-      c.workspace.defined() ? c.workspace.data_ptr() : nullptr, c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  const int rc = invoke(hcspmm_forward_fp8,
+                        std::make_tuple(c.N > 0 ? input.data_ptr() : nullptr, input.size(0), c.D, HCSPMM_FP8_E4M3,
+                                        scale.has_value() && scale->numel() > 0 ? scale->data_ptr<float>() : nullptr,
+                                        values && values->numel() > 0 ? values->data_ptr<float>() : nullptr,
+                                        c.N > 0 ? output.data_ptr<float>() : nullptr, c.D),
+                        c.graph(), c.ws());
   check_rc(rc, "forward_fp8");
   return output;
 }
@@ -302,7 +367,7 @@ std::vector<torch::Tensor> spmm_forward_weighted_heads(torch::Tensor input, torc
                                                        torch::Tensor edgeList, torch::Tensor blockPartition,
                                                        torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
                                                        torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr) {
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, CallOptions::kTyped);
   CHECK_INPUT(values);
   TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
   TORCH_CHECK(values.dim() == 2 && values.size(1) == c.E && values.size(0) >= 1, "values must be [heads, E] with E = ", c.E,
@@ -312,12 +377,9 @@ std::vector<torch::Tensor> spmm_forward_weighted_heads(torch::Tensor input, torc
   check_heads_width(c.D, heads, input);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
   auto vals = c.E > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_weighted_heads(
-      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>(), (int)heads);
+  const int rc = invoke(hcspmm_forward_weighted_heads,
+                        std::make_tuple(input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input)), c.graph(),
+                        c.ws(), std::make_tuple(vals.data_ptr<float>(), (int)heads));
   check_rc(rc, "forward_weighted_heads");
   return {output};
 }
@@ -329,7 +391,7 @@ std::vector<torch::Tensor> spmm_forward_weighted_indexed(torch::Tensor input, to
                                                          torch::Tensor blockPartition, torch::Tensor edgeToColumn,
                                                          torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
                                                          torch::Tensor col_nzr) {
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true);
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, CallOptions::kTyped);
   CHECK_INPUT(values);
   CHECK_INPUT(value_index);
   TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
@@ -344,12 +406,9 @@ std::vector<torch::Tensor> spmm_forward_weighted_indexed(torch::Tensor input, to
   if (heads > 1) check_heads_width(c.D, heads, input);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
   auto vals = V > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_weighted_indexed(
-      input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input), iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, vals.data_ptr<float>(), (int)heads, iptr(value_index), V);
+  const int rc = invoke(hcspmm_forward_weighted_indexed,
+                        std::make_tuple(input.data_ptr(), input.size(0), c.D, output.data_ptr(), c.D, feature_dtype(input)), c.graph(),
+                        c.ws(), std::make_tuple(vals.data_ptr<float>(), (int)heads, iptr(value_index), V));
   check_rc(rc, "forward_weighted_indexed");
   return {output};
 }
@@ -363,20 +422,16 @@ std::vector<torch::Tensor> spmm_forward_extremum(torch::Tensor input, torch::Ten
   CHECK_CUDA(input);
   TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
               "input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)");
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, true, true);
-  if (c.has_plan) {  // values and positions of the split rows' partial slots
-    const size_t need = hcspmm_extremum_workspace_bytes(&c.header, c.D);
-    if (need) c.workspace = torch::empty({(int64_t)(need / 4)}, input.options());
-  }
+  CallOptions o;
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_extremum_workspace_bytes;  // values and positions of the split rows' partial slots
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
   torch::Tensor arg;
   if (return_arg) arg = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kInt));
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_extremum(
-      input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, HCSPMM_DTYPE_F32, iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream, reduce, return_arg ? mptr(arg) : nullptr, c.D);
+  const int rc = invoke(hcspmm_forward_extremum,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, HCSPMM_DTYPE_F32),
+                        c.graph(), c.ws(), std::make_tuple(reduce, return_arg ? mptr(arg) : nullptr, c.D));
   check_rc(rc, reduce == HCSPMM_REDUCE_MAX ? "forward_max" : "forward_min");
   if (return_arg) return {output, arg};
   return {output};
@@ -399,14 +454,11 @@ torch::Tensor spmm_forward_extremum_backward(torch::Tensor grad_Z, torch::Tensor
   TORCH_CHECK(perm.scalar_type() == torch::kInt && perm.dim() == 1 && perm.numel() == E, "perm must be an int32 [E] tensor with E = ",
               E, ", got ", perm.scalar_type(), " ", perm.sizes());
   TORCH_CHECK(arg.device() == grad_Z.device() && perm.device() == grad_Z.device(), "arg and perm must be on the device of grad_Z");
-  Call c = prepare(grad_Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr);
+  PlannedCall c(&grad_Z, grad_Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr);
   auto grad_X = torch::empty({N, D}, grad_Z.options());
-  const c10::DeviceGuard guard(grad_Z.device());
-  const int rc = hcspmm_forward_extremum_backward(
-      grad_Z.data_ptr<float>(), D, iptr(arg), D, grad_X.data_ptr<float>(), D, iptr(nodePointer), iptr(edgeList), iptr(blockPartition),
-      iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr, c.has_plan ? &c.header : nullptr,
-      c.N, c.E, c.D, iptr(perm), c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  const int rc = invoke(hcspmm_forward_extremum_backward,
+                        std::make_tuple(grad_Z.data_ptr<float>(), D, iptr(arg), D, grad_X.data_ptr<float>(), D), c.graph(),
+                        std::make_tuple(iptr(perm)), c.ws());
   check_rc(rc, "forward_extremum_backward");
   return grad_X;
 }
@@ -433,28 +485,16 @@ std::vector<torch::Tensor> spmm_forward_edge_messages(c10::optional<torch::Tenso
   check_f32_view(F, "F");
   TORCH_CHECK(input.has_value() || code == HCSPMM_EDGE_OP_COPY, "input may be None for op='copy' only");
   TORCH_CHECK(F.size(1) > 0, "F must have at least one column");
-  Call c;
   if (input.has_value()) {
     check_f32_view(*input, "input");
     TORCH_CHECK(input->size(1) == F.size(1) && input->device() == F.device(), "input and F must have the same width and device, got ",
                 input->sizes(), " and ", F.sizes());
-    c = prepare(*input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, false, true, true);
-  } else {  // no rows are gathered: the plan is checked against the graph alone
-    CHECK_INPUT(nodePointer);
-    CHECK_INPUT(edgeList);
-    CHECK_INPUT(blockPartition);
-    CHECK_INPUT(edgeToColumn);
-    CHECK_INPUT(edgeToRow);
-    TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt,
-                "nodePointer / edgeList must be int32");
-    c.N = nodePointer.size(0) - 1;
-    c.E = edgeList.size(0);
-    c.D = (int)F.size(1);
-    c.has_plan = lookup(row_nzr, nodePointer, edgeList, c.N, c.E, &c.header);
-    const size_t need = c.has_plan ? hcspmm_workspace_bytes(&c.header, c.D) : 0;
-    if (need) c.workspace = torch::empty({(int64_t)(need / 4)}, F.options());
-    c.stream = (void*)c10::hip::getCurrentHIPStream(F.device().index()).stream();
   }
+  CallOptions o;
+  o.rect = o.strided = true;
+  // (no input: no rows are gathered, and the plan is checked against the graph alone)
+  PlannedCall c(input.has_value() ? &*input : nullptr, F, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                row_nzr, o);
   if (index.has_value()) {
     CHECK_INPUT((*index));
     TORCH_CHECK(index->scalar_type() == torch::kInt && index->dim() == 1 && index->numel() == c.E && index->device() == F.device(),
@@ -464,14 +504,12 @@ std::vector<torch::Tensor> spmm_forward_edge_messages(c10::optional<torch::Tenso
     TORCH_CHECK(F.size(0) >= c.E, "F has ", F.size(0), " rows but the graph has ", c.E, " entries");
   }
   auto output = torch::empty({c.N, (int64_t)c.D}, F.options());
-  const c10::DeviceGuard guard(F.device());
-  const int rc = hcspmm_forward_edge_messages(
-      input.has_value() && input->numel() > 0 ? input->data_ptr() : nullptr, input.has_value() ? input->size(0) : 0,
-      input.has_value() ? input->stride(0) : c.D, F.numel() > 0 ? F.data_ptr<float>() : nullptr, F.size(0), F.stride(0),
-      index.has_value() ? iptr(*index) : nullptr, code, c.N > 0 ? output.data_ptr() : nullptr, c.D, iptr(nodePointer), iptr(edgeList),
-      iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  const int rc = invoke(hcspmm_forward_edge_messages,
+                        std::make_tuple(input.has_value() && input->numel() > 0 ? input->data_ptr() : nullptr,
+                                        input.has_value() ? input->size(0) : 0, input.has_value() ? input->stride(0) : c.D,
+                                        F.numel() > 0 ? F.data_ptr<float>() : nullptr, F.size(0), F.stride(0),
+                                        index.has_value() ? iptr(*index) : nullptr, code, c.N > 0 ? output.data_ptr() : nullptr, c.D),
+                        c.graph(), c.ws());
   check_rc(rc, "forward_edge_messages");
   return {output};
 }
@@ -481,7 +519,7 @@ torch::Tensor spmm_edge_messages_grad(torch::Tensor dZ, c10::optional<torch::Ten
   const int code = edge_op_code(op);
   CHECK_INPUT(nodePointer);
   CHECK_INPUT(edgeList);
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  check_i32_graph(nodePointer, edgeList);
   check_f32_view(dZ, "dZ");
   const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0), D = dZ.size(1);
   TORCH_CHECK(dZ.size(0) == N, "dZ has ", dZ.size(0), " rows but the graph has ", N, " nodes");
@@ -504,74 +542,53 @@ torch::Tensor spmm_edge_messages_grad(torch::Tensor dZ, c10::optional<torch::Ten
       dZ.numel() > 0 ? dZ.data_ptr<float>() : nullptr, dZ.stride(0), reads_x && input->numel() > 0 ? input->data_ptr<float>() : nullptr,
       reads_x ? input->size(0) : 0, reads_x ? input->stride(0) : D, reads_f && F->numel() > 0 ? F->data_ptr<float>() : nullptr,
       reads_f ? F->stride(0) : D, E > 0 ? out.data_ptr<float>() : nullptr, D, code, iptr(nodePointer), iptr(edgeList), N, E, (int)D,
-      (void*)c10::hip::getCurrentHIPStream(dZ.device().index()).stream());
+      current_stream(dZ));
   check_rc(rc, "edge_messages_grad");
   return out;
 }
 
-// Multi-head SDDMM (hcspmm_sddmm_heads): float32 [heads, E], out[h][e] = <A[row(e)][h-th Dh slice], B[col(e)][same slice]>
-torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
-                               torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
-                               torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr, int64_t heads) {
+// SDDMM (hcspmm_sddmm / hcspmm_sddmm_heads): A and B 2-D views with unit inner stride (column slices need no copy).
+// No heads: float32 [E], out[e] = <A[row(e)], B[col(e)]>; heads: float32 [heads, E], out[h][e] = <A[row(e)][h-th Dh slice],
+// B[col(e)][same slice]>
+torch::Tensor run_sddmm(const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor& nodePointer, const torch::Tensor& edgeList,
+                        const torch::Tensor& row_nzr, c10::optional<int64_t> heads) {
   CHECK_INPUT(nodePointer);
   CHECK_INPUT(edgeList);
   CHECK_CUDA(A);
   CHECK_CUDA(B);
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  check_i32_graph(nodePointer, edgeList);
   for (const torch::Tensor* t : {&A, &B})
     TORCH_CHECK(feature_dtype(*t) >= 0 && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
                 t == &A ? "A" : "B", " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
   TORCH_CHECK(B.scalar_type() == A.scalar_type(), "B must be a 2-D float32 / float16 / bfloat16 view with unit inner stride, of the "
               "dtype of A");
-  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0);
+  const int64_t N = nodePointer.size(0) - 1;
   TORCH_CHECK(A.size(0) == N, "A has ", A.size(0), " rows but the graph has ", N, " nodes");
   TORCH_CHECK(B.size(1) == A.size(1), "B has ", B.size(1), " columns but A has ", A.size(1));
   TORCH_CHECK(B.device() == A.device(), "B must be on the device of A");
-  check_heads_width(A.size(1), heads, A);
-  hcspmm_plan_header h;
-  const bool has_plan = lookup(row_nzr, nodePointer, edgeList, N, E, &h);
-  if (has_plan)
-    TORCH_CHECK(B.size(0) >= h.num_columns, "B has ", B.size(0), " rows but the plan gathers from ", h.num_columns);
-  auto out = torch::empty({heads, E}, A.options().dtype(torch::kFloat));
-  const c10::DeviceGuard guard(A.device());
-  check_rc(hcspmm_sddmm_heads(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
-                              E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList),
-                              has_plan ? iptr(row_nzr) : nullptr, has_plan ? &h : nullptr, N, E, (int)A.size(1),
-                              (void*)c10::hip::getCurrentHIPStream(A.device().index()).stream(), (int)heads),
-           "sddmm_heads");
+  if (heads) check_heads_width(A.size(1), *heads, A);
+  CallOptions o;
+  o.workspace_bytes = nullptr;
+  PlannedCall c(B, "B", nodePointer, edgeList, row_nzr, o);
+  auto out = heads ? torch::empty({*heads, c.E}, A.options().dtype(torch::kFloat)) : torch::empty({c.E}, A.options().dtype(torch::kFloat));
+  const auto operands = std::tuple_cat(std::make_tuple(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
+                                                       c.E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList)),
+                                       c.plan(), std::make_tuple(c.N, c.E, c.D, c.stream));
+  if (heads) check_rc(invoke(hcspmm_sddmm_heads, operands, std::make_tuple((int)*heads)), "sddmm_heads");
+  else check_rc(invoke(hcspmm_sddmm, operands), "sddmm");
   return out;
 }
 
-// SDDMM (hcspmm_sddmm): out[e] = <A[row(e)], B[col(e)]>, A and B 2-D views with unit inner stride (column slices need no copy)
+torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
+                               torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                               torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr, int64_t heads) {
+  return run_sddmm(A, B, nodePointer, edgeList, row_nzr, heads);
+}
+
 torch::Tensor spmm_sddmm(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
                          torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
                          torch::Tensor row_nzr, torch::Tensor col_nzr) {
-  CHECK_INPUT(nodePointer);
-  CHECK_INPUT(edgeList);
-  CHECK_CUDA(A);
-  CHECK_CUDA(B);
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
-  for (const torch::Tensor* t : {&A, &B})
-    TORCH_CHECK(feature_dtype(*t) >= 0 && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
-                t == &A ? "A" : "B", " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
-  TORCH_CHECK(B.scalar_type() == A.scalar_type(), "B must be a 2-D float32 / float16 / bfloat16 view with unit inner stride, of the "
-              "dtype of A");
-  const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0);
-  TORCH_CHECK(A.size(0) == N, "A has ", A.size(0), " rows but the graph has ", N, " nodes");
-  TORCH_CHECK(B.size(1) == A.size(1), "B has ", B.size(1), " columns but A has ", A.size(1));
-  TORCH_CHECK(B.device() == A.device(), "B must be on the device of A");
-  hcspmm_plan_header h;
-  const bool has_plan = lookup(row_nzr, nodePointer, edgeList, N, E, &h);
-  if (has_plan)
-    TORCH_CHECK(B.size(0) >= h.num_columns, "B has ", B.size(0), " rows but the plan gathers from ", h.num_columns);
-  auto out = torch::empty({E}, A.options().dtype(torch::kFloat));
-  const c10::DeviceGuard guard(A.device());
-  check_rc(hcspmm_sddmm(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
-                        E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList), has_plan ? iptr(row_nzr) : nullptr,
-                        has_plan ? &h : nullptr, N, E, (int)A.size(1),
-                        (void*)c10::hip::getCurrentHIPStream(A.device().index()).stream()),
-           "sddmm");
-  return out;
+  return run_sddmm(A, B, nodePointer, edgeList, row_nzr, c10::nullopt);
 }
 
 // the [E] or [heads, E] fp32 operands of the edge softmax -> heads
@@ -593,7 +610,7 @@ torch::Tensor edge_softmax(torch::Tensor logits, torch::Tensor nodePointer) {
   const c10::DeviceGuard guard(logits.device());
   check_rc(hcspmm_edge_softmax(logits.numel() ? logits.data_ptr<float>() : nullptr, alpha.numel() ? alpha.data_ptr<float>() : nullptr,
                                iptr(nodePointer), nodePointer.numel() - 1, E, (int)heads,
-                               (void*)c10::hip::getCurrentHIPStream(logits.device().index()).stream()),
+                               current_stream(logits)),
            "edge_softmax");
   return alpha;
 }
@@ -610,7 +627,7 @@ torch::Tensor edge_softmax_backward(torch::Tensor alpha, torch::Tensor grad_alph
   const bool any = alpha.numel() > 0;
   check_rc(hcspmm_edge_softmax_backward(any ? alpha.data_ptr<float>() : nullptr, any ? grad_alpha.data_ptr<float>() : nullptr,
                                         any ? grad.data_ptr<float>() : nullptr, iptr(nodePointer), nodePointer.numel() - 1, E,
-                                        (int)heads, (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
+                                        (int)heads, current_stream(alpha)),
            "edge_softmax_backward");
   return grad;
 }
@@ -628,7 +645,7 @@ int64_t gat_scores(const torch::Tensor& t, const char* name, const torch::Tensor
 int64_t gat_graph(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& s_dst, const torch::Tensor& s_src) {
   CHECK_INPUT(nodePointer);
   CHECK_INPUT(edgeList);
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  check_i32_graph(nodePointer, edgeList);
   const int64_t heads = gat_scores(s_dst, "s_dst", nodePointer);
   TORCH_CHECK(s_dst.dim() == s_src.dim() && gat_scores(s_src, "s_src", nodePointer) == heads,
               "s_dst and s_src must have the same number of heads, got ", s_dst.sizes(), " and ", s_src.sizes());
@@ -648,7 +665,7 @@ torch::Tensor gat_attention(torch::Tensor s_dst, torch::Tensor s_src, torch::Ten
   const c10::DeviceGuard guard(s_dst.device());
   check_rc(hcspmm_gat_attention(fptr(s_dst), fptr(s_src), s_src.size(0), (float)negative_slope, mfptr(alpha), iptr(nodePointer),
                                 E ? iptr(edgeList) : nullptr, N, E, (int)heads,
-                                (void*)c10::hip::getCurrentHIPStream(s_dst.device().index()).stream()),
+                                current_stream(s_dst)),
            "gat_attention");
   return alpha;
 }
@@ -684,21 +701,18 @@ std::vector<torch::Tensor> gat_attention_backward_any(torch::Tensor alpha, torch
   auto grad_s_dst = torch::empty_like(s_dst), grad_s_src = torch::empty_like(s_src);
   auto grad_scores = torch::empty(shape, alpha.options());
   const c10::DeviceGuard guard(alpha.device());
+  const auto operands = std::make_tuple(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
+                                        iptr(nodePointer), E ? iptr(edgeList) : nullptr);
+  const auto outputs = std::make_tuple(E, (int)heads, mfptr(grad_scores), mfptr(grad_s_dst), mfptr(grad_s_src), current_stream(alpha));
   if (rp_t.defined()) {
     check_transposed(rp_t, "row_pointers_t", N + 1, nodePointer);
-    check_rc(hcspmm_gat_attention_backward_directed(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
-                                                    iptr(nodePointer), E ? iptr(edgeList) : nullptr, iptr(rp_t),
-                                                    E ? iptr(perm32) : nullptr, N, N, E, (int)heads, mfptr(grad_scores),
-                                                    mfptr(grad_s_dst), mfptr(grad_s_src),
-                                                    (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
+    check_rc(invoke(hcspmm_gat_attention_backward_directed, operands,
+                    std::make_tuple(iptr(rp_t), E ? iptr(perm32) : nullptr, N, N), outputs),
              "gat_attention_backward_directed");
-    return {grad_s_dst, grad_s_src, grad_scores};
+  } else {
+    check_rc(invoke(hcspmm_gat_attention_backward, operands, std::make_tuple(E ? iptr(perm32) : nullptr, N), outputs),
+             "gat_attention_backward");
   }
-  check_rc(hcspmm_gat_attention_backward(fptr(alpha), fptr(grad_alpha), fptr(s_dst), fptr(s_src), (float)negative_slope,
-                                         iptr(nodePointer), E ? iptr(edgeList) : nullptr, E ? iptr(perm32) : nullptr, N, E, (int)heads,
-                                         mfptr(grad_scores), mfptr(grad_s_dst), mfptr(grad_s_src),
-                                         (void*)c10::hip::getCurrentHIPStream(alpha.device().index()).stream()),
-           "gat_attention_backward");
   return {grad_s_dst, grad_s_src, grad_scores};
 }
 
@@ -714,7 +728,7 @@ int64_t gatv2_operands(const torch::Tensor& H_dst, const torch::Tensor& H_src, c
                        const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
   CHECK_INPUT(nodePointer);
   CHECK_INPUT(edgeList);
-  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt && edgeList.scalar_type() == torch::kInt, "nodePointer / edgeList must be int32");
+  check_i32_graph(nodePointer, edgeList);
   for (const torch::Tensor* t : {&H_dst, &H_src}) {
     const char* name = t == &H_dst ? "H_dst" : "H_src";
     TORCH_CHECK(t->is_cuda(), name, " must be a CUDA tensor");
@@ -742,7 +756,7 @@ torch::Tensor gatv2_scores(torch::Tensor H_dst, torch::Tensor H_src, torch::Tens
   const c10::DeviceGuard guard(H_dst.device());
   check_rc(hcspmm_gatv2_scores(fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.size(0), H_src.stride(0), fptr(att),
                                (float)negative_slope, mfptr(out), iptr(nodePointer), iptr(edgeList), N, E, (int)D, (int)heads,
-                               (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
+                               current_stream(H_dst)),
            "gatv2_scores");
   return out;
 }
@@ -773,22 +787,19 @@ std::vector<torch::Tensor> gatv2_scores_backward_any(torch::Tensor grad_logits, 
   const size_t ws_bytes = hcspmm_gatv2_backward_workspace_bytes(N, E, (int)D, (int)heads);
   auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, att.options());
   const c10::DeviceGuard guard(H_dst.device());
+  const auto operands = std::make_tuple(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0), fptr(att),
+                                        (float)negative_slope, iptr(nodePointer), iptr(edgeList));
+  const auto outputs = std::make_tuple(E, (int)D, (int)heads, mfptr(grad_dst), D, mfptr(grad_src), D, mfptr(grad_att),
+                                       (void*)mfptr(ws), ws_bytes, current_stream(H_dst));
   if (rp_t.defined()) {
     check_transposed(rp_t, "row_pointers_t", N + 1, nodePointer);
     check_transposed(col_t, "column_index_t", E, nodePointer);
-    check_rc(hcspmm_gatv2_scores_backward_directed(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0),
-                                                   fptr(att), (float)negative_slope, iptr(nodePointer), iptr(edgeList), iptr(rp_t),
-                                                   iptr(col_t), iptr(perm32), N, N, E, (int)D, (int)heads, mfptr(grad_dst), D,
-                                                   mfptr(grad_src), D, mfptr(grad_att), mfptr(ws), ws_bytes,
-                                                   (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
+    check_rc(invoke(hcspmm_gatv2_scores_backward_directed, operands,
+                    std::make_tuple(iptr(rp_t), iptr(col_t), iptr(perm32), N, N), outputs),
              "gatv2_scores_backward_directed");
-    return {grad_dst, grad_src, grad_att};
+  } else {
+    check_rc(invoke(hcspmm_gatv2_scores_backward, operands, std::make_tuple(iptr(perm32), N), outputs), "gatv2_scores_backward");
   }
-  check_rc(hcspmm_gatv2_scores_backward(fptr(grad_logits), fptr(H_dst), H_dst.stride(0), fptr(H_src), H_src.stride(0), fptr(att),
-                                        (float)negative_slope, iptr(nodePointer), iptr(edgeList), iptr(perm32), N, E, (int)D,
-                                        (int)heads, mfptr(grad_dst), D, mfptr(grad_src), D, mfptr(grad_att), mfptr(ws), ws_bytes,
-                                        (void*)c10::hip::getCurrentHIPStream(H_dst.device().index()).stream()),
-           "gatv2_scores_backward");
   return {grad_dst, grad_src, grad_att};
 }
 
@@ -804,7 +815,7 @@ std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Te
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
                                      const torch::Tensor& hybrid_type, const torch::Tensor& row_nzr,
                                      const torch::Tensor& weights, torch::Tensor output) {
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr);
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr);
   // The reference takes weights.data<float>() without CHECK_INPUT and therefore multiplies a
   // transposed view by its raw storage; here the view's strides are honoured.
   TORCH_CHECK(weights.is_cuda() && weights.scalar_type() == torch::kFloat && weights.dim() == 2 &&
@@ -819,13 +830,10 @@ std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Te
                 "output must be float32 with num_nodes*hidden_dim elements");
   }
   auto output2 = torch::empty({c.N, (int64_t)c.D}, input.options());
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_fused(
-      input.data_ptr<float>(), output.data_ptr<float>(), output2.data_ptr<float>(), weights.data_ptr<float>(),
-      weights.stride(0), weights.stride(1), H, iptr(nodePointer), iptr(edgeList), iptr(blockPartition),
-      iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type), c.has_plan ? iptr(row_nzr) : nullptr,
-      c.has_plan ? &c.header : nullptr, c.N, c.E, c.D, c.workspace.defined() ? c.workspace.data_ptr() : nullptr,
-      c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0, c.stream);
+  const int rc = invoke(hcspmm_forward_fused,
+                        std::make_tuple(input.data_ptr<float>(), output.data_ptr<float>(), output2.data_ptr<float>(),
+                                        weights.data_ptr<float>(), weights.stride(0), weights.stride(1), H),
+                        c.graph(), c.ws());
   check_rc(rc, "forward_fused");
   return {output, output2};
 }
@@ -940,16 +948,15 @@ torch::Tensor spmm_forward_into(torch::Tensor input, torch::Tensor output, torch
                     t->stride(1) == 1 && t->stride(0) >= t->size(1),
                 t == &input ? "input" : "output", " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
   }
-  torch::Tensor ws = workspace.has_value() ? *workspace : torch::Tensor();
-  Call c = prepare(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_nzr, true, true, true, &ws);
+  CallOptions o(CallOptions::kTyped);
+  o.rect = o.strided = true;
+  if (workspace.has_value()) o.workspace = &*workspace;
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
   TORCH_CHECK(output.size(0) == c.N && output.size(1) == c.D, "output must be [num_nodes, embedding_dim]");
-  const c10::DeviceGuard guard(input.device());
-  const int rc = hcspmm_forward_typed(
-      input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), output.stride(0), feature_dtype(input),
-      iptr(nodePointer), iptr(edgeList), iptr(blockPartition), iptr(edgeToColumn), iptr(edgeToRow), iptr(hybrid_type),
-      c.has_plan ? iptr(row_nzr) : nullptr, c.has_plan ? &c.header : nullptr, c.N, c.E, c.D,
-      c.workspace.defined() ? c.workspace.data_ptr() : nullptr, c.workspace.defined() ? (size_t)c.workspace.nbytes() : 0,
-      c.stream);
+  const int rc = invoke(hcspmm_forward_typed,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), output.stride(0),
+                                        feature_dtype(input)),
+                        c.graph(), c.ws());
   check_rc(rc, "forward_into");
   return output;
 }
@@ -1016,13 +1023,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("slice_threshold") = 0, pybind11::arg("n_slices") = 0, pybind11::arg("panel_cols") = 0);
   m.def("wide_threshold", [](torch::Tensor row_nzr, int embedding_dim, int dtype) {
     hcspmm_plan_header h;
-    bool has = false;
-    if (row_nzr.defined() && row_nzr.numel() >= HCSPMM_PLAN_HEADER_WORDS && row_nzr.scalar_type() == torch::kInt) {
-      auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
-      std::memcpy(&h, host.data_ptr<int>(), sizeof(h));
-      has = h.magic == HCSPMM_PLAN_MAGIC;
-    }
-    return (int64_t)hcspmm_wide_threshold_typed(has ? &h : nullptr, embedding_dim, dtype);
+    return (int64_t)hcspmm_wide_threshold_typed(read_plan_header(row_nzr, &h) ? &h : nullptr, embedding_dim, dtype);
   }, "rows with more entries than this are summed by a whole wave (hcspmm.h hcspmm_wide_threshold_typed)",
         pybind11::arg("row_nzr"), pybind11::arg("embedding_dim"), pybind11::arg("dtype") = 0);
   m.def("set_rule", [](int rule) {
@@ -1045,10 +1046,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("slice_threshold") = 0, pybind11::arg("n_slices") = 0, pybind11::arg("panel_cols") = 0);
   m.def("fused_in_launch", [](torch::Tensor row_nzr, int embedding_dim, int hidden_dim) {
     hcspmm_plan_header h;
-    if (!row_nzr.defined() || row_nzr.numel() < HCSPMM_PLAN_HEADER_WORDS || row_nzr.scalar_type() != torch::kInt) return 0;
-    auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
-    std::memcpy(&h, host.data_ptr<int>(), sizeof(h));
-    return h.magic == HCSPMM_PLAN_MAGIC ? hcspmm_fused_in_launch(&h, embedding_dim, hidden_dim) : 0;
+    return read_plan_header(row_nzr, &h) ? hcspmm_fused_in_launch(&h, embedding_dim, hidden_dim) : 0;
   }, "form forward_*_fused takes with this plan and shape: 0 = two launches, 1 = dense-tile windows update inside the hybrid "
      "launch, 2 = the sparse-row path as well (row-tile form)");
   m.def("forward_weighted", &spmm_forward_weighted, "edge-weighted aggregation [A_w * X] (gfx950)");
@@ -1071,26 +1069,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "edge-weighted aggregation of 8-bit features: float32 [A_w * (scale[:, None] * Xq)] (gfx950)");
   m.def("wide_threshold_fp8", [](torch::Tensor row_nzr, int embedding_dim) {
     hcspmm_plan_header h;
-    bool has = false;
-    if (row_nzr.defined() && row_nzr.numel() >= HCSPMM_PLAN_HEADER_WORDS && row_nzr.scalar_type() == torch::kInt) {
-      auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
-      std::memcpy(&h, host.data_ptr<int>(), sizeof(h));
-      has = h.magic == HCSPMM_PLAN_MAGIC;
-    }
-    return (int64_t)hcspmm_wide_threshold_fp8(has ? &h : nullptr, embedding_dim);
+    return (int64_t)hcspmm_wide_threshold_fp8(read_plan_header(row_nzr, &h) ? &h : nullptr, embedding_dim);
   }, "wide_threshold for forward_fp8 / forward_weighted_fp8 (hcspmm.h hcspmm_wide_threshold_fp8)");
   m.def("edge_norm", [](torch::Tensor row_pointers, torch::Tensor column_index, std::string kind) {
     TORCH_CHECK(kind == "sym" || kind == "mean", "kind must be 'sym' or 'mean', got '", kind, "'");
     CHECK_INPUT(row_pointers);
     CHECK_INPUT(column_index);
-    TORCH_CHECK(row_pointers.scalar_type() == torch::kInt && column_index.scalar_type() == torch::kInt,
-                "nodePointer / edgeList must be int32");
+    check_i32_graph(row_pointers, column_index);
     const int64_t N = row_pointers.numel() - 1, E = column_index.numel();
     auto out = torch::empty({E}, row_pointers.options().dtype(torch::kFloat));
     const c10::DeviceGuard guard(row_pointers.device());
     check_rc(hcspmm_edge_norm_device(iptr(row_pointers), iptr(column_index), N, E, kind == "sym" ? HCSPMM_NORM_SYM : HCSPMM_NORM_MEAN,
                                      E ? out.data_ptr<float>() : nullptr,
-                                     (void*)c10::hip::getCurrentHIPStream(row_pointers.device().index()).stream()),
+                                     current_stream(row_pointers)),
              "edge_norm");
     return out;
   }, "edge values of the 'sym' (1/sqrt(deg_r deg_c)) or 'mean' (1/deg_r) normalisation, on the device");
@@ -1258,7 +1249,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto out = torch::empty({X.size(0), W.size(1)}, X.options());
     const c10::DeviceGuard guard(X.device());
     check_rc(hcspmm_dense_update(X.data_ptr<float>(), W.data_ptr<float>(), W.stride(0), W.stride(1), out.data_ptr<float>(), X.size(0),
-                                 (int)X.size(1), (int)W.size(1), (void*)c10::hip::getCurrentHIPStream(X.device().index()).stream()),
+                                 (int)X.size(1), (int)W.size(1), current_stream(X)),
              "update");
     return out;
   }, "X * W (the layers' update GEMM; W may be a transposed view); None if the operands are not contiguous fp32 device matrices");
@@ -1277,17 +1268,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto out = torch::empty({(int64_t)D, (int64_t)H}, A.options());
     const c10::DeviceGuard guard(A.device());
     check_rc(hcspmm_weight_grad(A.data_ptr<float>(), A.stride(0), B.data_ptr<float>(), B.stride(0), out.data_ptr<float>(), N,
-                                D, H, ws.data_ptr(), need, (void*)c10::hip::getCurrentHIPStream(A.device().index()).stream()),
+                                D, H, ws.data_ptr(), need, current_stream(A)),
              "weight_grad");
     return out;
   }, "dW = A^T B for the layers' backward passes (split-K MFMA kernel); None if the shape is unsupported");
   m.def("plan_info", [](torch::Tensor row_nzr) {
     pybind11::dict d;
     hcspmm_plan_header h;
-    if (!row_nzr.defined() || row_nzr.numel() < HCSPMM_PLAN_HEADER_WORDS || row_nzr.scalar_type() != torch::kInt) return d;
-    auto host = row_nzr.slice(0, 0, HCSPMM_PLAN_HEADER_WORDS).cpu().contiguous();
-    std::memcpy(&h, host.data_ptr<int>(), sizeof(h));
-    if (h.magic != HCSPMM_PLAN_MAGIC) return d;
+    if (!read_plan_header(row_nzr, &h)) return d;
     d["n_tasks"] = h.n_tasks; d["n_dense"] = h.n_dense; d["n_split_rows"] = h.n_split_rows;
     d["n_partials"] = h.n_partials; d["nnz_sparse"] = h.nnz_sparse; d["nnz_dense"] = h.nnz_dense;
     d["uniq_dense"] = h.uniq_dense; d["split_threshold"] = h.split_threshold; d["segment_len"] = h.segment_len;

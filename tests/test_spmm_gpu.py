@@ -686,6 +686,31 @@ def test_error_behaviour(oracle_mod, dev, fe):
     assert torch.equal(Zt, Z)
 
 
+def test_int64_csr_is_refused(dev, fe):
+    """The kernels read row_pointers / column_index as int32: another dtype is an argument error with one text in both
+    front-ends, raised before anything is enqueued (an 8-node ring, D = 4; with and without a plan)."""
+    N, D = 8, 4
+    rp = np.arange(N + 1, dtype=np.int32) * 2
+    col = np.stack([(np.arange(N) + N - 1) % N, (np.arange(N) + 1) % N], axis=1).astype(np.int32).reshape(-1)
+    X = torch.ones(N, D, device=dev)
+    for plan in (True, False):
+        g = Graph(rp, col, dev, fe=fe, plan=plan)
+        tail = g.args()[2:]
+        for bad in ((g.rp_d.long(), g.col_d), (g.rp_d, g.col_d.long())):
+            calls = [lambda: fe.forward(X, *bad, *tail),
+                     lambda: fe.forward_into(X, torch.empty_like(X), *bad, *tail),
+                     lambda: fe.forward_weighted(X, torch.ones(g.E, device=dev), *bad, *tail),
+                     lambda: fe.forward_max(X, *bad, *tail),
+                     lambda: fe.forward_fp8(torch.zeros(N, D, dtype=torch.uint8, device=dev), None, *bad, *tail),
+                     lambda: fe.forward_edge_messages(X, torch.ones(g.E, D, device=dev), *bad, *tail),
+                     lambda: fe.sddmm(X, X, *bad, *tail),
+                     lambda: fe.edge_norm(*bad, "sym")]
+            for call in calls:
+                with pytest.raises(RuntimeError, match="nodePointer / edgeList must be int32"):
+                    call()
+    assert torch.equal(fe.forward(X, *g.args())[0], torch.full((N, D), 2.0, device=dev))  # (the int32 arrays still pass)
+
+
 def test_reddit_scale_properties(oracle_mod, dev):
     """BASELINE config 3 at full size (233K nodes / 11.6M entries, D = 128): too big for the scalar
     oracle to be quick, so parity is checked through size-independent properties -- exact integer
