@@ -845,6 +845,132 @@ class SAGEConv(torch.nn.Module):
         return _Update.apply(X, self.weights_root) + _Update.apply(agg, self.weights_neigh)
 
 
+class MultiAggregate(torch.autograd.Function):
+    """Sum, sum of squares, max and min of each row's neighbour features from ONE gather pass (HCSPMM.forward_multi) ->
+    (Z_sum, Z_sumsq, Z_max, Z_min), with the gradient for X composed from existing launches on the graph the backward walks:
+      dX = A^T [g_sum | g_sumsq] (one binary HCSPMM.forward over both, 2 D wide), the second half times 2 X,
+         + HCSPMM.forward_extremum_backward(g_max, arg_max) + HCSPMM.forward_extremum_backward(g_min, arg_min).
+    tail = the eight graph tensors of A, the eight of the graph the backward walks (A itself when the pattern is symmetric, else
+    transposed_graph's) and the int32 index of its entries into A's (the transpose permutation, or entry_index_t)."""
+
+    @staticmethod
+    def forward(ctx, X, *tail):
+        X = X.contiguous()
+        z_sum, z_sumsq, z_max, z_min, arg_max, arg_min = HCSPMM.forward_multi(X, *tail[:N_GRAPH])
+        ctx.save_for_backward(X, arg_max, arg_min, *tail[N_GRAPH:])
+        ctx.set_materialize_grads(False)  # an aggregate the layer does not use costs no launch in the backward
+        return z_sum, z_sumsq, z_max, z_min
+
+    @staticmethod
+    def backward(ctx, g_sum, g_sumsq, g_max, g_min):
+        X, arg_max, arg_min, *rest = ctx.saved_tensors
+        graph_b, index = rest[:N_GRAPH], rest[N_GRAPH]
+        if not ctx.needs_input_grad[0]:
+            return (None,) * (2 * N_GRAPH + 2)
+        D = X.size(1)
+        d_x = None
+        if g_sum is not None and g_sumsq is not None:
+            t = HCSPMM.forward(torch.cat((g_sum, g_sumsq), 1), *graph_b)[0]
+            d_x = t[:, :D] + 2.0 * X * t[:, D:]
+        elif g_sum is not None:
+            d_x = HCSPMM.forward(g_sum.contiguous(), *graph_b)[0]
+        elif g_sumsq is not None:
+            d_x = 2.0 * X * HCSPMM.forward(g_sumsq.contiguous(), *graph_b)[0]
+        for g, arg in ((g_max, arg_max), (g_min, arg_min)):
+            if g is not None:
+                d = HCSPMM.forward_extremum_backward(g.contiguous(), arg, index, *graph_b)
+                d_x = d if d_x is None else d_x + d
+        if d_x is None:
+            d_x = torch.zeros_like(X)
+        return (d_x,) + (None,) * (2 * N_GRAPH + 1)
+
+
+def multi_aggregate(X, graph, directed=False):
+    """(sum, sum of squares, max, min) over each row's neighbours from one gather pass, with autograd for X (float32 [N, D]);
+    graph = the eight graph tensors, whose pattern must be symmetric (checked before any launch: the backward walks A^T)
+    unless directed=True: the backward then runs on transposed_graph(graph).  Rows without entries give 0 in all four."""
+    if directed:
+        return MultiAggregate.apply(X, *graph, *transposed_graph(graph))
+    perm32 = transpose_permutation_i32(graph[0], graph[1])
+    return MultiAggregate.apply(X, *graph, *graph, perm32)
+
+
+class PNAConv(torch.nn.Module):
+    """Principal neighbourhood aggregation:  out = X W_root + S W_neigh, S = the concatenation over scalers (outer) and
+    aggregators (inner) of scaler(deg) * aggregator(neighbours), all aggregators from one multi_aggregate pass.  With
+    deg = clamp(row length, 1):  mean = sum / deg;  std = sqrt(relu(sumsq / deg - mean^2) + 1e-5) (PyG's formula);  max, min.
+    Scalers: identity, amplification log(deg + 1) / delta, attenuation delta / log(deg + 1), delta =
+    avg_log_deg or, when that is None, the mean of log(deg + 1) over the graph, computed once per row_pointers tensor and kept
+    on the device (no host synchronisation, so the layer captures into a HIP graph without a warm-up).  Both products run on
+    _Update.  _Conv's call signature, so that Net builds it; edge_weight is refused.  The pattern must be
+    symmetric unless directed=True (the backward then runs on transposed_graph)."""
+
+    AGGREGATORS = ("mean", "min", "max", "std")
+    SCALERS = ("identity", "amplification", "attenuation")
+
+    def __init__(self, input_dim, output_dim, aggregators=("mean", "min", "max", "std"),
+                 scalers=("identity", "amplification", "attenuation"), avg_log_deg=None, directed=False):
+        super().__init__()
+        aggregators, scalers = tuple(aggregators), tuple(scalers)
+        for names, known, what in ((aggregators, self.AGGREGATORS, "aggregators"), (scalers, self.SCALERS, "scalers")):
+            if not names or any(n not in known for n in names):
+                raise ValueError("PNAConv %s must be among %s, got %r" % (what, ", ".join(repr(k) for k in known), names))
+        self.directed = bool(directed)
+        self.aggregators, self.scalers = aggregators, scalers
+        self.avg_log_deg = None if avg_log_deg is None else float(avg_log_deg)
+        self.weights_root = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self.weights_neigh = torch.nn.Parameter(torch.empty(len(scalers) * len(aggregators) * input_dim, output_dim))
+        self._degrees = None  # (row_pointers, deg [N, 1], log(deg + 1) [N, 1], delta) of the last graph
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.weights_root.size(1))
+        for p in (self.weights_root, self.weights_neigh):
+            p.data.uniform_(-stdv, stdv)
+
+    def degree_terms(self, row_pointers):
+        """(deg, log(deg + 1), delta) of a graph: float32 [N, 1], [N, 1] and avg_log_deg or a 0-dim tensor on the graph's device,
+        cached per row_pointers tensor"""
+        m = self._degrees
+        if m is None or m[0] is not row_pointers:
+            deg = (row_pointers[1:] - row_pointers[:-1]).clamp(min=1).to(torch.float32).unsqueeze(1)
+            log_deg = torch.log(deg + 1.0)
+            delta = self.avg_log_deg if self.avg_log_deg is not None else log_deg.mean()
+            self._degrees = m = (row_pointers, deg, log_deg, delta)
+        return m[1:]
+
+    def scaled_aggregates(self, z_sum, z_sumsq, z_max, z_min, row_pointers):
+        """S [N, scalers x aggregators x D] from the four aggregates of multi_aggregate"""
+        deg, log_deg, delta = self.degree_terms(row_pointers)
+        mean = z_sum / deg
+        parts = []
+        for a in self.aggregators:
+            if a == "mean":
+                parts.append(mean)
+            elif a == "std":
+                parts.append(torch.sqrt(torch.relu(z_sumsq / deg - mean * mean) + 1e-5))
+            else:
+                parts.append(z_min if a == "min" else z_max)
+        agg = torch.cat(parts, 1)
+        scaled = []
+        for s in self.scalers:
+            if s == "identity":
+                scaled.append(agg)
+            elif s == "amplification":
+                scaled.append(agg * (log_deg / delta))
+            else:
+                scaled.append(agg * (delta / log_deg))
+        return torch.cat(scaled, 1) if len(scaled) > 1 else scaled[0]
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("PNAConv aggregates with its own aggregators: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        S = self.scaled_aggregates(*multi_aggregate(X, graph, self.directed), row_pointers)
+        return _Update.apply(X, self.weights_root) + _Update.apply(S, self.weights_neigh)
+
+
 class EdgeMessageAggregate(torch.autograd.Function):
     """Z[i] = sum over the entries e = (i, j) of m(X[j], F[e]) (HCSPMM.forward_edge_messages; op "mul" x * f, "add_relu"
     relu(x + f), "copy" f) with gradients for X and F [E, D].  dF is HCSPMM.edge_messages_grad; dX is the same forward on A^T:

@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, SAGEConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, PNAConv, SAGEConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage", "pna"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -59,7 +59,7 @@ def parse_args(argv=None):
     p.add_argument("--heads", type=int, default=1, help="attention heads (--model gat / gatv2)")
     # addition: the first and hidden GAT layers concatenate their heads (hidden / heads features each), the last averages
     # addition: neighbour aggregation of --model sage (GNN_model.SAGEConv: out = X W_root + AGG(X) W_neigh)
-    p.add_argument("--aggr", type=str, default="max", choices=["max", "min", "mean"], help="aggregation of --model sage")
+    p.add_argument("--aggr", type=str, default=None, choices=["max", "min", "mean"], help="aggregation of --model sage (default max)")
     p.add_argument("--gat-concat", action="store_true",
                    help="--model gat / gatv2: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
@@ -72,6 +72,12 @@ def parse_args(argv=None):
     # of them per stored entry are drawn once from a seeded generator
     p.add_argument("--edge-dim", type=int, default=8, help="edge attributes per entry (--model gine; synthesised, seeded)")
     args = p.parse_args(argv)
+    # addition: --model pna (GNN_model.PNAConv: mean / min / max / std of the neighbours from one gather pass, times degree scalers);
+    # its aggregators are the layer's own, so --aggr is refused
+    if args.model == "pna" and args.aggr is not None:
+        p.error("--aggr does not apply to --model pna: PNAConv combines mean, min, max and std")
+    if args.aggr is None:
+        args.aggr = "max"
     if args.edge_dim < 1:
         p.error("--edge-dim must be at least 1")
     if args.model == "gine" and args.norm != "none":
@@ -89,6 +95,8 @@ def parse_args(argv=None):
         p.error("--norm does not apply to --model %s: its edge values are the attention weights" % args.model)
     if args.model == "sage" and args.norm != "none":
         p.error("--norm does not apply to --model sage: its aggregation is --aggr")
+    if args.model == "pna" and args.norm != "none":
+        p.error("--norm does not apply to --model pna: its aggregators and degree scalers are the layer's own")
     if args.heads < 1:
         p.error("--heads must be at least 1")
     if args.gat_concat and args.model not in ("gat", "gatv2"):
@@ -204,6 +212,11 @@ def main(argv=None):
     if args.model == "sage":
         def conv_cls(input_dim, output_dim, fixed):
             return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed)
+    if args.model == "pna":
+        def conv_cls(input_dim, output_dim, fixed):
+            if fixed == 2:  # the last layer, as for sage
+                return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed)
+            return PNAConv(input_dim, output_dim, directed=directed)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated

@@ -520,6 +520,45 @@ extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg
                        HCSPMM_REDUCE_MAX, nullptr, arg, ldarg, transpose_perm);
 }
 
+extern "C" size_t hcspmm_multi_workspace_bytes(const hcspmm_plan_header* ph, int D) { return 6 * hcspmm_workspace_bytes(ph, D); }
+
+// Sum, sum of squares, max and min in one gather pass (spmm_multi.hip): the plan and checks of hcspmm_forward_extremum, six
+// nullable outputs.
+extern "C" int hcspmm_forward_multi(const void* X, int64_t x_rows, int64_t ldx, int dtype, float* Z_sum, float* Z_sumsq, float* Z_max,
+                                    float* Z_min, int64_t ldz, int32_t* arg_max, int32_t* arg_min, int64_t ldarg,
+                                    const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                    const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                    const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
+                                    size_t workspace_bytes, void* stream_v) {
+  if (dtype != HCSPMM_DTYPE_F32) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
+  if (!Z_sum && !Z_sumsq && !Z_max && !Z_min) return HCSPMM_EINVAL;
+  if ((arg_max || arg_min) && ldarg < D) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::MArgs m{};
+  // workspace: six areas of hcspmm_workspace_bytes each -- sum, sum of squares, max, its position, min, its position
+  const int rc = bind_graph(m.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 6, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (m.p.plan) {
+    m.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+    m.segment_len = ph->segment_len;
+  }
+  set_operands(m.p, X, nullptr, ldx, ldz);
+  m.rowptr = rowptr;
+  m.zsum = Z_sum;
+  m.zsumsq = Z_sumsq;
+  m.zmax = Z_max;
+  m.zmin = Z_min;
+  m.amax = arg_max;
+  m.amin = arg_min;
+  m.ldarg = (size_t)ldarg;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldx, ldz, X, nullptr, nullptr);
+  const hipError_t e = hcspmm::launch_multi_f32(m, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 // Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
 // every call.
 extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64_t ldx, const float* F, int64_t f_rows, int64_t ldf,

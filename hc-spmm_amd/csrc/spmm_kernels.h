@@ -270,6 +270,22 @@ struct XArgs {
 hipError_t launch_extremum_f32(const XArgs& a, int vec, hipStream_t stream);
 hipError_t launch_extremum_backward_f32(const XArgs& a, int vec, hipStream_t stream);
 
+// Sum, sum of squares, max and min of each row's neighbours in one gather pass (spmm_multi.hip; include/hcspmm.h
+// hcspmm_forward_multi), fp32.  p as for launch_extremum_f32 with p.Z unused: the six outputs below share the row stride p.ldz
+// (values) / ldarg (positions), and a null one is not written.  p.partial = six areas of `area` floats each -- sum, sum of
+// squares, max, its position, min, its position of every partial slot (n_partials x D per area).
+struct MArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  float *zsum, *zsumsq, *zmax, *zmin;
+  int *amax, *amin;
+  size_t ldarg;
+  size_t area;        // floats per workspace area
+};
+// vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
+hipError_t launch_multi_f32(const MArgs& a, int vec, hipStream_t stream);
+
 // Edge-feature messages (spmm_edge_messages.hip; include/hcspmm.h hcspmm_forward_edge_messages), fp32: Z[r] = sum over the entries
 // e of row r of m(X[col(e)], F[fi(e)]), fi(e) = findex ? findex[e] : e.  p as for launch_extremum_f32 (p.plan == nullptr: plan-free;
 // p.X may be null for the copy op); partial = fp32 sums of the split rows.

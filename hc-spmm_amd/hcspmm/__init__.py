@@ -28,7 +28,7 @@ __all__ = [
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
     "gatv2_scores", "gatv2_scores_backward",
     "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
-    "forward_max", "forward_min", "forward_extremum_backward",
+    "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
@@ -729,6 +729,50 @@ def forward_extremum_backward(grad_Z, arg, perm, row_pointers, column_index, blo
         check(lib().hcspmm_forward_extremum_backward(_ptr(grad_Z), D, _ptr(arg), D, _ptr(grad_X), D, *c.graph, _ptr(perm),
                                                      *c.ws))
     return grad_X
+
+
+def _ws_bytes_multi(h, D):
+    return int(lib().hcspmm_multi_workspace_bytes(ctypes.byref(h), D))
+
+
+MULTI_AGGREGATES = ("sum", "sumsq", "max", "min")
+
+
+def _multi_wanted(aggregates):
+    """which of MULTI_AGGREGATES a forward_multi call asks for, in that order"""
+    aggregates = (aggregates,) if isinstance(aggregates, str) else tuple(aggregates)
+    for a in aggregates:
+        if a not in MULTI_AGGREGATES:
+            raise ValueError("aggregates must be among %s, got %r" % (", ".join(repr(k) for k in MULTI_AGGREGATES), a))
+    if not aggregates:
+        raise ValueError("aggregates must name at least one of %s" % ", ".join(repr(k) for k in MULTI_AGGREGATES))
+    return [a in aggregates for a in MULTI_AGGREGATES]
+
+
+def forward_multi(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                  aggregates=MULTI_AGGREGATES, return_arg=True):
+    """Sum, sum of squares, max and min over each row's neighbours in one gather pass -> [Z_sum, Z_sumsq, Z_max, Z_min, arg_max,
+    arg_min] (hcspmm.h hcspmm_forward_multi): contiguous [N, D] tensors, float32 values and int32 args.  An aggregate that
+    `aggregates` does not name is None, and so is the arg of an extremum that was not asked for; both args are None with
+    return_arg=False.  max / min / args follow forward_max's contract bit for bit.  X: as for forward_max."""
+    want = _multi_wanted(aggregates)
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    if not X.is_cuda:
+        raise RuntimeError("input must be a CUDA tensor")
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("input must be a 2-D float32 view with unit inner stride (multi aggregation is float32 only)")
+    N, D = row_pointers.size(0) - 1, X.size(1)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, X.size(0),
+                      X.device, ws_fn=_ws_bytes_multi)
+    Z = [torch.empty((N, D), dtype=torch.float32, device=X.device) if w else None for w in want]
+    args = [torch.empty((N, D), dtype=torch.int32, device=X.device) if (w and return_arg) else None for w in want[2:]]
+    if N == 0:
+        return Z + args
+    null = ctypes.c_void_p(0)
+    with c:
+        check(lib().hcspmm_forward_multi(_ptr(X), X.size(0), X.stride(0), 0, *(_ptr(z) if z is not None else null for z in Z), D,
+                                         *(_ptr(a) if a is not None else null for a in args), D, *c.graph, *c.ws))
+    return Z + args
 
 
 EDGE_OPS = {"mul": 0, "add_relu": 1, "copy": 2}  # include/hcspmm.h HCSPMM_EDGE_OP_*

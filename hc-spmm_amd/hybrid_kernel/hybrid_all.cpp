@@ -10,6 +10,7 @@
 
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <tuple>
 #include <unordered_map>
 #include <vector>
@@ -435,6 +436,52 @@ std::vector<torch::Tensor> spmm_forward_extremum(torch::Tensor input, torch::Ten
   check_rc(rc, reduce == HCSPMM_REDUCE_MAX ? "forward_max" : "forward_min");
   if (return_arg) return {output, arg};
   return {output};
+}
+
+// Sum, sum of squares, max and min in one gather pass (hcspmm_forward_multi): forward_max's input contract ->
+// {Z_sum, Z_sumsq, Z_max, Z_min, arg_max, arg_min}, None for what was not asked for
+std::vector<c10::optional<torch::Tensor>> spmm_forward_multi(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                             torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                                             torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
+                                                             torch::Tensor col_nzr, const std::vector<std::string>& aggregates,
+                                                             bool return_arg) {
+  static const char* const kNames[4] = {"sum", "sumsq", "max", "min"};
+  bool want[4] = {false, false, false, false};
+  for (const std::string& a : aggregates) {
+    int k = 0;
+    while (k < 4 && a != kNames[k]) ++k;
+    if (k == 4) throw pybind11::value_error("aggregates must be among 'sum', 'sumsq', 'max', 'min', got '" + a + "'");
+    want[k] = true;
+  }
+  if (aggregates.empty()) throw pybind11::value_error("aggregates must name at least one of 'sum', 'sumsq', 'max', 'min'");
+  CHECK_CUDA(input);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
+              "input must be a 2-D float32 view with unit inner stride (multi aggregation is float32 only)");
+  CallOptions o;
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_multi_workspace_bytes;  // six arrays per partial slot of a split row
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  std::vector<c10::optional<torch::Tensor>> out(6);
+  float* z[4] = {nullptr, nullptr, nullptr, nullptr};
+  int* arg[2] = {nullptr, nullptr};
+  for (int k = 0; k < 4; ++k) {
+    if (!want[k]) continue;
+    auto t = torch::empty({c.N, (int64_t)c.D}, input.options());
+    z[k] = c.N > 0 ? t.data_ptr<float>() : nullptr;
+    out[k] = t;
+    if (k >= 2 && return_arg) {
+      auto a = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kInt));
+      arg[k - 2] = mptr(a);
+      out[k + 2] = a;
+    }
+  }
+  if (c.N == 0) return out;
+  const int rc = invoke(hcspmm_forward_multi,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), HCSPMM_DTYPE_F32, z[0], z[1], z[2], z[3],
+                                        c.D, arg[0], arg[1], c.D),
+                        c.graph(), c.ws());
+  check_rc(rc, "forward_multi");
+  return out;
 }
 
 // Backward of forward_max / forward_min (hcspmm_forward_extremum_backward): square, pattern-symmetric graph, perm int32
@@ -1160,6 +1207,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
         pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
         pybind11::arg("col_nzr"), pybind11::arg("return_arg") = true);
+  m.def("forward_multi", &spmm_forward_multi,
+        "sum, sum of squares, max and min over each row's neighbours in one gather pass -> [Z_sum, Z_sumsq, Z_max, Z_min, arg_max, "
+        "arg_min], None for what `aggregates` / return_arg leave out; max / min / args as forward_max (gfx950)",
+        pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
+        pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
+        pybind11::arg("col_nzr"), pybind11::arg("aggregates") = std::vector<std::string>{"sum", "sumsq", "max", "min"},
+        pybind11::arg("return_arg") = true);
   m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
         "backward of forward_max / forward_min -> grad_X: a square, pattern-symmetric graph with perm = int32 transpose_permutation, "
         "or any square graph's A^T (transpose_graph's tensors and their preprocessing) with perm = entry_index_t (gfx950)");

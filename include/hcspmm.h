@@ -32,7 +32,8 @@ extern "C" {
  * hcspmm_gat_attention_backward (round 7); hcspmm_forward_weighted_heads, hcspmm_sddmm_heads (round 8); hcspmm_extremum_workspace_bytes,
  * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9); hcspmm_gatv2_scores, hcspmm_gatv2_backward_workspace_bytes,
  * hcspmm_gatv2_scores_backward (round 10); hcspmm_quantize_fp8, hcspmm_forward_fp8,
- * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14);
+ * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -454,6 +455,33 @@ int hcspmm_forward_extremum_backward(const float* grad_Z_d, int64_t ldg, const i
                                      const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                                      int64_t num_edges, int embedding_dim, const int32_t* transpose_perm_d, void* workspace_d,
                                      size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sum, sum of squares, max and min of each row's neighbours in ONE gather pass (PNA's mean / std / max / min; any layer that
+ * needs more than one of them).  With x_e = X[column_index[e]][d] over e in [row_pointers[r], row_pointers[r+1]):
+ *   Z_sum[r][d]   = sum of x_e
+ *   Z_sumsq[r][d] = sum of fl(x_e * x_e): the square is rounded to fp32 before it is added (never an fma), so a row summed by
+ *                   one lane group has the bits of a sequential fp32 scan
+ *   Z_max / arg_max, Z_min / arg_min: exactly hcspmm_forward_extremum's contract (ties to the lowest e, -0 == +0, NaN wins,
+ *                   the winning entry's own bits, independent of the split)
+ * Rows without entries get +0.0 in all four values and -1 in both args.  The sums run in a fixed order (CSR order inside a
+ * lane group, the wide tasks' shuffle tree, split rows in slot order): deterministic, no atomics; combined rows are within
+ * 1e-5 * sum|x_e| (1e-5 * sum x_e^2) of the exact value.
+ * Each of the six outputs may be NULL and is then not written; at least one Z_* must be set.  The four Z_* share the row
+ * stride ldz, the two args ldarg: one [num_nodes][4 * D] buffer is the call with pointers D apart and ldz = 4 * D.
+ * Other arguments as hcspmm_forward_extremum (strided X, x_rows, rectangular blocks, with a plan or plan-free);
+ * workspace_d >= hcspmm_multi_workspace_bytes() (six arrays per partial slot of a split row).
+ * fp32 only: HCSPMM_DTYPE_F16 / BF16, all four Z_* NULL, ldx or ldz < embedding_dim, ldarg < embedding_dim with an arg set
+ * and the other argument errors of hcspmm_forward_extremum are HCSPMM_EINVAL before any device call.  num_nodes == 0 returns
+ * HCSPMM_OK without a launch.  Asynchronous on `stream`.  Separate kernels (spmm_multi.hip) on the binary product's plan.
+ * ---------------------------------------------------------------------------------------- */
+size_t hcspmm_multi_workspace_bytes(const hcspmm_plan_header* header_h, int embedding_dim); /* 6 x hcspmm_workspace_bytes */
+int hcspmm_forward_multi(const void* X_d, int64_t x_rows, int64_t ldx, int dtype, float* Z_sum_d, float* Z_sumsq_d, float* Z_max_d,
+                         float* Z_min_d, int64_t ldz, int32_t* arg_max_d, int32_t* arg_min_d, int64_t ldarg,
+                         const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                         const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                         const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
+                         int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge-feature messages (GINE, SchNet / CFConv continuous filters, edge-gated convolutions, "sum the incident edge vectors"):
