@@ -248,6 +248,7 @@ int bind_graph(hcspmm::PlanArgs& p, const GraphIn& g, int D, int64_t src_rows, v
   p.col = g.col;
   p.N = (int)g.N;
   p.D = D;
+  p.E = (int)g.E;
   const hcspmm_plan_header* ph = g.ph;
   if (!(g.plan_d && ph)) {
     if (g.plan_d || ph) return HCSPMM_EINVAL;  // both or neither

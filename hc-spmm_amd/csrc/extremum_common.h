@@ -12,10 +12,7 @@ template <int L> struct XTinyT {
   static constexpr int value = L >= 32 ? 2 : TinyT<L>::value;
 };
 
-template <int VEC> struct MemI32 { typedef int type __attribute__((ext_vector_type(VEC), aligned(4))); };
-template <> struct MemI32<1> { typedef int type; };
-template <int VEC> struct IntV { typedef int type __attribute__((ext_vector_type(VEC))); };
-template <> struct IntV<1> { typedef int type; };
+// (MemI32, IntV: spmm_impl.h)
 __device__ __forceinline__ int iget(const int& v, int) { return v; }
 template <typename V> __device__ __forceinline__ int iget(const V& v, int i) { return v[i]; }
 __device__ __forceinline__ void iset(int& v, int, int x) { v = x; }

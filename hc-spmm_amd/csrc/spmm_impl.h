@@ -124,6 +124,11 @@ template <> struct MemF32<1> { typedef float type; };
 // onto the row's last 8 elements): D = 22 takes three 16-byte lanes instead of 22 two-byte ones.
 template <int WORDS> struct MemU32 { typedef unsigned int type __attribute__((ext_vector_type(WORDS), aligned(4))); };
 template <> struct MemU32<1> { typedef unsigned int type; };
+// VEC ints in registers (IntV) and as they are addressed in memory (MemI32: dword-aligned, like MemF32)
+template <int VEC> struct MemI32 { typedef int type __attribute__((ext_vector_type(VEC), aligned(4))); };
+template <> struct MemI32<1> { typedef int type; };
+template <int VEC> struct IntV { typedef int type __attribute__((ext_vector_type(VEC))); };
+template <> struct IntV<1> { typedef int type; };
 
 // 8-bit rows are addressed like the 16-bit ones: dword-aligned vectors of four codes (widths and strides that are multiples of 4),
 // the last lane moved back onto the row's last VEC codes; the narrow dense-tile lanes (2 codes, 1 code) load them as they are.
@@ -229,18 +234,26 @@ template <int L> struct TinyT {
 // basic block -- UB broadcasts, UB address computations, UB loads back to back, counted waits.
 // (Staging the rows through LDS instead was built and measured -- never faster, +9 % at D = 32:
 // profiles/r01/ab_lds_stage.log, code at commit 950912e.)
-template <typename E, int VEC, int UB>
+//
+// IV: column indices a lane holds per chunk.  1: lane src0 + u holds entry u of the batch.  4 (sparse_task_body, L = 8): a
+// lane holds four consecutive entries, so entry u comes from lane src0 + u / 4, component u % 4.  A batch always starts at a
+// multiple of U entries -- sparse_task_body's ladder issues full batches and then at most ONE shorter tail batch -- so the
+// component is a compile-time constant in every batch, the 2- and 1-entry tails included.
+template <typename E, int VEC, int UB, int IV = 1>
 __device__ __forceinline__ void gather_batch(const typename E::T* __restrict__ X, size_t ldx, int csafe, bool cok,
-                                             int myidx, int src0, typename AccT<VEC>::type& acc,
-                                             const int* prefetch_from, int& prefetched) {
+                                             const typename IntV<IV>::type& myidx, int src0, typename AccT<VEC>::type& acc,
+                                             const int* prefetch_from, typename IntV<IV>::type& prefetched) {
   typedef Lane<E, VEC> Ln;
   int idx[UB];
   typename Ln::raw_t v[UB];
 #pragma unroll
-  for (int u = 0; u < UB; ++u) idx[u] = __shfl(myidx, src0 + u, 64);
+  for (int u = 0; u < UB; ++u) {
+    if constexpr (IV == 1) idx[u] = __shfl(myidx, src0 + u, 64);
+    else idx[u] = __shfl(myidx[u % IV], src0 + u / IV, 64);
+  }
   // the next chunk's indices are requested here -- after this chunk's were broadcast, ahead of its row
   // loads -- so they arrive under those loads and a chunk costs one round trip, not two
-  if (prefetch_from != nullptr) prefetched = *prefetch_from;
+  if (prefetch_from != nullptr) prefetched = *reinterpret_cast<const typename MemI32<IV>::type*>(prefetch_from);
 #pragma unroll
   for (int u = 0; u < UB; ++u) v[u] = Ln::load(X + (size_t)max(idx[u], 0) * ldx + csafe);
 #pragma unroll
@@ -257,52 +270,88 @@ __device__ __forceinline__ void gather_batch(const typename E::T* __restrict__ X
 // predicated off by idx = -1, and adding the resulting 0.0f is exact.  The result goes to
 // dstZ (a row of Z, element type) or dstP (a partial-sum row of the fp32 workspace).
 // ------------------------------------------------------------------------------------------
-template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U>
-__device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
-                                            float* __restrict__ dstP, const int* __restrict__ col, int e0, int n,
-                                            size_t ldx, int c0, int cend, int lane) {
+// Column indices per lane and chunk (IV above).  The planned kernel's fp32 tasks of 8 lanes -- every launch with 32-column panels -- in a wave
+// whose longest task exceeds HCSPMM_INDEX_VEC_MIN entries hold HCSPMM_INDEX_VEC = 4: lane s loads entries base + 4s ..
+// base + 4s + 3 of its task with ONE dword-aligned 16-byte load, so a lane group asks L2 for one 128-byte line of `col` per 32
+// entries.  With one index per lane the line's four 32-byte quarters are requested a full gather batch apart, and a CU's
+// 1 280 feature lines in flight have usually pushed the line out of its 256-line L1 in between (profiles/r16/
+// index_requests.log).  Shorter tasks lose 1.6-2.2 % to the wider path, so do 16-lane groups (ab_index_loads.log): they,
+// wide tasks, the other L, the plan-free kernel and the 16-bit / 8-bit builds keep one index per lane -- sparse_task_body<.., 1>, the code as it was.
+#ifndef HCSPMM_INDEX_VEC
+#define HCSPMM_INDEX_VEC 4
+#endif
+#ifndef HCSPMM_INDEX_VEC_MIN
+#define HCSPMM_INDEX_VEC_MIN 32  // waves whose longest task is at most this keep one index per lane
+#endif
+
+// Where a lane's IV indices from entry e on come from, `left` of them inside its task (<= 0: none, nothing is read): the
+// address of one IV-dword load when all IV lie inside col[0, nE) -- they may run past the task, never past the array; the
+// caller issues it and discards the surplus -- or nullptr after reading the array's last entries one at a time into v.
+template <int IV>
+__device__ __forceinline__ const int* index_source(const int* __restrict__ col, int e, int left, int nE,
+                                                   typename IntV<IV>::type& v) {
+  if (left <= 0) return nullptr;
+  if constexpr (IV == 1) return col + e;
+  else {
+    if (e <= nE - IV) return col + e;
+#pragma unroll
+    for (int k = 0; k < IV; ++k)
+      if (k < left) v[k] = col[e + k];
+    return nullptr;
+  }
+}
+
+// (IV indices per lane and chunk; nmax: the wave's longest task)
+template <typename E, int L, int VEC, bool WIDE, int UMAX, int IV>
+__device__ __forceinline__ void sparse_task_body(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
+                                                 float* __restrict__ dstP, const int* __restrict__ col, int nE, int e0, int n,
+                                                 int nmax, size_t ldx, int c0, int cend, int lane) {
   typedef Lane<E, VEC> Ln;
   typedef typename Ln::acc_t acc_t;
   constexpr int U = (L < UMAX) ? L : UMAX;  // loads in flight per lane
+  typedef typename IntV<IV>::type idx_t;
+  typedef typename MemI32<IV>::type idx_mem_t;
   // WIDE: the whole wave owns ONE task (e0, n wave-uniform); per 64-entry super-chunk lane i holds
   // entry base+i, so lane group g sums entries [base + g*L, base + (g+1)*L) and the 64/L group sums
-  // are combined by a fixed xor-shuffle tree at the end.  Otherwise each lane group owns its own task.
-  constexpr int STRIDE = WIDE ? 64 : L;
+  // are combined by a fixed xor-shuffle tree at the end.  Otherwise each lane group owns its own task,
+  // L * IV entries per chunk.
+  constexpr int STRIDE = WIDE ? 64 : L * IV;
+  static_assert(IV == 1 || U % IV == 0, "a batch must start on a lane's first index");
   const int s = lane & (L - 1);
-  const int pos = WIDE ? lane : s;
+  const int pos = WIDE ? lane : s * IV;
   const int gbase = lane & ~(L - 1);
-  int nmax = n;
-  if (!WIDE) {
-#pragma unroll
-    for (int off = L; off < 64; off <<= 1) nmax = max(nmax, __shfl_xor(nmax, off, 64));
-  }
-  nmax = __builtin_amdgcn_readfirstlane(nmax);
 
   for (int pbase = c0; pbase < cend; pbase += L * VEC) {  // feature columns [c0, cend) of the rows
     const bool cok = pbase + s * VEC < cend;
     const int c = cok ? lane_col<VEC>(pbase + s * VEC, cend) : 0;
     const int csafe = c;
     acc_t acc = azero<VEC>();
-    int next = (pos < n) ? col[e0 + pos] : -1;
+    idx_t next = idx_t(-1);
+    if (const int* p0 = index_source<IV>(col, e0 + pos, n - pos, nE, next)) next = *reinterpret_cast<const idx_mem_t*>(p0);
     for (int base = 0; base < nmax; base += STRIDE) {
-      const int myidx = next;
-      const bool more = base + STRIDE + pos < n;
-      next = -1;
-      const int cnt = min(L, nmax - base);  // longest lane group's share of this chunk
-      const int* pf = more ? col + e0 + base + STRIDE + pos : nullptr;  // consumed by the chunk's first batch
+      idx_t myidx = next;
+      if constexpr (IV > 1) {  // a lane's IV entries may run past its task
+#pragma unroll
+        for (int k = 1; k < IV; ++k) myidx[k] = (base + pos + k < n) ? myidx[k] : -1;
+      }
+      next = idx_t(-1);
+      const int cnt = min(WIDE ? L : STRIDE, nmax - base);  // longest lane group's share of this chunk
+      // consumed by the chunk's first batch
+      const int* pf = index_source<IV>(col, e0 + base + STRIDE + pos, n - (base + STRIDE + pos), nE, next);
       for (int j = 0; j < cnt;) {
         const int left = cnt - j;  // wave-uniform: short tasks (the bulk of a low-degree graph) get
+        const int src = gbase + j / IV;  // j is a multiple of U here (and U of IV): see gather_batch
         if (left > U / 2) {        // short batches instead of a full one padded with dummy loads
-          gather_batch<E, VEC, U>(X, ldx, csafe, cok, myidx, gbase + j, acc, pf, next);
+          gather_batch<E, VEC, U, IV>(X, ldx, csafe, cok, myidx, src, acc, pf, next);
           j += U;
         } else if (U >= 8 && left > U / 4) {
-          gather_batch<E, VEC, (U >= 8 ? U / 2 : 1)>(X, ldx, csafe, cok, myidx, gbase + j, acc, pf, next);
+          gather_batch<E, VEC, (U >= 8 ? U / 2 : 1), IV>(X, ldx, csafe, cok, myidx, src, acc, pf, next);
           j += U / 2;
         } else if (U >= 4 && left > 1) {
-          gather_batch<E, VEC, (U >= 8 ? U / 4 : 2)>(X, ldx, csafe, cok, myidx, gbase + j, acc, pf, next);
+          gather_batch<E, VEC, (U >= 8 ? U / 4 : 2), IV>(X, ldx, csafe, cok, myidx, src, acc, pf, next);
           j += (U >= 8 ? U / 4 : 2);
         } else {
-          gather_batch<E, VEC, 1>(X, ldx, csafe, cok, myidx, gbase + j, acc, pf, next);
+          gather_batch<E, VEC, 1, IV>(X, ldx, csafe, cok, myidx, src, acc, pf, next);
           j += 1;
         }
         pf = nullptr;
@@ -320,6 +369,28 @@ __device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X,
       else if (dstP != nullptr) Ln::store_partial(dstP + c, acc);
     }
   }
+}
+
+// IVREQ: indices per lane the caller asks for where the 16-byte path applies (the planned kernel's ordinary and sliced tasks
+// pass HCSPMM_INDEX_VEC; the plan-free kernel, whose lane groups never see more than kPlanFreeWide = 64 entries, keeps 1)
+template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U, int IVREQ = 1>
+__device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
+                                            float* __restrict__ dstP, const int* __restrict__ col, int nE, int e0, int n,
+                                            size_t ldx, int c0, int cend, int lane) {
+  int nmax = n;
+  if (!WIDE) {
+#pragma unroll
+    for (int off = L; off < 64; off <<= 1) nmax = max(nmax, __shfl_xor(nmax, off, 64));
+  }
+  nmax = __builtin_amdgcn_readfirstlane(nmax);
+  constexpr int IV = (!WIDE && L == 8 && sizeof(typename E::T) == 4) ? IVREQ : 1;
+  if constexpr (IV > 1) {
+    if (nmax > HCSPMM_INDEX_VEC_MIN) {  // wave-uniform: the plan sorts tasks by length class
+      sparse_task_body<E, L, VEC, WIDE, UMAX, IV>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane);
+      return;
+    }
+  }
+  sparse_task_body<E, L, VEC, WIDE, UMAX, 1>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -749,7 +820,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
       const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
       typename E::Z* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
       float* dp = (t.w < 0) ? nullptr : a.partial + (size_t)t.w * (size_t)a.D;
-      sparse_task<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, __builtin_amdgcn_readfirstlane(t.y),
+      sparse_task<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, a.E, __builtin_amdgcn_readfirstlane(t.y),
                                            __builtin_amdgcn_readfirstlane(t.z), a.ldx, c0, cend, lane);
     } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
       // (bf >= free_wgs_pp: the workgroups that pad a sliced panel to a multiple of 8 -- with the tiny tasks in their own
@@ -794,7 +865,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
           else dp = a.partial + (size_t)t.w * (size_t)a.D;
         }
       }
-      sparse_task<E, L, VEC, false, UNROLL>(X, dz, dp, a.col, e0, n, a.ldx, c0, cend, lane);
+      sparse_task<E, L, VEC, false, UNROLL, HCSPMM_INDEX_VEC>(X, dz, dp, a.col, a.E, e0, n, a.ldx, c0, cend, lane);
     }
   } else {
     if constexpr (FUSED) {  // fp32 only: dense windows aggregate AND multiply by the weights (one window per wave)
@@ -958,7 +1029,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_kernel(WindowArgs a) {
           dst = nullptr;
         }
       }
-      sparse_task<E, L, VEC, false>(X, dst, nullptr, a.col, e0, n, a.ldx, 0, a.D, lane);
+      sparse_task<E, L, VEC, false>(X, dst, nullptr, a.col, 0, e0, n, a.ldx, 0, a.D, lane);
     }
     // longer rows: whole waves (all 64/L lane groups on one row, shuffle-tree combine), dealt
     // round-robin over the workgroup's waves -- a hub row no longer crawls on one lane group
@@ -969,7 +1040,7 @@ __global__ __launch_bounds__(kThreads) void hybrid_window_kernel(WindowArgs a) {
         const int n = a.rowptr[r + 1] - e0;
         if (n > kPlanFreeWide) {
           if (k % nwaves == wave)
-            sparse_task<E, L, VEC, true>(X, Z + (size_t)r * a.ldz, nullptr, a.col, e0, n, a.ldx, 0, a.D, lane);
+            sparse_task<E, L, VEC, true>(X, Z + (size_t)r * a.ldz, nullptr, a.col, 0, e0, n, a.ldx, 0, a.D, lane);
           ++k;
         }
       }

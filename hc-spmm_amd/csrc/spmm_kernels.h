@@ -47,6 +47,9 @@ struct PlanArgs {
   };
   long long w_ldr, w_ldc;
   float* out;
+  // entries of col: the 16-byte index loads of sparse_task stay inside col[0, E).  (Last, so that no other member moves: one
+  // more dword in the middle cost the 16-bit weighted L = 32 build four more bytes of scratch.)
+  int E;
 };
 
 // Arguments of the row-tile fused launch (fused_rows.hip): the planned launch's arguments (Z = out2; W / out / H set) plus the
