@@ -971,6 +971,84 @@ class PNAConv(torch.nn.Module):
         return _Update.apply(X, self.weights_root) + _Update.apply(S, self.weights_neigh)
 
 
+class SoftmaxAggregate(torch.autograd.Function):
+    """Per-channel softmax aggregation of each row's neighbour features, Z[i] = sum_j p_ij X[j] with p_ij the softmax over row
+    i's entries of t * X[j] (HCSPMM.forward_softmax: one online-softmax gather pass), with gradients for X and t:
+      dX = HCSPMM.softmax_backward on the graph the backward walks -- the weights are recomputed from the forward's row maxima
+           M and normalisers L, no per-entry tensor is kept;
+      dt = sum_i dZ[i] * (Q[i] - Z[i]^2), Q the softmax-weighted mean of the squares (asked of the forward only when t needs a
+           gradient), summed over the rows (and the columns, for a t of one element).
+    t: a Python float or a tensor of 1 or D elements.  tail = the eight graph tensors of A followed by the eight of the graph the
+    backward walks (A itself when the pattern is symmetric, else transposed_graph's)."""
+
+    @staticmethod
+    def forward(ctx, X, t, *tail):
+        X = X.contiguous()
+        learnt = isinstance(t, torch.Tensor)
+        beta = t.detach() if learnt else float(t)
+        need_t = learnt and ctx.needs_input_grad[1]
+        Z, M, L, Q = HCSPMM.forward_softmax(X, beta, *tail[:N_GRAPH], ("M", "L", "Q") if need_t else ("M", "L"))
+        ctx.beta = None if learnt else beta
+        ctx.save_for_backward(X, Z, M, L, Q, beta if learnt else None, *tail[N_GRAPH:])
+        return Z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward is a launch, not a graph of differentiable ops
+    def backward(ctx, d_out):
+        X, Z, M, L, Q, beta, *graph_b = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_x = d_t = None
+        if ctx.needs_input_grad[0]:
+            d_x = HCSPMM.softmax_backward(d_out, Z, M, L, X, ctx.beta if beta is None else beta, *graph_b)
+        if ctx.needs_input_grad[1]:
+            per_column = (d_out * (Q - Z * Z)).sum(0)
+            d_t = (per_column.sum() if beta.numel() == 1 else per_column).reshape(beta.shape)
+        return (d_x, d_t) + (None,) * (2 * N_GRAPH)
+
+
+def softmax_aggregate(X, graph, t=1.0, directed=False):
+    """Softmax aggregation over each row's neighbours (DeeperGCN; PyG SoftmaxAggregation), per feature column:
+    Z[i] = sum_j softmax_j(t * X[j]) X[j], with autograd for X (float32 [N, D]) and for t when it is a tensor that requires grad
+    (1 or D elements; a float otherwise).  t -> +-inf approaches max / min, t = 0 is the mean.  graph = the eight graph tensors,
+    whose pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then
+    runs on transposed_graph(graph).  Rows without entries give 0."""
+    if directed:
+        return SoftmaxAggregate.apply(X, t, *graph, *transposed_graph(graph)[:N_GRAPH])
+    transpose_permutation_i32(graph[0], graph[1])  # an asymmetric pattern is refused before any launch (cached)
+    return SoftmaxAggregate.apply(X, t, *graph, *graph)
+
+
+class GENConv(torch.nn.Module):
+    """DeeperGCN's generalised aggregation layer with the softmax aggregator:
+      out = (X + softmax_aggregate(relu(X) + eps, t)) W
+    one softmax_aggregate pass and one product on _Update.  t is the inverse temperature: a float, or with learn_t=True a scalar
+    Parameter initialised to it (its gradient costs no kernel: SoftmaxAggregate).  _Conv's call signature, so that Net builds
+    it; edge_weight is refused.  The pattern must be symmetric unless directed=True (the backward then runs on
+    transposed_graph)."""
+
+    def __init__(self, input_dim, output_dim, t=1.0, learn_t=False, eps=1e-7, directed=False):
+        super().__init__()
+        self.directed, self.eps = bool(directed), float(eps)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self.initial_t = float(t)
+        self.t = torch.nn.Parameter(torch.empty(())) if learn_t else self.initial_t
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.weights.size(1))
+        self.weights.data.uniform_(-stdv, stdv)
+        if isinstance(self.t, torch.Tensor):
+            self.t.data.fill_(self.initial_t)
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("GENConv aggregates with its own softmax weights: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        agg = softmax_aggregate(torch.relu(X) + self.eps, graph, self.t, self.directed)
+        return _Update.apply(X + agg, self.weights)
+
+
 class EdgeMessageAggregate(torch.autograd.Function):
     """Z[i] = sum over the entries e = (i, j) of m(X[j], F[e]) (HCSPMM.forward_edge_messages; op "mul" x * f, "add_relu"
     relu(x + f), "copy" f) with gradients for X and F [E, D].  dF is HCSPMM.edge_messages_grad; dX is the same forward on A^T:

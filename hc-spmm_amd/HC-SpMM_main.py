@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GCN / GIN / GINE / GAT / GATv2 / SAGE training driver and single-kernel profiler over the HCSPMM operators -- counterpart
+"""GCN / GIN / GINE / GAT / GATv2 / SAGE / PNA / GEN training driver and single-kernel profiler over the HCSPMM operators -- counterpart
 of the reference's HC-SpMM_main.py (same eight flags, HC-SpMM_main.py:18-27, same printed lines
 "Prep. (ms)" :54 and "=> SAG profiling avg (ms)" GNN_model.py:261, same model shape :66-110, same
 schedule: 9 untimed warm-up epochs then --epochs timed ones, Adam lr 0.01, nll_loss :114-158).
@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GINConv, GINEConv, PNAConv, SAGEConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, SAGEConv, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage", "pna"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage", "pna", "gen"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -71,7 +71,14 @@ def parse_args(argv=None):
     # addition: --model gine (GNN_model.GINEConv: sum_j relu(x_j + e_ij W_e)); the datasets carry no edge attributes, so --edge-dim
     # of them per stored entry are drawn once from a seeded generator
     p.add_argument("--edge-dim", type=int, default=8, help="edge attributes per entry (--model gine; synthesised, seeded)")
+    # addition: --model gen (GNN_model.GENConv: DeeperGCN's softmax aggregation, out = (x + sum_j softmax_j(t x_j) x_j) W)
+    p.add_argument("--gen-t", type=float, default=1.0, help="inverse temperature t of --model gen")
+    p.add_argument("--gen-learn-t", action="store_true", help="--model gen: learn t (one scalar per layer)")
     args = p.parse_args(argv)
+    if args.model == "gen" and args.aggr is not None:
+        p.error("--aggr does not apply to --model gen: GENConv aggregates with its softmax weights")
+    if args.model == "gen" and args.norm != "none":
+        p.error("--norm does not apply to --model gen: its edge values are the softmax weights")
     # addition: --model pna (GNN_model.PNAConv: mean / min / max / std of the neighbours from one gather pass, times degree scalers);
     # its aggregators are the layer's own, so --aggr is refused
     if args.model == "pna" and args.aggr is not None:
@@ -217,6 +224,9 @@ def main(argv=None):
             if fixed == 2:  # the last layer, as for sage
                 return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed)
             return PNAConv(input_dim, output_dim, directed=directed)
+    if args.model == "gen":
+        def conv_cls(input_dim, output_dim, fixed):
+            return GENConv(input_dim, output_dim, t=args.gen_t, learn_t=args.gen_learn_t, directed=directed)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated

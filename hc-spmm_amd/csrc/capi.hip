@@ -560,6 +560,70 @@ extern "C" int hcspmm_forward_multi(const void* X, int64_t x_rows, int64_t ldx, 
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+extern "C" size_t hcspmm_softmax_workspace_bytes(const hcspmm_plan_header* ph, int D) { return 4 * hcspmm_workspace_bytes(ph, D); }
+
+// Per-channel softmax aggregation (spmm_softmax.hip): the plan and checks of hcspmm_forward_multi, Z required, three nullable
+// statistics.
+extern "C" int hcspmm_forward_softmax(const void* X, int64_t x_rows, int64_t ldx, int dtype, const float* beta, float* Z, float* M,
+                                      float* L, float* Q, int64_t ldz, const int32_t* rowptr, const int32_t* col,
+                                      const int32_t* blockPartition, const int32_t* edgeToColumn, const int32_t* edgeToRow,
+                                      const int32_t* hybrid_type, const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N,
+                                      int64_t E, int D, void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype != HCSPMM_DTYPE_F32) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D) return HCSPMM_EINVAL;
+  if (!Z || !beta) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::SArgs s{};
+  // workspace: four areas of hcspmm_workspace_bytes each -- m, l, a, q of the split rows' partial slots
+  const int rc = bind_graph(s.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 4, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (s.p.plan) {
+    s.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+    s.segment_len = ph->segment_len;
+  }
+  set_operands(s.p, X, nullptr, ldx, ldz);
+  s.rowptr = rowptr;
+  s.beta = beta;
+  s.z = Z;
+  s.m = M;
+  s.l = L;
+  s.q = Q;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldx, ldz, X, nullptr, nullptr);
+  const hipError_t e = hcspmm::launch_softmax_f32(s, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+// Its gradient with respect to X (softmax_aggr_grad.hip) on the graph the backward walks: a plain-sum launch, one partial area.
+extern "C" int hcspmm_softmax_backward(const float* grad_Z, const float* Z, const float* M, const float* L, int64_t ld_in,
+                                       int64_t src_rows, const float* X, int64_t ldx, const float* beta, float* grad_X, int64_t ldgx,
+                                       const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                       const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                       const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                       void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || E < 0 || src_rows < 0 || D <= 0 || ld_in < D || ldx < D || ldgx < D) return HCSPMM_EINVAL;
+  if (!grad_X || !beta) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && (!col || !grad_Z || !Z || !M || !L || src_rows == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::SGradArgs a{};
+  const int rc = bind_graph(a.p, GRAPH_IN, D, src_rows, workspace, workspace_bytes, 1, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.plan) a.segment_len = ph->segment_len;
+  set_operands(a.p, X, grad_X, ldx, ldgx);
+  a.rowptr = rowptr;
+  a.beta = beta;
+  a.G = grad_Z;
+  a.Zf = Z;
+  a.M = M;
+  a.L = L;
+  a.ld_in = (size_t)ld_in;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldx, ldgx, X, grad_X, nullptr);
+  const hipError_t e = hcspmm::launch_softmax_backward_f32(a, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 // Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
 // every call.
 extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64_t ldx, const float* F, int64_t f_rows, int64_t ldf,

@@ -289,6 +289,33 @@ struct MArgs {
 // vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
 hipError_t launch_multi_f32(const MArgs& a, int vec, hipStream_t stream);
 
+// Per-channel softmax aggregation (spmm_softmax.hip; include/hcspmm.h hcspmm_forward_softmax), fp32.  p as for launch_multi_f32
+// with p.Z unused: the outputs below share the row stride p.ldz, z is required and a null m / l / q is not written.
+// p.partial = four areas of `area` floats each -- m, l, a, q of every partial slot (n_partials x D per area).
+struct SArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  const float* beta;  // [D]
+  float *z, *m, *l, *q;
+  size_t area;        // floats per workspace area
+};
+// vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
+hipError_t launch_softmax_f32(const SArgs& a, int vec, hipStream_t stream);
+// its gradient with respect to X (softmax_aggr_grad.hip, hcspmm_softmax_backward), a plain-sum launch on the graph the backward
+// walks: row j sums exp(beta x_j - M_i) / L_i * G_i * (1 + beta (x_j - Z_i)) over its entries (j, i).  p as for
+// launch_edge_messages_f32 with p.X = X (the tasks' OWN rows, N of them, stride p.ldx) and p.Z = grad_X; G, Z, M, L are gathered
+// through the column ids and share the row stride ld_in; partial = fp32 sums of the split rows.
+struct SGradArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  const float* beta;  // [D]
+  const float *G, *Zf, *M, *L;
+  size_t ld_in;
+};
+hipError_t launch_softmax_backward_f32(const SGradArgs& a, int vec, hipStream_t stream);
+
 // Edge-feature messages (spmm_edge_messages.hip; include/hcspmm.h hcspmm_forward_edge_messages), fp32: Z[r] = sum over the entries
 // e of row r of m(X[col(e)], F[fi(e)]), fi(e) = findex ? findex[e] : e.  p as for launch_extremum_f32 (p.plan == nullptr: plan-free;
 // p.X may be null for the copy op); partial = fp32 sums of the split rows.

@@ -29,6 +29,7 @@ __all__ = [
     "gatv2_scores", "gatv2_scores_backward",
     "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
+    "forward_softmax", "softmax_backward",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
@@ -773,6 +774,99 @@ def forward_multi(X, row_pointers, column_index, blockPartition, edgeToColumn, e
         check(lib().hcspmm_forward_multi(_ptr(X), X.size(0), X.stride(0), 0, *(_ptr(z) if z is not None else null for z in Z), D,
                                          *(_ptr(a) if a is not None else null for a in args), D, *c.graph, *c.ws))
     return Z + args
+
+
+def _ws_bytes_softmax(h, D):
+    return int(lib().hcspmm_softmax_workspace_bytes(ctypes.byref(h), D))
+
+
+def _beta_vector(beta, D, device):
+    """beta of the softmax aggregation as a float32 [D] device vector: a Python number, or a float32 tensor of 1 or D elements
+    on the input's device, broadcast there (no host synchronisation: the call captures into a HIP graph)"""
+    if isinstance(beta, torch.Tensor):
+        if beta.dtype != torch.float32 or beta.numel() not in (1, D) or beta.device != device:
+            raise RuntimeError("beta must be a Python float or a float32 tensor with 1 or D = %d elements on the device of the "
+                               "input, got %s %s on %s" % (D, beta.dtype, tuple(beta.shape), beta.device))
+        return beta.detach().reshape(-1).expand(D).contiguous()
+    return torch.full((D,), float(beta), dtype=torch.float32, device=device)
+
+
+def forward_softmax(X, beta, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                    return_stats=True):
+    """Per-channel softmax aggregation of each row's neighbours in one gather pass -> (Z, M, L, Q) (hcspmm.h
+    hcspmm_forward_softmax): Z[r][d] = sum_e p_e x_e with p_e = softmax over the row's entries of beta[d] * x_e, and the
+    statistics of its backward, M = max_e fl(beta x_e), L = sum_e exp(beta x_e - M), Q = sum_e p_e x_e^2 -- contiguous float32
+    [N, D].  return_stats: True for all three, False for none ((Z, None, None, None)), or an iterable naming some of "M", "L",
+    "Q"; a statistic not asked for is None.  beta: a Python float or a float32 tensor of 1 or D elements.  Rows without
+    entries give Z = Q = 0, M = -inf, L = 0.  X: as for forward_max."""
+    if isinstance(return_stats, (str, bytes)):
+        return_stats = (return_stats,)
+    if not hasattr(return_stats, "__iter__"):  # a bool, or anything else with a truth value (0 / 1, numpy.bool_)
+        want = [bool(return_stats)] * 3
+    else:
+        names = tuple(return_stats)
+        for n in names:
+            if n not in ("M", "L", "Q"):
+                raise ValueError("return_stats must be a bool or name some of 'M', 'L', 'Q', got %r" % (n,))
+        want = [n in names for n in ("M", "L", "Q")]
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    if not X.is_cuda:
+        raise RuntimeError("input must be a CUDA tensor")
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("input must be a 2-D float32 view with unit inner stride (softmax aggregation is float32 only)")
+    N, D = row_pointers.size(0) - 1, X.size(1)
+    if D == 0:
+        raise RuntimeError("input must have at least one column")
+    b = _beta_vector(beta, D, X.device)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, X.size(0),
+                      X.device, ws_fn=_ws_bytes_softmax)
+    Z = torch.empty((N, D), dtype=torch.float32, device=X.device)
+    stats = [torch.empty((N, D), dtype=torch.float32, device=X.device) if w else None for w in want]
+    if N == 0:
+        return (Z, *stats)
+    null = ctypes.c_void_p(0)
+    with c:
+        check(lib().hcspmm_forward_softmax(_ptr(X), X.size(0), X.stride(0), 0, _ptr(b), _ptr(Z),
+                                           *(_ptr(t) if t is not None else null for t in stats), D, *c.graph, *c.ws))
+    return (Z, *stats)
+
+
+def softmax_backward(grad_Z, Z, M, L, X, beta, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                     row_nzr, col_nzr):
+    """Gradient of forward_softmax with respect to X -> float32 [n, D], on the graph the backward WALKS (A^T's eight tensors, or
+    A's own for a symmetric pattern; n rows): dX[j] = sum over the entries (j, i) of row j of exp(beta x_j - M[i]) / L[i] * grad_Z[i]
+    * (1 + beta (x_j - Z[i])).  grad_Z, Z, M, L: contiguous float32 [rows, D] of the forward (rows >= the walked graph's column
+    ids); X: the float32 [n, D] view the forward gathered; beta as for forward_softmax.  Deterministic, no atomics (hcspmm.h
+    hcspmm_softmax_backward).  The gradient with respect to beta is (grad_Z * (Q - Z * Z)).sum(0)."""
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    for t, n in ((grad_Z, "grad_Z"), (Z, "Z"), (M, "M"), (L, "L")):
+        _check_input(t, n)
+    if not X.is_cuda:
+        raise RuntimeError("input must be a CUDA tensor")
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("input must be a 2-D float32 view with unit inner stride (softmax aggregation is float32 only)")
+    n, D = row_pointers.size(0) - 1, X.size(1)
+    if X.size(0) != n:
+        raise RuntimeError("input has %d rows but the walked graph has %d nodes" % (X.size(0), n))
+    if grad_Z.dtype != torch.float32 or grad_Z.dim() != 2 or grad_Z.size(1) != D or D == 0:
+        raise RuntimeError("grad_Z must be a float32 [rows, D] tensor with D = %d > 0, got %s %s" % (D, grad_Z.dtype, tuple(grad_Z.shape)))
+    for t, name in ((Z, "Z"), (M, "M"), (L, "L")):
+        if t.dtype != torch.float32 or t.shape != grad_Z.shape or t.device != X.device:
+            raise RuntimeError("%s must be a float32 tensor of grad_Z's shape on the device of the input" % name)
+    if grad_Z.device != X.device:
+        raise RuntimeError("grad_Z must be on the device of the input")
+    b = _beta_vector(beta, D, X.device)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D,
+                      grad_Z.size(0), X.device)
+    if c.E > 0 and grad_Z.size(0) == 0:
+        raise RuntimeError("grad_Z has no rows but the walked graph has %d entries" % c.E)
+    grad_X = torch.empty((n, D), dtype=torch.float32, device=X.device)
+    if n == 0:
+        return grad_X
+    with c:
+        check(lib().hcspmm_softmax_backward(_ptr(grad_Z), _ptr(Z), _ptr(M), _ptr(L), D, grad_Z.size(0), _ptr(X), X.stride(0),
+                                            _ptr(b), _ptr(grad_X), D, *c.graph, *c.ws))
+    return grad_X
 
 
 EDGE_OPS = {"mul": 0, "add_relu": 1, "copy": 2}  # include/hcspmm.h HCSPMM_EDGE_OP_*

@@ -484,6 +484,103 @@ std::vector<c10::optional<torch::Tensor>> spmm_forward_multi(torch::Tensor input
   return out;
 }
 
+// beta of the softmax aggregation as a float32 [D] vector on the input's device: a Python number, or a float32 tensor of 1 or D
+// elements on that device, broadcast there (no host synchronisation: the call captures into a HIP graph)
+torch::Tensor beta_vector(const pybind11::object& beta, int64_t D, const torch::Tensor& input) {
+  if (THPVariable_Check(beta.ptr())) {
+    const torch::Tensor t = pybind11::cast<torch::Tensor>(beta);
+    TORCH_CHECK(t.scalar_type() == torch::kFloat && (t.numel() == 1 || t.numel() == D) && t.device() == input.device(),
+                "beta must be a Python float or a float32 tensor with 1 or D = ", D, " elements on the device of the input, got ",
+                t.scalar_type(), " ", t.sizes(), " on ", t.device());
+    return t.detach().reshape({-1}).expand({D}).contiguous();
+  }
+  return torch::full({D}, pybind11::cast<double>(beta), input.options());
+}
+
+// Per-channel softmax aggregation in one gather pass (hcspmm_forward_softmax): forward_max's input contract -> (Z, M, L, Q),
+// None for a statistic that return_stats (a bool, or an iterable naming some of "M", "L", "Q") leaves out
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+spmm_forward_softmax(torch::Tensor input, pybind11::object beta, torch::Tensor nodePointer, torch::Tensor edgeList,
+                     torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
+                     torch::Tensor row_nzr, torch::Tensor col_nzr, pybind11::object return_stats) {
+  static const char* const kNames[3] = {"M", "L", "Q"};
+  bool want[3] = {false, false, false};
+  if (pybind11::isinstance<pybind11::str>(return_stats)) return_stats = pybind11::make_tuple(return_stats);
+  if (!pybind11::isinstance<pybind11::iterable>(return_stats)) {  // a bool, or anything else with a truth value (0 / 1, numpy.bool_)
+    want[0] = want[1] = want[2] = PyObject_IsTrue(return_stats.ptr()) == 1;
+  } else {
+    for (const auto& item : return_stats) {
+      const std::string a = pybind11::cast<std::string>(item);
+      int k = 0;
+      while (k < 3 && a != kNames[k]) ++k;
+      if (k == 3) throw pybind11::value_error("return_stats must be a bool or name some of 'M', 'L', 'Q', got '" + a + "'");
+      want[k] = true;
+    }
+  }
+  CHECK_CUDA(input);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
+              "input must be a 2-D float32 view with unit inner stride (softmax aggregation is float32 only)");
+  TORCH_CHECK(input.size(1) > 0, "input must have at least one column");
+  CallOptions o;
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_softmax_workspace_bytes;  // four arrays per partial slot of a split row
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  const torch::Tensor b = beta_vector(beta, c.D, input);
+  auto Z = torch::empty({c.N, (int64_t)c.D}, input.options());
+  c10::optional<torch::Tensor> stats[3];
+  float* sp[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (!want[k]) continue;
+    auto t = torch::empty({c.N, (int64_t)c.D}, input.options());
+    sp[k] = c.N > 0 ? t.data_ptr<float>() : nullptr;
+    stats[k] = t;
+  }
+  if (c.N > 0) {
+    const int rc = invoke(hcspmm_forward_softmax,
+                          std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), HCSPMM_DTYPE_F32, b.data_ptr<float>(),
+                                          Z.data_ptr<float>(), sp[0], sp[1], sp[2], c.D),
+                          c.graph(), c.ws());
+    check_rc(rc, "forward_softmax");
+  }
+  return {Z, stats[0], stats[1], stats[2]};
+}
+
+// Its gradient with respect to X (hcspmm_softmax_backward) on the graph the backward walks: grad_Z, Z, M, L contiguous float32
+// [rows, D] of the forward, input the float32 [num_nodes, D] view the forward gathered
+torch::Tensor spmm_softmax_backward(torch::Tensor grad_Z, torch::Tensor Z, torch::Tensor M, torch::Tensor L, torch::Tensor input,
+                                    pybind11::object beta, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                    torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                    torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr) {
+  CHECK_INPUT(Z);
+  CHECK_INPUT(M);
+  CHECK_INPUT(L);
+  CHECK_CUDA(input);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
+              "input must be a 2-D float32 view with unit inner stride (softmax aggregation is float32 only)");
+  const int64_t n = nodePointer.size(0) - 1, D = input.size(1);
+  TORCH_CHECK(input.size(0) == n, "input has ", input.size(0), " rows but the walked graph has ", n, " nodes");
+  CallOptions o;
+  o.rect = true;  // grad_Z's rows are indexed by the walked graph's column ids
+  PlannedCall c(&grad_Z, grad_Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  TORCH_CHECK(grad_Z.size(1) == D && D > 0, "grad_Z must be a float32 [rows, D] tensor with D = ", D, " > 0, got ", grad_Z.sizes());
+  for (const torch::Tensor* t : {&Z, &M, &L})
+    TORCH_CHECK(t->scalar_type() == torch::kFloat && t->sizes() == grad_Z.sizes() && t->device() == input.device(),
+                "Z, M and L must be float32 tensors of grad_Z's shape on the device of the input");
+  TORCH_CHECK(grad_Z.device() == input.device(), "grad_Z must be on the device of the input");
+  TORCH_CHECK(c.E == 0 || grad_Z.size(0) > 0, "grad_Z has no rows but the walked graph has ", c.E, " entries");
+  const torch::Tensor b = beta_vector(beta, D, input);
+  auto grad_X = torch::empty({n, D}, grad_Z.options());
+  if (n == 0) return grad_X;
+  const bool any = grad_Z.numel() > 0;
+  const int rc = invoke(hcspmm_softmax_backward,
+                        std::make_tuple(any ? grad_Z.data_ptr<float>() : nullptr, any ? Z.data_ptr<float>() : nullptr,
+                                        any ? M.data_ptr<float>() : nullptr, any ? L.data_ptr<float>() : nullptr, D, grad_Z.size(0),
+                                        input.data_ptr<float>(), input.stride(0), b.data_ptr<float>(), grad_X.data_ptr<float>(), D),
+                        c.graph(), c.ws());
+  check_rc(rc, "softmax_backward");
+  return grad_X;
+}
+
 // Backward of forward_max / forward_min (hcspmm_forward_extremum_backward): square, pattern-symmetric graph, perm int32
 torch::Tensor spmm_forward_extremum_backward(torch::Tensor grad_Z, torch::Tensor arg, torch::Tensor perm, torch::Tensor nodePointer,
                                              torch::Tensor edgeList, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
@@ -1214,6 +1311,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
         pybind11::arg("col_nzr"), pybind11::arg("aggregates") = std::vector<std::string>{"sum", "sumsq", "max", "min"},
         pybind11::arg("return_arg") = true);
+  m.def("forward_softmax", &spmm_forward_softmax,
+        "per-channel softmax aggregation over each row's neighbours in one gather pass -> (Z, M, L, Q): Z = sum_e softmax_e(beta * "
+        "x_e) x_e, M = max_e beta x_e, L = sum_e exp(beta x_e - M), Q = sum_e p_e x_e^2; a statistic return_stats leaves out is None "
+        "(gfx950)",
+        pybind11::arg("input"), pybind11::arg("beta"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("return_stats") = true);
+  m.def("softmax_backward", &spmm_softmax_backward,
+        "gradient of forward_softmax with respect to X -> grad_X, on the graph the backward walks (A^T's tensors, or A's own for a "
+        "symmetric pattern); the weights are recomputed from M and L (gfx950)");
   m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
         "backward of forward_max / forward_min -> grad_X: a square, pattern-symmetric graph with perm = int32 transpose_permutation, "
         "or any square graph's A^T (transpose_graph's tensors and their preprocessing) with perm = entry_index_t (gfx950)");

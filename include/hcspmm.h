@@ -33,7 +33,8 @@ extern "C" {
  * hcspmm_forward_extremum, hcspmm_forward_extremum_backward (round 9); hcspmm_gatv2_scores, hcspmm_gatv2_backward_workspace_bytes,
  * hcspmm_gatv2_scores_backward (round 10); hcspmm_quantize_fp8, hcspmm_forward_fp8,
  * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14);
- * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15); hcspmm_softmax_workspace_bytes, hcspmm_forward_softmax,
+ * hcspmm_softmax_backward (round 17).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -482,6 +483,46 @@ int hcspmm_forward_multi(const void* X_d, int64_t x_rows, int64_t ldx, int dtype
                          const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
                          const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
                          int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-channel softmax aggregation of each row's neighbours in ONE gather pass (DeeperGCN / GENConv, PyG SoftmaxAggregation).
+ * With x_e = X[column_index[e]][d] and s_e = fl(beta[d] * x_e) over e in [row_pointers[r], row_pointers[r+1]):
+ *   Z[r][d] = sum_e p_e x_e,   p_e = exp(s_e) / sum_e' exp(s_e')
+ *   M[r][d] = max_e s_e (bit for bit)    L[r][d] = sum_e exp(s_e - M)    Q[r][d] = sum_e p_e fl(x_e * x_e)
+ * beta -> +inf / -inf approaches the max / min, beta = 0 is the mean.  One online-softmax pass: a running maximum, ONE
+ * exponential per gathered element, never with a positive argument, so any finite beta * x is safe.  Rows without entries
+ * get Z = Q = +0, M = -inf, L = 0.  A column stored twice in a row counts twice.  Fixed order (CSR order inside a lane group,
+ * the wide tasks' shuffle tree, split rows in slot order): deterministic, no atomics.  Defined for finite X and beta;
+ * other inputs give unspecified values but no out-of-range access.
+ * beta_d: [embedding_dim] fp32 on the device.  Z_d is required; M_d, L_d, Q_d may each be NULL and are then not written.  The
+ * four share the row stride ldz.  Other arguments as hcspmm_forward_multi (strided X, x_rows, rectangular blocks, with a plan
+ * or plan-free); workspace_d >= hcspmm_softmax_workspace_bytes() (four arrays per partial slot of a split row).
+ * fp32 only: another dtype, NULL X_d / beta_d / Z_d, ldx or ldz < embedding_dim and the other argument errors of
+ * hcspmm_forward_multi are HCSPMM_EINVAL before any device call.  num_nodes == 0 returns HCSPMM_OK without a launch.
+ * Asynchronous on `stream`.  Separate kernels (spmm_softmax.hip) on the binary product's plan.
+ *
+ * hcspmm_softmax_backward: the gradient with respect to X from grad_Z and the forward's Z, M, L ([src_rows] rows of one
+ * stride ld_in), on the graph the backward WALKS -- A^T's tensors and plan (hcspmm_transpose_graph), or A's own for a
+ * symmetric pattern; num_nodes rows, column ids below src_rows:
+ *   grad_X[j][d] = sum over the entries (j, i) of row j of
+ *                  exp(fl(beta[d] X[j][d]) - M[i][d]) / L[i][d] * grad_Z[i][d] * (1 + beta[d] (X[j][d] - Z[i][d]))
+ * X_d: the [num_nodes] rows the forward gathered (stride ldx).  The weight is recomputed, no per-entry tensor is read.  A
+ * plain-sum launch in hcspmm_forward_weighted's order; workspace_d >= hcspmm_workspace_bytes().  The gradient with respect
+ * to beta needs no kernel: sum_i grad_Z[i][d] (Q[i][d] - Z[i][d]^2).  Argument errors as above, for every operand.
+ * ---------------------------------------------------------------------------------------- */
+size_t hcspmm_softmax_workspace_bytes(const hcspmm_plan_header* header_h, int embedding_dim); /* 4 x hcspmm_workspace_bytes */
+int hcspmm_forward_softmax(const void* X_d, int64_t x_rows, int64_t ldx, int dtype, const float* beta_d, float* Z_d, float* M_d,
+                           float* L_d, float* Q_d, int64_t ldz, const int32_t* row_pointers_d, const int32_t* column_index_d,
+                           const int32_t* blockPartition_d, const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d,
+                           const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
+                           int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes,
+                           void* stream);
+int hcspmm_softmax_backward(const float* grad_Z_d, const float* Z_d, const float* M_d, const float* L_d, int64_t ld_in,
+                            int64_t src_rows, const float* X_d, int64_t ldx, const float* beta_d, float* grad_X_d, int64_t ldgx,
+                            const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                            const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                            const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
+                            int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge-feature messages (GINE, SchNet / CFConv continuous filters, edge-gated convolutions, "sum the incident edge vectors"):
