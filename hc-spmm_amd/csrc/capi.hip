@@ -263,6 +263,7 @@ int bind_graph(hcspmm::PlanArgs& p, const GraphIn& g, int D, int64_t src_rows, v
   p.partial = need ? reinterpret_cast<float*>(workspace) : nullptr;
   p.plan = g.plan_d;
   p.off_tasks = ph->off_tasks;
+  p.off_sched = ph->off_tasks;  // (use_schedule moves the binary product onto the exact-length copies)
   p.n_tasks = ph->n_tasks;
   p.n_tiny = ph->n_tiny;
   p.off_slice_table = ph->off_slice_table;
@@ -280,6 +281,14 @@ int bind_graph(hcspmm::PlanArgs& p, const GraphIn& g, int D, int64_t src_rows, v
   p.n_split_rows = ph->n_split_rows;
   wide_choice(ph, D, dtype, &p.n_wide, &p.panel_cols);
   return HCSPMM_OK;
+}
+
+// The binary product (launches of spmm_impl.h) reads its wide, ordinary and sliced descriptors from the plan's schedule copies
+// where the plan has them (hcspmm.h off_task_sched): the same tasks, each summed by the same lanes in the same order, with the
+// lane groups of a wave ending together.  The tiny tasks, the fix-up pass and every other launch keep the lists as they are.
+inline void use_schedule(hcspmm::PlanArgs& p, const hcspmm_plan_header* ph) {
+  if (ph->off_task_sched != 0) p.off_sched = ph->off_task_sched;
+  if (ph->off_slice_sched != 0) p.off_slice_tasks = ph->off_slice_sched;
 }
 
 inline void set_operands(hcspmm::PlanArgs& p, const void* X, void* Z, int64_t ldx, int64_t ldz) {
@@ -349,6 +358,7 @@ int forward_impl(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ld
       else if (heads > 0) e = launch_plan_wh_f32(WHPlanArgs{wa, (long long)g.E, D / heads, nullptr}, vec, stream);
       else e = launch_typed(dtype, launch_plan_w_f32, launch_plan_w_f16, launch_plan_w_bf16, wa, vec, stream);
     } else {
+      if (!fused) use_schedule(a, g.ph);
       e = launch_typed(dtype, launch_plan_f32, launch_plan_f16, launch_plan_bf16, a, vec, stream);
     }
   } else {
@@ -448,6 +458,7 @@ extern "C" int hcspmm_forward_fp8(const void* Xq, int64_t x_rows, int64_t ldx, i
   hipError_t e;
   if (a.plan) {
     if (binary) {
+      use_schedule(a, ph);
       e = hcspmm::launch_plan_f8(a, vec, stream);
     } else {
       a.row_scale = row_scale;

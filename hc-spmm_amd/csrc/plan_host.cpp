@@ -32,9 +32,16 @@
 //             67 %, the launch 17 % faster and no longer bound by the fabric).  A column slice of a column-sorted row
 //             is a contiguous CSR range, so the pieces are ordinary (row, first, length, slot) tasks whose partial
 //             sums the fix-up pass adds in slice order = CSR order.
+//   schedule : copies of the non-tiny tasks and of the slice lists in EXACT descending length order (ties in list order), which
+//             the binary product's launch reads instead of the lists above.  The eight lane groups of a wave loop to the
+//             longest of their eight tasks and issue dummy gathers once their own has ended; inside a power-of-two class
+//             lengths differ by up to 2x (28 % of the gathers of the Reddit-scale headline are such dummies), in exact
+//             order by almost nothing (2 %).  The lists above keep their order: every other launch, and the tests that
+//             pin "class, then rows ascending", read them.
 // Blob layout (int32 words): header[64] | tasks[n_tasks][4] | dense_index[n_dense][4] |
 // dense_pack[...] | compact2[n_dense_compact2][128] | compact[n_dense_compact][64] | fixups[n_split_rows][4] |
-// sparse_windows[n_sparse_windows] | slice_table[n_slices + 1] | slice_tasks[n_slice_tasks][4].
+// sparse_windows[n_sparse_windows] | slice_table[n_slices + 1] | slice_tasks[n_slice_tasks][4] |
+// task_sched[n_tasks - n_tiny][4] | slice_sched[n_slice_tasks][4].
 // All section offsets are multiples of 4 words, the compact sections' of 64.  With slices the sections are sized
 // by upper bounds that do not depend on the column ids (hcspmm_plan_words has none): the header holds the real counts.
 #include <algorithm>
@@ -63,11 +70,20 @@ constexpr int64_t kSliceAutoMinColumns = 65536;  // a 128-byte line per X row: b
 constexpr int64_t kSliceAutoAlwaysColumns = 250000;
 constexpr int64_t kSliceAutoMinEntries = 3000000;
 constexpr int kSliceSample = 4;                  // the boundary histogram looks at every 4th entry of the long rows
+// The schedule copies are built when one 128-byte line per X row fits the 256 MiB Infinity Cache.  Exact length order gives up
+// part of the row order inside a class, i.e. the closeness of neighbouring waves' Z stores, index and descriptor reads.
+// Measured with the copies forced (profiles/r18/ab_task_schedule.log, schedule_counters.log): RD-sized D = 32 (4.86 M columns)
+// +0.6 % and +1.8 % in two jobs, its hybrid launch missing L2 2.2 % more often and fetching 2.4 % more bytes from HBM; 16 M-column
+// share D = 128 +0.4 %; 233 K columns -2.4 ... -3.0 %.  The slot count falls by 17-26 % of the useful slots on all three, so
+// the count does not tell them apart.  Three graphs stand behind the rule: WHERE between 233 K and 4.86 M columns the sign
+// turns is not measured -- the boundary is the cache's size, a hypothesis that fits them.
+constexpr int64_t kScheduleMaxColumns = (256ll << 20) / 128;
 constexpr int kSlicePad = 64;                    // slice lists are padded to whole waves of any lane-group count (4 waves x 16)
 
 struct Resolved {
   int32_t split_threshold, segment_len, fuse_in_launch;
   int32_t slice_mode, slice_threshold, n_slices, panel_cols;
+  int32_t schedule;  // the exact-length copies of the task lists: 0 off, > 0 on, < 0 decided by hcspmm_plan_build (kScheduleMaxColumns)
 };
 
 int env_int(const char* name, int dflt) {
@@ -76,7 +92,7 @@ int env_int(const char* name, int dflt) {
 }
 
 Resolved resolve(const hcspmm_plan_params* p) {
-  Resolved r{512, 256, 0, kSliceAuto, kSliceAutoThreshold, 8, 0};
+  Resolved r{512, 256, 0, kSliceAuto, kSliceAutoThreshold, 8, 0, -1};
   if (p) {
     if (p->split_threshold > 0) r.split_threshold = p->split_threshold;
     if (p->segment_len > 0) r.segment_len = p->segment_len;
@@ -89,6 +105,7 @@ Resolved resolve(const hcspmm_plan_params* p) {
   if (thr > 0) { r.slice_mode = kSliceOn; r.slice_threshold = thr; }
   else if (thr < 0) r.slice_mode = kSliceOff;
   if (ns > 0) r.n_slices = std::min(64, (ns + 7) / 8 * 8);
+  r.schedule = env_int("HCSPMM_TASK_SCHEDULE", -1);  // A/B runs and the fallback: 0 leaves both schedule sections out, 1 forces them
   if (p && p->panel_cols != 0) r.panel_cols = p->panel_cols < 0 ? -1 : std::min(1 << 20, (p->panel_cols + 15) / 16 * 16);
   return r;
 }
@@ -124,14 +141,14 @@ inline void for_each_piece(const int32_t* cuts, int32_t e0, int S, int32_t seg, 
 inline int64_t align4(int64_t x) { return (x + 3) & ~int64_t(3); }
 
 struct Layout {
-  int64_t n_tasks = 0, n_dense = 0, n_compact = 0, n_compact2 = 0, n_split_rows = 0, n_partials = 0;
+  int64_t n_tasks = 0, n_tiny = 0, n_dense = 0, n_compact = 0, n_compact2 = 0, n_split_rows = 0, n_partials = 0;
   int64_t dense_pack_words = 0;
   int64_t nnz_sparse = 0, nnz_dense = 0, dense_k_sum = 0;
   int32_t max_dense_k = 0;
   int64_t n_sparse_windows = 0;
   int64_t n_slice_tasks = 0, n_sliced_rows = 0, nnz_sliced = 0;  // with slices: n_slice_tasks, n_split_rows, n_partials are upper bounds
   int64_t off_tasks = 0, off_dense_index = 0, off_dense_pack = 0, off_compact2 = 0, off_compact = 0, off_fixups = 0,
-          off_sparse_windows = 0, off_slice_table = 0, off_slice_tasks = 0, total = 0;
+          off_sparse_windows = 0, off_slice_table = 0, off_slice_tasks = 0, off_task_sched = 0, off_slice_sched = 0, total = 0;
 };
 
 // The workers of ONE hcspmm_plan_build / hcspmm_plan_words call: started once, handed the call's passes one after the other (a
@@ -251,10 +268,13 @@ int compute_layout(const int32_t* rowptr, int64_t N, const int32_t* bp, const in
           } else if (d > rp.split_threshold) {
             const int64_t segs = (d + rp.segment_len - 1) / rp.segment_len;
             L.n_tasks += segs;
+            // (segments of at most HCSPMM_TINY_LEN entries are all tiny; otherwise only a row's last one can be)
+            L.n_tiny += rp.segment_len <= HCSPMM_TINY_LEN ? segs : (d - (segs - 1) * rp.segment_len <= HCSPMM_TINY_LEN);
             L.n_partials += segs;
             L.n_split_rows++;
           } else {
             L.n_tasks++;
+            L.n_tiny += d <= HCSPMM_TINY_LEN;
           }
         }
         L.nnz_sparse += nnz;
@@ -266,7 +286,7 @@ int compute_layout(const int32_t* rowptr, int64_t N, const int32_t* bp, const in
   for (int t = 0; t < T; ++t) {
     if (bad[(size_t)t]) return HCSPMM_EINVAL;
     const Layout& p = part[(size_t)t];
-    L.n_tasks += p.n_tasks; L.n_dense += p.n_dense; L.n_compact += p.n_compact; L.n_compact2 += p.n_compact2;
+    L.n_tasks += p.n_tasks; L.n_tiny += p.n_tiny; L.n_dense += p.n_dense; L.n_compact += p.n_compact; L.n_compact2 += p.n_compact2;
     L.n_split_rows += p.n_split_rows; L.n_partials += p.n_partials; L.dense_pack_words += p.dense_pack_words;
     L.nnz_sparse += p.nnz_sparse; L.nnz_dense += p.nnz_dense; L.dense_k_sum += p.dense_k_sum;
     L.n_sparse_windows += p.n_sparse_windows;
@@ -284,9 +304,59 @@ int compute_layout(const int32_t* rowptr, int64_t N, const int32_t* bp, const in
   L.off_slice_table = align4(L.off_sparse_windows + L.n_sparse_windows);
   L.off_slice_tasks = slicing ? align4(L.off_slice_table + rp.n_slices + 1) : L.off_slice_table;
   L.total = align4(L.off_slice_tasks + 4 * (slicing ? L.n_slice_tasks : 0));
+  if (rp.schedule) {  // the schedule copies: the non-tiny tasks, then (with slices) the slice lists under the same table
+    L.off_task_sched = L.total;
+    L.total += 4 * (L.n_tasks - L.n_tiny);
+    if (slicing) {
+      L.off_slice_sched = L.total;
+      L.total += 4 * L.n_slice_tasks;
+    }
+  }
   if (L.total > INT32_MAX) return HCSPMM_ERANGE;
   *out = L;
   return HCSPMM_OK;
+}
+
+// dst = the n descriptors (row, first, length, slot) of src by descending length, equal lengths in src's order; lengths lie in
+// [0, max_len].  T threads take contiguous shares of src: a share's descriptors of one length follow those of the shares
+// before it, so the result is the same for every T.
+void sort_by_length(const int32_t* src, int32_t* dst, int64_t n, int32_t max_len, int T) {
+  if (n <= 0) return;
+  if (n < 65536) T = 1;
+  int32_t longest = 0;
+  {
+    std::vector<int32_t> part((size_t)T, 0);
+    parallel_for(T, [&](int t) {
+      int32_t m = 0;
+      for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) m = std::max(m, src[4 * i + 2]);
+      part[(size_t)t] = m;
+    });
+    for (int t = 0; t < T; ++t) longest = std::max(longest, part[(size_t)t]);
+  }
+  longest = std::min(longest, max_len);  // (the plan's own lists never exceed split_threshold: resolve() caps segment_len at it)
+  const size_t nb = (size_t)longest + 1;
+  if (nb * (size_t)T > ((size_t)1 << 24)) T = 1;  // a giant split_threshold with rows to match: one histogram
+  std::vector<std::vector<int64_t>> at((size_t)T);
+  parallel_for(T, [&](int t) {
+    std::vector<int64_t> h(nb, 0);
+    for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) h[(size_t)std::min(std::max(src[4 * i + 2], 0), longest)]++;
+    at[(size_t)t].swap(h);
+  });
+  int64_t run = 0;
+  for (size_t len = nb; len-- > 0;)
+    for (int t = 0; t < T; ++t) {
+      const int64_t c = at[(size_t)t][len];
+      at[(size_t)t][len] = run;
+      run += c;
+    }
+  parallel_for(T, [&](int t) {
+    std::vector<int64_t> cur;
+    cur.swap(at[(size_t)t]);  // thread-private cursors
+    for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) {
+      const int64_t q = cur[(size_t)std::min(std::max(src[4 * i + 2], 0), longest)]++;
+      std::memcpy(dst + 4 * q, src + 4 * i, 16);
+    }
+  });
 }
 
 }  // namespace
@@ -372,7 +442,8 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
     if (frc != HCSPMM_OK) return frc;
   }
   tp[1] = now();
-  const Resolved rp = resolve(params);
+  Resolved rp = resolve(params);
+  rp.schedule = rp.schedule < 0 ? (M <= kScheduleMaxColumns) : (rp.schedule != 0);
   Layout L;
   int rc = HCSPMM_OK;
   // XCD-affine slices: asked for, or (automatic) worth it -- X spans many L2s and the long rows hold a real share
@@ -402,7 +473,8 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
   {  // zero what the passes below do not overwrite word for word: everything behind the task list (masks are OR-ed
      // in, records and section gaps are padded).  The task list itself -- 16 bytes per row, 78 of the 80 MB of a
      // 4.9 M-row plan -- is written completely, so it is not cleared first.
-    const int64_t z0 = L.off_dense_index, zn = L.total - z0;
+    // (The schedule copies behind the lists are written completely as well, but for the slack of the slice copy: cleared where it is built.)
+    const int64_t z0 = L.off_dense_index, zn = (L.off_task_sched ? L.off_task_sched : L.total) - z0;
     std::vector<int64_t> zc((size_t)T + 1);
     for (int t = 0; t <= T; ++t) zc[(size_t)t] = z0 + zn * t / T;
     parallel_for(T, [&](int t) {
@@ -553,11 +625,12 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
   if (slicing ? (fix_at[(size_t)T] > L.n_split_rows || slot_at[(size_t)T] > L.n_partials)
               : (fix_at[(size_t)T] != L.n_split_rows || slot_at[(size_t)T] != L.n_partials))
     return HCSPMM_EINVAL;
-  if (dense_at[(size_t)T] != L.n_dense || start.back() != L.n_tasks || sparse_w_at[(size_t)T] != L.n_sparse_windows)
+  if (dense_at[(size_t)T] != L.n_dense || start.back() != L.n_tasks || sparse_w_at[(size_t)T] != L.n_sparse_windows ||
+      n_tiny != L.n_tiny)
     return HCSPMM_EINVAL;
   // slice lists: slice s owns descriptors [table[s], table[s+1]) (padded to whole waves), longest class first, and inside a
   // class the threads' shares in range order (= rows ascending)
-  std::vector<int64_t> table((size_t)S + 1, 0);
+  std::vector<int64_t> table((size_t)S + 1, 0), slice_real((size_t)S, 0);  // slice_real: descriptors of a list without its padding
   std::vector<std::vector<int64_t>> spos((size_t)T, std::vector<int64_t>((size_t)S * (size_t)n_cls, 0));
   int64_t slice_xcd_tasks = 0;
   if (slicing) {
@@ -569,6 +642,7 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
           spos[(size_t)t][(size_t)sl * (size_t)n_cls + (size_t)c] = run;
           run += cnt[(size_t)t].slice_cls[(size_t)sl * (size_t)n_cls + (size_t)c];
         }
+      slice_real[(size_t)sl] = run - table[(size_t)sl];
       const int64_t padded = (run - table[(size_t)sl] + kSlicePad - 1) / kSlicePad * kSlicePad;
       int32_t* pad = plan + L.off_slice_tasks;
       for (int64_t q = run; q < table[(size_t)sl] + padded; ++q) {
@@ -627,6 +701,26 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
            sout[4 * q + 3] = slot_id;
          });
   });
+
+  // ---- schedule copies (see the head of the file): stable counting sorts by descending length.  A descriptor's slot is the
+  // number of longer ones plus the number of equally long ones before it in its list: the same for every thread count.
+  if (rp.schedule) {
+    const int64_t n_nt = L.n_tasks - L.n_tiny;
+    sort_by_length(out, plan + L.off_task_sched, n_nt, rp.split_threshold, T);
+    if (slicing) {
+      int32_t* ssched = plan + L.off_slice_sched;
+      std::atomic<int> next_list{0};
+      parallel_for(T, [&](int) {  // one list at a time per thread; a list's result does not depend on who sorts it
+        for (int sl; (sl = next_list.fetch_add(1, std::memory_order_relaxed)) < S;) {
+          const int64_t lo = table[(size_t)sl], real = slice_real[(size_t)sl];
+          sort_by_length(sout + 4 * lo, ssched + 4 * lo, real, rp.split_threshold, 1);
+          std::memcpy(ssched + 4 * (lo + real), sout + 4 * (lo + real), 16 * (size_t)(table[(size_t)sl + 1] - lo - real));  // padding
+        }
+      });
+      // the section is sized by the lists' bound: clear what lies behind the last list
+      std::memset(ssched + 4 * table[(size_t)S], 0, 16 * (size_t)(L.n_slice_tasks - table[(size_t)S]));
+    }
+  }
 
   tp[5] = now();
   // ---- dense windows: widest first (stable, so window order inside a width); pack U and the MFMA lane masks
@@ -726,6 +820,8 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
   h.nnz_sliced = slicing ? (int32_t)L.nnz_sliced : 0;
   h.n_sliced_rows = slicing ? (int32_t)L.n_sliced_rows : 0;
   h.panel_cols = rp.panel_cols;
+  h.off_task_sched = (int32_t)L.off_task_sched;
+  h.off_slice_sched = (int32_t)L.off_slice_sched;
   static_assert(sizeof(hcspmm_plan_header) == HCSPMM_PLAN_HEADER_WORDS * 4, "header size");
   std::memcpy(plan, &h, sizeof(h));
   if (dbg) {
@@ -778,6 +874,17 @@ extern "C" int hcspmm_plan_check(const hcspmm_plan_header* h, int64_t N, int64_t
   } else if (h->n_slice_tasks != 0 || h->slice_xcd_tasks != 0) {
     return HCSPMM_EPLAN;
   }
+  // the schedule copies, each absent (0) or behind every earlier section and inside the blob
+  const int64_t lists_end = h->n_slices > 0 ? h->off_slice_tasks + 4 * (int64_t)h->n_slice_tasks
+                                            : h->off_sparse_windows + (int64_t)h->n_sparse_windows;
+  const int64_t n_nt = (int64_t)h->n_tasks - h->n_tiny;
+  if (h->off_task_sched != 0 &&
+      (h->off_task_sched < lists_end || (h->off_task_sched & 3) || h->total_words < h->off_task_sched + 4 * n_nt))
+    return HCSPMM_EPLAN;
+  if (h->off_slice_sched != 0 &&
+      (h->n_slices == 0 || h->off_task_sched == 0 || h->off_slice_sched < h->off_task_sched + 4 * n_nt || (h->off_slice_sched & 3) ||
+       h->total_words < h->off_slice_sched + 4 * (int64_t)h->n_slice_tasks))
+    return HCSPMM_EPLAN;
   if (words_available > 0 && h->total_words > words_available) return HCSPMM_EPLAN;
   if ((int64_t)h->nnz_sparse + h->nnz_dense != E) return HCSPMM_EPLAN;
   return HCSPMM_OK;

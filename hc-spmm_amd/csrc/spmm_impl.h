@@ -817,7 +817,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
       // wide tasks: the a.n_wide longest tasks, one per wave
       const int tid = bf * kWaves + wave;
       if (tid >= a.n_wide) return;
-      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
+      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_sched)[tid];
       typename E::Z* dz = (t.w < 0) ? Z + (size_t)t.x * a.ldz : nullptr;
       float* dp = (t.w < 0) ? nullptr : a.partial + (size_t)t.w * (size_t)a.D;
       sparse_task<E, L, VEC, true, UNROLL>(X, dz, dp, a.col, a.E, __builtin_amdgcn_readfirstlane(t.y),
@@ -851,7 +851,7 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
         }
       } else {
         const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
+        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_sched) + tid;
       }
       int e0 = 0, n = 0;
       typename E::Z* dz = nullptr;

@@ -50,6 +50,9 @@ struct PlanArgs {
   // entries of col: the 16-byte index loads of sparse_task stay inside col[0, E).  (Last, so that no other member moves: one
   // more dword in the middle cost the 16-bit weighted L = 32 build four more bytes of scratch.)
   int E;
+  // where the wide and the ordinary regions of the binary product's launch read their descriptors: off_tasks, or the plan's
+  // exact-length schedule copy of the non-tiny tasks (hcspmm.h off_task_sched).  (Last as well, for the same reason.)
+  int off_sched;
 };
 
 // Arguments of the row-tile fused launch (fused_rows.hip): the planned launch's arguments (Z = out2; W / out / H set) plus the

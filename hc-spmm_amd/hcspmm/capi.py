@@ -33,7 +33,9 @@ class Header(ctypes.Structure):
                                                                                   ("off_slice_table", ctypes.c_int32), ("off_slice_tasks", ctypes.c_int32),
                                                                                   ("n_slice_tasks", ctypes.c_int32), ("slice_xcd_tasks", ctypes.c_int32),
                                                                                   ("nnz_sliced", ctypes.c_int32), ("n_sliced_rows", ctypes.c_int32),
-                                                                                  ("panel_cols", ctypes.c_int32), ("reserved", ctypes.c_int32 * 18)]
+                                                                                  ("panel_cols", ctypes.c_int32),
+                                                                                  ("off_task_sched", ctypes.c_int32), ("off_slice_sched", ctypes.c_int32),
+                                                                                  ("reserved", ctypes.c_int32 * 16)]
 
     @property
     def fingerprint(self):

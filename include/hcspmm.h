@@ -109,7 +109,7 @@ int hcspmm_edge_to_row_device(const int32_t* row_pointers_d, int64_t num_nodes, 
  * read-back).
  * ---------------------------------------------------------------------------------------- */
 #define HCSPMM_PLAN_MAGIC 0x48435350 /* "HCSP" */
-#define HCSPMM_PLAN_VERSION 7
+#define HCSPMM_PLAN_VERSION 8
 #define HCSPMM_TINY_LEN 2 /* tasks of at most this many entries carry their indices in the descriptor */
 #define HCSPMM_COMPACT_K 40     /* dense windows of at most this many (padded) columns use compact records ... */
 #define HCSPMM_COMPACT_WORDS 64 /* ... of this many words: [window, K/4, U[40], 10 x (mask lo, mask hi), pad] */
@@ -126,7 +126,8 @@ typedef struct hcspmm_plan_header {
   int32_t num_windows;      /* W */
   int32_t split_threshold;  /* rows with more entries than this are split ... */
   int32_t segment_len;      /* ... into segments of this many entries */
-  int32_t n_tasks;          /* sparse-row tasks (one per whole row or row segment), by descending length class */
+  int32_t n_tasks;          /* sparse-row tasks (one per whole row or row segment), by descending power-of-two length class,
+                               rows ascending inside a class (off_task_sched: the same in exact length order) */
   int32_t n_dense;          /* dense-tile windows */
   int32_t n_split_rows;     /* rows whose partial sums are combined by the fix-up pass */
   int32_t n_partials;       /* partial-sum slots (rows of the workspace) */
@@ -175,7 +176,17 @@ typedef struct hcspmm_plan_header {
   int32_t n_sliced_rows;
   int32_t panel_cols;       /* hcspmm_plan_params.panel_cols: 0 = the launch chooses, > 0: feature columns per
                                sparse pass for fp32 features (16-bit features: twice as many), < 0: one pass over all columns */
-  int32_t reserved[18];
+  /* Schedule copies: the same descriptors in exact descending length order, equal lengths in the order of
+   * the list they were copied from, so that the lane groups of a wave end together.  The binary product's launch reads them
+   * in place of the lists above.  Built when num_columns <= 2 097 152 (one 128-byte line per X row fits the Infinity Cache:
+   * measured a gain at 233 K columns and a loss at 4.86 M and 16 M, where the lost row order costs L2 hits; the boundary between
+   * them is not measured); HCSPMM_TASK_SCHEDULE=0 / 1 in the
+   * environment at plan build forces them off / on.  Both offsets are 0 when absent. */
+  int32_t off_task_sched;   /* n_tasks - n_tiny descriptors: the non-tiny prefix of the task list.  Its first n_len_gt[b]
+                               are still exactly the tasks longer than 16 << b.  0: absent */
+  int32_t off_slice_sched;  /* n_slice_tasks descriptors under the same slice table: every list's real descriptors in that
+                               order, its padding behind them.  0: absent (always when n_slices == 0) */
+  int32_t reserved[16];
 } hcspmm_plan_header;
 
 #define HCSPMM_PLAN_FUSE_IN_LAUNCH 1

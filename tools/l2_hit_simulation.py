@@ -4,7 +4,7 @@ column slices -- rows longer than a threshold cut at S column boundaries, slice 
 blockIdx % 8 == s % 8, so each L2 holds 1/8 (S = 8) of the X rows those tasks touch.  Host-only (numpy + a small C
 helper compiled on the fly); results quoted in DESIGN.md.
 
-  python tools/l2_hit_simulation.py [--workload reddit] [--thresholds 512,128,64] [--slices 8,16]
+  python tools/l2_hit_simulation.py [--workload reddit] [--thresholds 512,128,64] [--slices 8,16] [--order class|exact]
 """
 import argparse
 import ctypes
@@ -45,11 +45,13 @@ def cut_segments(row, e0, ln, seg):
     return row[idx], e0[idx] + k * seg, np.minimum(seg, ln[idx] - k * seg)
 
 
-def class_order(row, ln):
-    return np.lexsort((row, -length_class(ln)))
+def class_order(row, ln, exact=False):
+    """The plan's lists: descending power-of-two length class, rows ascending inside a class; or (exact) their schedule
+    copies (hcspmm.h off_task_sched): descending length, equal lengths in list order = rows ascending."""
+    return np.lexsort((row, -(ln if exact else length_class(ln))))
 
 
-def build_schedule(rp, col, n_cols, thr, S, seg=256, split=512, tasks_per_wg=32, n_xcd=8, interleave=False):
+def build_schedule(rp, col, n_cols, thr, S, seg=256, split=512, tasks_per_wg=32, n_xcd=8, interleave=False, exact=False):
     """-> per-XCD (e0, len, kind, wg_start) + statistics.  thr <= 0: the round-2 schedule (rows > split cut every seg entries)."""
     N = len(rp) - 1
     deg = np.diff(rp).astype(np.int64)
@@ -79,7 +81,7 @@ def build_schedule(rp, col, n_cols, thr, S, seg=256, split=512, tasks_per_wg=32,
         stats["slice_cols"] = np.diff(np.concatenate([[0], bounds, [n_cols]])).tolist()
         for s in range(S):
             m = q_sl == s
-            o = class_order(q_row[m], q_len[m])
+            o = class_order(q_row[m], q_len[m], exact)
             x = s % n_xcd
             per_xcd[x]["e0"].append(q_e0[m][o])
             per_xcd[x]["ln"].append(q_len[m][o])
@@ -100,7 +102,7 @@ def build_schedule(rp, col, n_cols, thr, S, seg=256, split=512, tasks_per_wg=32,
         ln = np.concatenate(per_xcd[x]["ln"]) if per_xcd[x]["ln"] else np.empty(0, np.int64)
         kd = np.concatenate(per_xcd[x]["kind"]) if per_xcd[x]["kind"] else np.empty(0, np.int8)
         wg_lists.append([e0, ln, kd])
-    o = class_order(f_row, f_len)
+    o = class_order(f_row, f_len, exact)
     f_e0, f_len = f_e0[o], f_len[o]
     n_free_wg = (len(f_e0) + tasks_per_wg - 1) // tasks_per_wg
     out = []
@@ -155,6 +157,8 @@ def main():
     ap.add_argument("--lines", type=int, default=32768)
     ap.add_argument("--conc", type=int, default=160)
     ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--order", default="class", choices=["class", "exact"],
+                    help="task order inside every list: the plan's lists (length class, then rows) or its schedule copies (exact length)")
     ap.add_argument("--interleave", action="store_true", help="sliced and free workgroups alternate instead of sliced first")
     args = ap.parse_args()
     sys.path.insert(0, R)
@@ -164,12 +168,13 @@ def main():
     N, E, n_cols = len(rp) - 1, len(col), n_local * vw
     lib = _lib()
     panels = max(1, args.dim // 32)
+    print("task order: %s" % args.order)
     print("%s: N=%d E=%d columns=%d; X panel = %.1f MB; L2 lines per XCD %d; %d panels" % (args.workload, N, E, n_cols, n_cols * 128 / 1e6, args.lines, panels))
     print("thr    S | hit_all hit_sliced hit_free | sliced_nnz%% partials | est. traffic/launch GB (X miss + partials w+r + Z + idx) | max/mean XCD nnz")
     for thr in [int(t) for t in args.thresholds.split(",")]:
         for S in ([0] if thr <= 0 else [int(s) for s in args.slices.split(",")]):
             t0 = time.time()
-            sched, st = build_schedule(rp, col, n_cols, thr, S, interleave=args.interleave)
+            sched, st = build_schedule(rp, col, n_cols, thr, S, interleave=args.interleave, exact=args.order == "exact")
             hits, tot = simulate(lib, col, n_cols, sched, args.lines, args.conc)
             miss = (tot - hits).sum()
             traffic = panels * (miss * 128 + st["n_partials"] * 128 * 2 + N * 128) + 4 * E * panels + 4 * (N + 1)
