@@ -256,6 +256,35 @@ def transposed_graph(graph):
     return out
 
 
+_SAMPLE_ROW_POINTERS = {}  # (row_pointers pointer and size, fanout) -> (weak ref, row_pointers_s): one scan per (graph, fanout)
+
+
+def sampled_graph(graph, fanout, seed):
+    """A fanout-limited random neighbourhood of every node (GraphSAGE's; redraw it every epoch with seed = the epoch) ->
+    (graph_s, entry_index_s): graph_s = the eight graph tensors of the sample (HCSPMM.sample_neighbors, then
+    HCSPMM.plan_free_graph: every entry point takes its plan-free sparse-row path), entry_index_s = int32 [E_s], the position in
+    A of every kept entry (edge values of A travel as values[entry_index_s]).  A sample is a directed graph: its transpose is
+    built on the device as well (HCSPMM.transpose_graph_device, plan_free_graph) and entered where transposed_graph looks, so
+    every directed=True layer and function works on graph_s as it stands and nothing is copied to the host.  row_pointers_s
+    depends on the graph and the fanout only and is made once for them; graph = the eight graph tensors of A."""
+    import weakref
+    row_pointers, column_index = graph[0], graph[1]
+    key = (row_pointers.data_ptr(), row_pointers.numel(), int(fanout))
+    hit = _SAMPLE_ROW_POINTERS.get(key)
+    if hit is None or hit[0]() is not row_pointers:
+        for k in [k for k, v in _SAMPLE_ROW_POINTERS.items() if v[0]() is None]:
+            del _SAMPLE_ROW_POINTERS[k]
+        hit = _SAMPLE_ROW_POINTERS[key] = (weakref.ref(row_pointers), HCSPMM.sample_row_pointers(row_pointers, int(fanout)))
+    rp_s, col_s, eid_s = HCSPMM.sample_neighbors(row_pointers, column_index, int(fanout), int(seed), hit[1])
+    graph_s = tuple(HCSPMM.plan_free_graph(rp_s, col_s))
+    rp_t, col_t, eid_t = HCSPMM.transpose_graph_device(rp_s, col_s)
+    for k in [k for k, v in _TRANSPOSED_GRAPH.items() if v[0]() is None or v[1]() is None]:
+        del _TRANSPOSED_GRAPH[k]
+    _TRANSPOSED_GRAPH[(rp_s.data_ptr(), col_s.data_ptr(), rp_s.numel(), col_s.numel())] = (
+        weakref.ref(rp_s), weakref.ref(col_s), tuple(HCSPMM.plan_free_graph(rp_t, col_t)) + (eid_t,))
+    return graph_s, eid_s
+
+
 class EdgeWeightedAggregateDirected(torch.autograd.Function):
     """A_w X on any square graph, edge_weight [E] or [heads, E]: the forward is EdgeWeightedAggregate(Heads)'s;
     dX = A_w^T dY = HCSPMM.forward_weighted_indexed(dY, w, entry_index_t) on A^T's graph tensors and plan (the values are read

@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, SAGEConv, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, SAGEConv, sampled_graph, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -74,7 +74,20 @@ def parse_args(argv=None):
     # addition: --model gen (GNN_model.GENConv: DeeperGCN's softmax aggregation, out = (x + sum_j softmax_j(t x_j) x_j) W)
     p.add_argument("--gen-t", type=float, default=1.0, help="inverse temperature t of --model gen")
     p.add_argument("--gen-learn-t", action="store_true", help="--model gen: learn t (one scalar per layer)")
+    # addition: GraphSAGE's neighbour sampling (GNN_model.sampled_graph): every epoch trains on a fresh sample of at most K
+    # neighbours per node, drawn on the device with seed = the epoch; a sample is a directed graph, so this implies --directed
+    p.add_argument("--sample-fanout", type=int, default=0,
+                   help="train every epoch on a fresh sample of at most K neighbours per node (0: off); implies --directed")
     args = p.parse_args(argv)
+    if args.sample_fanout < 0:
+        p.error("--sample-fanout must not be negative")
+    if args.sample_fanout > 0:
+        if args.model in ("gcn", "gin") and args.norm == "none":
+            p.error("--sample-fanout with --model %s needs --norm: a sample is a directed graph, and the fused binary layer "
+                    "functions have no directed form (their backward aggregates with A, as the reference does)" % args.model)
+        if args.graph:
+            p.error("--sample-fanout redraws the graph every epoch: the step cannot be replayed from a HIP graph")
+        args.directed = True
     if args.model == "gen" and args.aggr is not None:
         p.error("--aggr does not apply to --model gen: GENConv aggregates with its softmax weights")
     if args.model == "gen" and args.norm != "none":
@@ -252,8 +265,22 @@ def main(argv=None):
         set_feature_storage(model, "fp8")
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 
+    epoch = [0]
+
+    def draw_sample():
+        """this epoch's sample in the model's place of the graph, with the edge values that go with it"""
+        graph_s, entry_index_s = sampled_graph(graph, args.sample_fanout, seed=epoch[0])
+        epoch[0] += 1
+        model.graph = graph_s
+        if edge_weight is not None:  # the normalisation of the SAMPLED graph: its degrees are the sample's
+            model.ew["edge_weight"] = HCSPMM.edge_norm(graph_s[0], graph_s[1], args.norm)
+        if edge_attr is not None:  # an entry's attributes travel with it
+            model.ew["edge_attr"] = edge_attr[entry_index_s.long()]
+
     def train():
         model.train()
+        if args.sample_fanout > 0:
+            draw_sample()
         optimizer.zero_grad()
         loss = nll_loss(model()[:], dataset.y[:])
         loss.backward()
@@ -287,6 +314,15 @@ def main(argv=None):
     torch.cuda.synchronize()
     print("Train (ms/epoch):\t{:.3f}\tfinal loss {:.4f}".format((time.perf_counter() - t0) * 1e3 / max(args.epochs, 1),
                                                                  float(loss.detach()) if loss is not None else float("nan")))
+    if args.sample_fanout > 0:  # evaluation aggregates over the full neighbourhoods
+        model.graph = graph
+        if edge_weight is not None:
+            model.ew["edge_weight"] = edge_weight
+        if edge_attr is not None:
+            model.ew["edge_attr"] = edge_attr
+        model.eval()
+        with torch.no_grad():
+            print("Eval (full graph):\tloss {:.4f}".format(float(nll_loss(model(), dataset.y))))
     if args.fp8:
         log_probs = {}
         model.eval()

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "fingerprint.h"
+#include "graph_build.h"
 #include "hcspmm.h"
 #include "spmm_kernels.h"
 
@@ -194,6 +195,50 @@ extern "C" int hcspmm_edge_to_row_device(const int32_t* rowptr, int64_t N, int64
   hipLaunchKernelGGL(edge_to_row_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_v), rowptr,
                      (int)N, (long long)E, e2r);
   const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+// Graphs built on the device (graph_build.h): the sampler's scan and selection, and the transpose
+static_assert(HCSPMM_SAMPLE_WAVE_ROW_MAX == hcspmm::kSampleWaveRowMax, "hcspmm.h documents the sampler's wave-row limit");
+
+extern "C" size_t hcspmm_sample_workspace_bytes(int64_t N) {
+  return (N < 0 || N > INT32_MAX - 16) ? 0 : hcspmm::sample_workspace_bytes((long long)N);
+}
+
+extern "C" int hcspmm_sample_row_pointers_device(const int32_t* rowptr, int64_t N, int fanout, int32_t* rowptr_s, void* workspace,
+                                                 size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || fanout < 1 || !rowptr || !rowptr_s) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16) return HCSPMM_ERANGE;
+  if (!workspace || workspace_bytes < hcspmm::sample_workspace_bytes((long long)N)) return HCSPMM_EWORKSPACE;
+  const hipError_t e = hcspmm::launch_sample_row_pointers(rowptr, (long long)N, fanout, rowptr_s, workspace,
+                                                          reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" int hcspmm_sample_neighbors_device(const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_s, int64_t N, int64_t E,
+                                              int fanout, uint64_t seed, int32_t* col_s, int32_t* entry_s, void* stream_v) {
+  if (N < 0 || E < 0 || fanout < 1 || !rowptr || !rowptr_s || (E > 0 && (!col || !col_s || !entry_s))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if (N == 0 || E == 0) return HCSPMM_OK;
+  const hipError_t e = hcspmm::launch_sample_neighbors(rowptr, col, rowptr_s, (long long)N, fanout, seed, col_s, entry_s,
+                                                       reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" size_t hcspmm_transpose_graph_device_workspace_bytes(int64_t N, int64_t M, int64_t E) {
+  if (N < 0 || M < 0 || E < 0 || M > INT32_MAX - 16 || E > INT32_MAX) return 0;
+  return hcspmm::transpose_workspace_bytes((long long)M, (long long)E);
+}
+
+extern "C" int hcspmm_transpose_graph_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t M, int64_t E,
+                                             int32_t* rowptr_t, int32_t* col_t, int32_t* entry_t, void* workspace,
+                                             size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || M < 0 || E < 0 || !rowptr || !rowptr_t || (E > 0 && (!col || !col_t || !entry_t))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || M > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  const size_t need = hcspmm::transpose_workspace_bytes((long long)M, (long long)E);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return HCSPMM_EWORKSPACE;
+  const hipError_t e = hcspmm::launch_transpose_graph(rowptr, col, (long long)N, (long long)M, (long long)E, rowptr_t, col_t, entry_t,
+                                                      workspace, reinterpret_cast<hipStream_t>(stream_v));
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 

@@ -27,7 +27,8 @@ __all__ = [
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
     "gatv2_scores", "gatv2_scores_backward",
-    "transpose_graph", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
+    "transpose_graph", "transpose_graph_device", "sample_row_pointers", "sample_neighbors", "plan_free_graph",
+    "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
     "forward_softmax", "softmax_backward",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
@@ -999,6 +1000,112 @@ def transpose_graph(row_pointers, column_index, num_cols=None):
     check(lib().hcspmm_transpose_graph(_ptr(rp), _ptr(col), N, M, E, _ptr(rp_t), _ptr(col_t), _ptr(eid_t)))
     dev = row_pointers.device
     return rp_t.to(dev), col_t.to(dev), eid_t.to(dev)
+
+
+def _device_graph(row_pointers, column_index):
+    """the checks of the entry points that BUILD graphs on the device -> (N, E, stream)"""
+    _check_graph(row_pointers, column_index)
+    if row_pointers.dim() != 1 or row_pointers.numel() < 1 or column_index.dim() != 1:
+        raise RuntimeError("row_pointers [N + 1] and column_index [E] must be 1-D")
+    if column_index.device != row_pointers.device:
+        raise RuntimeError("column_index must be on the device of row_pointers")
+    return (row_pointers.numel() - 1, column_index.numel(),
+            ctypes.c_void_p(torch.cuda.current_stream(row_pointers.device).cuda_stream))
+
+
+def transpose_graph_device(row_pointers, column_index, num_cols=None):
+    """transpose_graph built on the device (hcspmm_transpose_graph_device, a stable radix sort by column) -> the same
+    (row_pointers_t, column_index_t, entry_index_t), element for element, asynchronously on the current stream and with no host
+    copy.  What transpose_graph validates is trusted here: ids in [0, num_cols), row_pointers[0] = 0, row_pointers[N] = E."""
+    N, E, stream = _device_graph(row_pointers, column_index)
+    M = N if num_cols is None else int(num_cols)
+    if M < 0:
+        raise RuntimeError("num_cols must not be negative, got %d" % M)
+    dev = row_pointers.device
+    rp_t = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    col_t, eid_t = torch.empty(E, dtype=torch.int32, device=dev), torch.empty(E, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().hcspmm_transpose_graph_device_workspace_bytes(N, M, E))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        check(lib().hcspmm_transpose_graph_device(_ptr(row_pointers), _ptr(column_index), N, M, E, _ptr(rp_t), _ptr(col_t),
+                                                  _ptr(eid_t), _ptr(ws), ws_bytes, stream))
+    return rp_t, col_t, eid_t
+
+
+# Rows longer than the fanout are selected by one wave up to this many entries and by a workgroup beyond (hcspmm.h
+# HCSPMM_SAMPLE_WAVE_ROW_MAX); the other class limit is the fanout itself.
+SAMPLE_WAVE_ROW_MAX = 512
+
+
+def sample_row_pointers(row_pointers, fanout):
+    """row_pointers_s of every sample of this graph at this fanout: the exclusive scan of min(deg, fanout), on the device
+    (hcspmm_sample_row_pointers_device).  It does not depend on the seed: make it once per (graph, fanout)."""
+    _check_input(row_pointers, "nodePointer")
+    if row_pointers.dtype != torch.int32 or row_pointers.dim() != 1 or row_pointers.numel() < 1:
+        raise RuntimeError("nodePointer must be a 1-D int32 tensor [N + 1]")
+    if int(fanout) < 1:
+        raise RuntimeError("fanout must be at least 1, got %d" % int(fanout))
+    N, dev = row_pointers.numel() - 1, row_pointers.device
+    rp_s = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().hcspmm_sample_workspace_bytes(N))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        check(lib().hcspmm_sample_row_pointers_device(_ptr(row_pointers), N, int(fanout), _ptr(rp_s), _ptr(ws), ws_bytes,
+                                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return rp_s
+
+
+def sample_neighbors(row_pointers, column_index, fanout, seed, row_pointers_s=None):
+    """A fanout-limited sample of every row's neighbours, on the device (hcspmm_sample_neighbors_device) ->
+    (row_pointers_s, column_index_s, entry_index_s), int32: a row with at most `fanout` entries keeps them all, a longer one the
+    `fanout` entries with the smallest key(e, seed) (include/hcspmm.h), in ascending CSR position; entry_index_s names the kept
+    entries' positions in A, so edge values travel as values[entry_index_s] or through forward_weighted_indexed.  seed: any
+    integer, taken modulo 2^64.  row_pointers_s: sample_row_pointers(row_pointers, fanout) when the caller kept it -- the call
+    then reads nothing back from the device (without it E_s, four bytes, is read once)."""
+    N, E, stream = _device_graph(row_pointers, column_index)
+    if int(fanout) < 1:
+        raise RuntimeError("fanout must be at least 1, got %d" % int(fanout))
+    if row_pointers_s is None:
+        row_pointers_s = sample_row_pointers(row_pointers, fanout)
+    else:
+        _check_input(row_pointers_s, "row_pointers_s")
+        if row_pointers_s.dtype != torch.int32 or row_pointers_s.numel() != N + 1 or row_pointers_s.device != row_pointers.device:
+            raise RuntimeError("row_pointers_s must be sample_row_pointers(row_pointers, fanout): int32 [N + 1] on the graph's device")
+    E_s = _sampled_edges(row_pointers_s)
+    dev = row_pointers.device
+    col_s, eid_s = torch.empty(E_s, dtype=torch.int32, device=dev), torch.empty(E_s, dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        check(lib().hcspmm_sample_neighbors_device(_ptr(row_pointers), _ptr(column_index), _ptr(row_pointers_s), N, E, int(fanout),
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(col_s), _ptr(eid_s), stream))
+    return row_pointers_s, col_s, eid_s
+
+
+_SAMPLED_EDGES = {}  # data_ptr of a row_pointers_s tensor -> (weak ref, E_s): the 4-byte read happens once per tensor
+
+
+def _sampled_edges(row_pointers_s):
+    key = row_pointers_s.data_ptr()
+    hit = _SAMPLED_EDGES.get(key)
+    if hit is not None and hit[0]() is row_pointers_s:
+        return hit[1]
+    E_s = int(row_pointers_s[-1].item())
+    for k in [k for k, v in _SAMPLED_EDGES.items() if v[0]() is None]:
+        del _SAMPLED_EDGES[k]
+    _SAMPLED_EDGES[key] = (weakref.ref(row_pointers_s), E_s)
+    return E_s
+
+
+def plan_free_graph(row_pointers, column_index):
+    """The eight graph tensors with which every entry point takes its plan-free, all-sparse-row path on (row_pointers,
+    column_index), made on the device with no host copy: zero hybrid_type (every window on the sparse-row path, which reads
+    row_pointers and column_index only), zero blockPartition, and [0] placeholders for row_nzr / col_nzr and for edgeToColumn /
+    edgeToRow, which only dense-tile windows read.  For graphs that change from step to step (sample_neighbors,
+    transpose_graph_device); a graph that is multiplied many times wants preprocess and its plan."""
+    N, _, _ = _device_graph(row_pointers, column_index)
+    dev = row_pointers.device
+    windows = max((N + 15) // 16, 1)
+    zeros = [torch.zeros(n, dtype=torch.int32, device=dev) for n in (windows, 1, 1, windows, 1, 1)]
+    return [row_pointers, column_index] + zeros
 
 
 def _check_view(t, name, dtype=None):

@@ -97,6 +97,11 @@ SYMBOLS = {
     "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "hcspmm_transpose_graph": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "hcspmm_transpose_graph_device_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "hcspmm_transpose_graph_device": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "hcspmm_sample_workspace_bytes": (_sz, [_i64]),
+    "hcspmm_sample_row_pointers_device": (_int, [_vp, _i64, _int, _vp, _vp, _sz, _vp]),
+    "hcspmm_sample_neighbors_device": (_int, [_vp, _vp, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp, _vp, _vp]),
     "hcspmm_sddmm": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp]),
     "hcspmm_sddmm_heads": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _int]),
     "hcspmm_edge_softmax": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),

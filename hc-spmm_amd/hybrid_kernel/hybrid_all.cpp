@@ -1129,6 +1129,106 @@ torch::Tensor build_plan(torch::Tensor row_pointers, torch::Tensor column_index,
   return plan_d;
 }
 
+// ---- graphs built on the device: hcspmm_transpose_graph_device, hcspmm_sample_*; everything on the current stream ----
+void check_device_graph(const torch::Tensor& row_pointers, const torch::Tensor& column_index) {
+  auto& nodePointer = row_pointers;  // (the names of the CHECK_INPUT messages)
+  auto& edgeList = column_index;
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  check_i32_graph(row_pointers, column_index);
+  TORCH_CHECK(row_pointers.dim() == 1 && row_pointers.numel() >= 1 && column_index.dim() == 1,
+              "row_pointers [N + 1] and column_index [E] must be 1-D");
+  TORCH_CHECK(column_index.device() == row_pointers.device(), "column_index must be on the device of row_pointers");
+}
+
+std::vector<torch::Tensor> transpose_graph_device(torch::Tensor row_pointers, torch::Tensor column_index,
+                                                  c10::optional<int64_t> num_cols) {
+  check_device_graph(row_pointers, column_index);
+  const int64_t N = row_pointers.numel() - 1, E = column_index.numel(), M = num_cols.has_value() ? *num_cols : N;
+  TORCH_CHECK(M >= 0, "num_cols must not be negative, got ", M);
+  const auto opts = row_pointers.options();
+  auto rp_t = torch::empty({M + 1}, opts), col_t = torch::empty({E}, opts), eid_t = torch::empty({E}, opts);
+  const size_t ws_bytes = hcspmm_transpose_graph_device_workspace_bytes(N, M, E);
+  auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, opts);
+  const c10::DeviceGuard guard(row_pointers.device());
+  check_rc(hcspmm_transpose_graph_device(iptr(row_pointers), iptr(column_index), N, M, E, mptr(rp_t), mptr(col_t), mptr(eid_t),
+                                         mptr(ws), ws_bytes, current_stream(row_pointers)),
+           "transpose_graph_device");
+  return {rp_t, col_t, eid_t};
+}
+
+torch::Tensor sample_row_pointers(torch::Tensor row_pointers, int64_t fanout) {
+  auto& nodePointer = row_pointers;
+  CHECK_INPUT(nodePointer);
+  TORCH_CHECK(row_pointers.scalar_type() == torch::kInt && row_pointers.dim() == 1 && row_pointers.numel() >= 1,
+              "nodePointer must be a 1-D int32 tensor [N + 1]");
+  TORCH_CHECK(fanout >= 1 && fanout <= INT32_MAX, "fanout must be at least 1, got ", fanout);
+  const int64_t N = row_pointers.numel() - 1;
+  auto rp_s = torch::empty({N + 1}, row_pointers.options());
+  const size_t ws_bytes = hcspmm_sample_workspace_bytes(N);
+  auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, row_pointers.options());
+  const c10::DeviceGuard guard(row_pointers.device());
+  check_rc(hcspmm_sample_row_pointers_device(iptr(row_pointers), N, (int)fanout, mptr(rp_s), mptr(ws), ws_bytes,
+                                             current_stream(row_pointers)),
+           "sample_row_pointers");
+  return rp_s;
+}
+
+// E_s of a row_pointers_s tensor: its last element, read back once per tensor (entries hold weak references, as g_plans)
+struct SampledEdges {
+  WeakTensor ref;
+  int64_t edges;
+};
+std::unordered_map<const void*, SampledEdges> g_sampled_edges;
+
+int64_t sampled_edges(const torch::Tensor& row_pointers_s) {
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_sampled_edges.find(row_pointers_s.data_ptr());
+    if (it != g_sampled_edges.end() && it->second.ref.lock().get() == row_pointers_s.unsafeGetTensorImpl()) return it->second.edges;
+  }
+  const int64_t edges = row_pointers_s[-1].item<int>();
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (auto it = g_sampled_edges.begin(); it != g_sampled_edges.end();)
+    it = it->second.ref.expired() ? g_sampled_edges.erase(it) : std::next(it);
+  g_sampled_edges.insert_or_assign(row_pointers_s.data_ptr(), SampledEdges{weak_of(row_pointers_s), edges});
+  return edges;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_neighbors(torch::Tensor row_pointers, torch::Tensor column_index,
+                                                                         int64_t fanout, pybind11::int_ seed,
+                                                                         c10::optional<torch::Tensor> row_pointers_s) {
+  check_device_graph(row_pointers, column_index);
+  TORCH_CHECK(fanout >= 1 && fanout <= INT32_MAX, "fanout must be at least 1, got ", fanout);
+  const int64_t N = row_pointers.numel() - 1, E = column_index.numel();
+  torch::Tensor rp_s;
+  if (row_pointers_s.has_value()) {
+    rp_s = *row_pointers_s;
+    CHECK_INPUT(rp_s);
+    TORCH_CHECK(rp_s.scalar_type() == torch::kInt && rp_s.numel() == N + 1 && rp_s.device() == row_pointers.device(),
+                "row_pointers_s must be sample_row_pointers(row_pointers, fanout): int32 [N + 1] on the graph's device");
+  } else {
+    rp_s = sample_row_pointers(row_pointers, fanout);
+  }
+  const uint64_t seed64 = seed.attr("__and__")(pybind11::int_(0xFFFFFFFFFFFFFFFFull)).cast<uint64_t>();  // modulo 2^64
+  const int64_t E_s = sampled_edges(rp_s);
+  auto col_s = torch::empty({E_s}, row_pointers.options()), eid_s = torch::empty({E_s}, row_pointers.options());
+  const c10::DeviceGuard guard(row_pointers.device());
+  check_rc(hcspmm_sample_neighbors_device(iptr(row_pointers), iptr(column_index), iptr(rp_s), N, E, (int)fanout, seed64, mptr(col_s),
+                                          mptr(eid_s), current_stream(row_pointers)),
+           "sample_neighbors");
+  return {rp_s, col_s, eid_s};
+}
+
+std::vector<torch::Tensor> plan_free_graph(torch::Tensor row_pointers, torch::Tensor column_index) {
+  check_device_graph(row_pointers, column_index);
+  const int64_t windows = std::max<int64_t>((row_pointers.numel() - 1 + HCSPMM_BLK_H - 1) / HCSPMM_BLK_H, 1);
+  const auto opts = row_pointers.options();
+  auto placeholder = [&] { return torch::zeros({1}, opts); };
+  return {row_pointers, column_index, torch::zeros({windows}, opts), placeholder(), placeholder(), torch::zeros({windows}, opts),
+          placeholder(), placeholder()};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("preprocess", &preprocess, "Preprocess step: window condensing + classifier + MI355X launch plan (host)",
         pybind11::arg("column_index"), pybind11::arg("row_pointers"), pybind11::arg("num_nodes"), pybind11::arg("num_edges"),
@@ -1254,6 +1354,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "A^T of any CSR graph (host counting sort) -> [row_pointers_t, column_index_t, entry_index_t], int32 on the inputs' device; "
      "entry_index_t[e_t] = the CSR position in A of A^T's entry e_t",
         pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("num_cols") = pybind11::none());
+  m.def("transpose_graph_device", &transpose_graph_device,
+        "transpose_graph built on the device (a stable radix sort by column): the same [row_pointers_t, column_index_t, "
+        "entry_index_t], element for element, asynchronously and with no host copy; the input is trusted, not validated (gfx950)",
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("num_cols") = pybind11::none());
+  m.def("sample_row_pointers", &sample_row_pointers,
+        "row_pointers_s of every sample of this graph at this fanout: the exclusive scan of min(deg, fanout), on the device (gfx950)",
+        pybind11::arg("row_pointers"), pybind11::arg("fanout"));
+  m.def("sample_neighbors", &sample_neighbors,
+        "fanout-limited neighbour sample on the device -> (row_pointers_s, column_index_s, entry_index_s): rows up to `fanout` "
+        "entries keep them all, longer ones the `fanout` entries with the smallest key(e, seed) (hcspmm.h), in ascending CSR "
+        "position; row_pointers_s = sample_row_pointers(...) when the caller kept it (gfx950)",
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("fanout"), pybind11::arg("seed"),
+        pybind11::arg("row_pointers_s") = pybind11::none());
+  m.def("plan_free_graph", &plan_free_graph,
+        "the eight graph tensors of the plan-free, all-sparse-row path on (row_pointers, column_index), made on the device: zero "
+        "hybrid_type / blockPartition, [0] placeholders for edgeToColumn, edgeToRow, row_nzr, col_nzr",
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"));
+  m.attr("SAMPLE_WAVE_ROW_MAX") = (int)HCSPMM_SAMPLE_WAVE_ROW_MAX;
   m.def("forward_weighted_indexed", &spmm_forward_weighted_indexed,
         "multi-head edge-weighted aggregation with indexed values [Z]: entry e of head h weighs values[h][value_index[e]]; the "
         "bits of forward_weighted_heads(X, values[:, value_index]) without the gathered copy (gfx950)");

@@ -34,7 +34,9 @@ extern "C" {
  * hcspmm_gatv2_scores_backward (round 10); hcspmm_quantize_fp8, hcspmm_forward_fp8,
  * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14);
  * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15); hcspmm_softmax_workspace_bytes, hcspmm_forward_softmax,
- * hcspmm_softmax_backward (round 17).  HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
+ * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
+ * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19).
+ * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
 
@@ -617,6 +619,48 @@ int hcspmm_transpose_graph(const int32_t* row_pointers_h, const int32_t* column_
                            int64_t num_edges, int32_t* row_pointers_t_out_h /* [num_cols + 1] */,
                            int32_t* column_index_t_out_h /* [E]: the row i of A */,
                            int32_t* entry_index_t_out_h /* [E]: the CSR position e of (i, j) in A */);
+
+/* hcspmm_transpose_graph on the device: the same three outputs, element for element, on every input the host function
+ * accepts (rectangular ones included), asynchronous on `stream` with no host read -- for graphs that change from step to step
+ * (a sample redrawn every epoch, below).  A stable radix sort of (column, e) by column: within a row of A^T the entries ascend
+ * in e.  What the host version validates this one TRUSTS, as the plan-free kernels trust column_index: row_pointers[0] = 0,
+ * row_pointers[num_rows] = num_edges, ids in [0, num_cols).  It never writes out of bounds whatever the ids are -- a column id
+ * is never used as an address, only eight bits of it at a time as a digit -- and with an id outside [0, num_cols) the result is
+ * unspecified.  workspace_d >= hcspmm_transpose_graph_device_workspace_bytes() (HCSPMM_EWORKSPACE otherwise; 0 bytes for
+ * num_edges = 0, which fills row_pointers_t with zeros).  NULL pointers and negative sizes are HCSPMM_EINVAL before any device
+ * call. */
+size_t hcspmm_transpose_graph_device_workspace_bytes(int64_t num_rows, int64_t num_cols, int64_t num_edges);
+int hcspmm_transpose_graph_device(const int32_t* row_pointers_d, const int32_t* column_index_d, int64_t num_rows, int64_t num_cols,
+                                  int64_t num_edges, int32_t* row_pointers_t_out_d /* [num_cols + 1] */,
+                                  int32_t* column_index_t_out_d /* [E] */, int32_t* entry_index_t_out_d /* [E] */,
+                                  void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fanout-limited neighbour sampling on the device (GraphSAGE's neighbourhood, on the full node set):
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16                 (uint32 arithmetic)
+ *   key(e, seed) = fmix32(fmix32((uint32)e * 0x9E3779B1 + (uint32)seed) + (uint32)(seed >> 32))          e: CSR position
+ * A row with at most `fanout` entries keeps them all; a longer one keeps the `fanout` entries with the smallest keys.  Kept
+ * entries stay in ascending e, so ascending columns stay ascending.  For one seed, key is a bijection of e: no ties.  A key
+ * depends on (e, seed) alone, so the sample is the same whatever the launch shape; no atomics, no floating point.
+ *   row_pointers_s [num_nodes + 1]  the exclusive scan of min(deg, fanout): a function of the graph and the fanout, NOT of the
+ *                                   seed -- hcspmm_sample_row_pointers_device, once per (graph, fanout); E_s = its last element
+ *   column_index_s [E_s], entry_index_s [E_s]  the kept entries' column ids and their positions in A (values travel as
+ *                                   values[entry_index_s], or through hcspmm_forward_weighted_indexed) --
+ *                                   hcspmm_sample_neighbors_device, once per seed: fixed output shapes, no host read, no allocation
+ * Rows longer than the fanout are selected by one wave up to HCSPMM_SAMPLE_WAVE_ROW_MAX entries and by a workgroup beyond.
+ * hcspmm_sample_neighbors_device trusts row_pointers_s_d to be the scan for THIS graph and fanout.  fanout < 1, NULL pointers
+ * and negative sizes are HCSPMM_EINVAL before any device call; a workspace below hcspmm_sample_workspace_bytes() is
+ * HCSPMM_EWORKSPACE.  num_nodes = 0 or num_edges = 0 samples nothing (the scan still writes its zeros).  Asynchronous on
+ * `stream`. */
+#define HCSPMM_SAMPLE_WAVE_ROW_MAX 512
+size_t hcspmm_sample_workspace_bytes(int64_t num_nodes);
+int hcspmm_sample_row_pointers_device(const int32_t* row_pointers_d, int64_t num_nodes, int fanout,
+                                      int32_t* row_pointers_s_out_d /* [num_nodes + 1] */, void* workspace_d,
+                                      size_t workspace_bytes, void* stream);
+int hcspmm_sample_neighbors_device(const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                   const int32_t* row_pointers_s_d, int64_t num_nodes, int64_t num_edges, int fanout,
+                                   uint64_t seed, int32_t* column_index_s_out_d /* [E_s] */,
+                                   int32_t* entry_index_s_out_d /* [E_s] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * SDDMM (sampled dense-dense product) on the stored entries -- with the two edge softmax entry points below, the kernels
