@@ -334,6 +334,17 @@ int bind_graph(hcspmm::PlanArgs& p, const GraphIn& g, int D, int64_t src_rows, v
 inline void use_schedule(hcspmm::PlanArgs& p, const hcspmm_plan_header* ph) {
   if (ph->off_task_sched != 0) p.off_sched = ph->off_task_sched;
   if (ph->off_slice_sched != 0) p.off_slice_tasks = ph->off_slice_sched;
+  // ... and the first indices of those descriptors from the records that belong to the copies (hcspmm.h off_task_sched_idx),
+  // the sliced region's list bounds from the header's copy of the slice table.  A plan without the records leaves all of it
+  // zero: the kernel then reads col behind the descriptor and the table from the plan, as before.
+  if (ph->off_task_sched != 0 && ph->off_task_sched_idx != 0) p.off_sched_idx = ph->off_task_sched_idx;
+  if (ph->off_slice_sched != 0 && ph->off_slice_sched_idx != 0) {
+    p.off_slice_idx = ph->off_slice_sched_idx;
+    if (ph->n_slices == 8) {
+      p.slice_tbl_n = 9;
+      for (int s = 0; s < 9; ++s) p.slice_tbl[s] = ph->slice_table_copy[s];
+    }
+  }
 }
 
 inline void set_operands(hcspmm::PlanArgs& p, const void* X, void* Z, int64_t ldx, int64_t ldz) {

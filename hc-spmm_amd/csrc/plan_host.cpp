@@ -41,8 +41,13 @@
 // Blob layout (int32 words): header[64] | tasks[n_tasks][4] | dense_index[n_dense][4] |
 // dense_pack[...] | compact2[n_dense_compact2][128] | compact[n_dense_compact][64] | fixups[n_split_rows][4] |
 // sparse_windows[n_sparse_windows] | slice_table[n_slices + 1] | slice_tasks[n_slice_tasks][4] |
-// task_sched[n_tasks - n_tiny][4] | slice_sched[n_slice_tasks][4].
-// All section offsets are multiples of 4 words, the compact sections' of 64.  With slices the sections are sized
+// task_sched[n_tasks - n_tiny][4] | slice_sched[n_slice_tasks][4] | task_sched_idx[n_tasks - n_tiny][32] |
+// slice_sched_idx[n_slice_tasks][32].
+//   first-index records : behind the schedule copies, one record of 32 words per descriptor of either copy, in the copy's order:
+//             col[first, first + min(length, 32)) and -1 behind it (all -1 for a padding descriptor).  A wave of the binary
+//             product's launch knows its records' address from its place in the grid, so it asks for descriptor and first
+//             indices at once instead of one after the other; HCSPMM_SCHED_INDEX=0 leaves them out.
+// All section offsets are multiples of 4 words, the compact sections' of 64, the record sections' of 32.  With slices the sections are sized
 // by upper bounds that do not depend on the column ids (hcspmm_plan_words has none): the header holds the real counts.
 #include <algorithm>
 #include <atomic>
@@ -78,12 +83,14 @@ constexpr int kSliceSample = 4;                  // the boundary histogram looks
 // the count does not tell them apart.  Three graphs stand behind the rule: WHERE between 233 K and 4.86 M columns the sign
 // turns is not measured -- the boundary is the cache's size, a hypothesis that fits them.
 constexpr int64_t kScheduleMaxColumns = (256ll << 20) / 128;
+constexpr int64_t kIdxWords = HCSPMM_SCHED_INDEX_WORDS;  // words per first-index record
 constexpr int kSlicePad = 64;                    // slice lists are padded to whole waves of any lane-group count (4 waves x 16)
 
 struct Resolved {
   int32_t split_threshold, segment_len, fuse_in_launch;
   int32_t slice_mode, slice_threshold, n_slices, panel_cols;
   int32_t schedule;  // the exact-length copies of the task lists: 0 off, > 0 on, < 0 decided by hcspmm_plan_build (kScheduleMaxColumns)
+  int32_t sched_index;  // the first-index records of those copies (built only with them): 0 off, else on
 };
 
 int env_int(const char* name, int dflt) {
@@ -92,7 +99,7 @@ int env_int(const char* name, int dflt) {
 }
 
 Resolved resolve(const hcspmm_plan_params* p) {
-  Resolved r{512, 256, 0, kSliceAuto, kSliceAutoThreshold, 8, 0, -1};
+  Resolved r{512, 256, 0, kSliceAuto, kSliceAutoThreshold, 8, 0, -1, 1};
   if (p) {
     if (p->split_threshold > 0) r.split_threshold = p->split_threshold;
     if (p->segment_len > 0) r.segment_len = p->segment_len;
@@ -106,6 +113,7 @@ Resolved resolve(const hcspmm_plan_params* p) {
   else if (thr < 0) r.slice_mode = kSliceOff;
   if (ns > 0) r.n_slices = std::min(64, (ns + 7) / 8 * 8);
   r.schedule = env_int("HCSPMM_TASK_SCHEDULE", -1);  // A/B runs and the fallback: 0 leaves both schedule sections out, 1 forces them
+  r.sched_index = env_int("HCSPMM_SCHED_INDEX", 1) != 0;  // A/B runs and the fallback: 0 leaves both record sections out
   if (p && p->panel_cols != 0) r.panel_cols = p->panel_cols < 0 ? -1 : std::min(1 << 20, (p->panel_cols + 15) / 16 * 16);
   return r;
 }
@@ -148,7 +156,7 @@ struct Layout {
   int64_t n_sparse_windows = 0;
   int64_t n_slice_tasks = 0, n_sliced_rows = 0, nnz_sliced = 0;  // with slices: n_slice_tasks, n_split_rows, n_partials are upper bounds
   int64_t off_tasks = 0, off_dense_index = 0, off_dense_pack = 0, off_compact2 = 0, off_compact = 0, off_fixups = 0,
-          off_sparse_windows = 0, off_slice_table = 0, off_slice_tasks = 0, off_task_sched = 0, off_slice_sched = 0, total = 0;
+          off_sparse_windows = 0, off_slice_table = 0, off_slice_tasks = 0, off_task_sched = 0, off_slice_sched = 0, off_task_sched_idx = 0, off_slice_sched_idx = 0, total = 0;
 };
 
 // The workers of ONE hcspmm_plan_build / hcspmm_plan_words call: started once, handed the call's passes one after the other (a
@@ -311,10 +319,33 @@ int compute_layout(const int32_t* rowptr, int64_t N, const int32_t* bp, const in
       L.off_slice_sched = L.total;
       L.total += 4 * L.n_slice_tasks;
     }
+    if (rp.sched_index) {  // one 128-byte record per descriptor of either copy, on 128-byte boundaries of the blob
+      L.off_task_sched_idx = (L.total + kIdxWords - 1) / kIdxWords * kIdxWords;
+      L.total = L.off_task_sched_idx + kIdxWords * (L.n_tasks - L.n_tiny);
+      if (slicing) {
+        L.off_slice_sched_idx = L.total;
+        L.total += kIdxWords * L.n_slice_tasks;
+      }
+    }
   }
   if (L.total > INT32_MAX) return HCSPMM_ERANGE;
   *out = L;
   return HCSPMM_OK;
+}
+
+// rec[i] = the first-index record of descriptor desc[i], i in [0, n): col[first, first + min(length, 32)), the rest -1; a padding
+// descriptor (row -1) and every record in [n, n_all) are all -1.
+void first_index_records(const int32_t* desc, int32_t* rec, int64_t n, int64_t n_all, const int32_t* col, int T) {
+  if (n_all < 4096) T = 1;
+  parallel_for(T, [&](int t) {
+    for (int64_t i = n_all * t / T; i < n_all * (t + 1) / T; ++i) {
+      int32_t* r = rec + kIdxWords * i;
+      const int32_t* d = desc + 4 * i;
+      const int64_t k = (i < n && d[0] >= 0) ? std::min<int64_t>(std::max(d[2], 0), kIdxWords) : 0;
+      if (k > 0) std::memcpy(r, col + d[1], sizeof(int32_t) * (size_t)k);
+      for (int64_t j = k; j < kIdxWords; ++j) r[j] = -1;
+    }
+  });
 }
 
 // dst = the n descriptors (row, first, length, slot) of src by descending length, equal lengths in src's order; lengths lie in
@@ -444,6 +475,7 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
   tp[1] = now();
   Resolved rp = resolve(params);
   rp.schedule = rp.schedule < 0 ? (M <= kScheduleMaxColumns) : (rp.schedule != 0);
+  rp.sched_index = rp.schedule && rp.sched_index;
   Layout L;
   int rc = HCSPMM_OK;
   // XCD-affine slices: asked for, or (automatic) worth it -- X spans many L2s and the long rows hold a real share
@@ -720,6 +752,12 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
       // the section is sized by the lists' bound: clear what lies behind the last list
       std::memset(ssched + 4 * table[(size_t)S], 0, 16 * (size_t)(L.n_slice_tasks - table[(size_t)S]));
     }
+    if (L.off_task_sched_idx) {  // the first-index records of both copies (and the gap in front of them)
+      std::memset(plan + L.off_task_sched + 4 * n_nt + (slicing ? 4 * L.n_slice_tasks : 0), 0,
+                  sizeof(int32_t) * (size_t)(L.off_task_sched_idx - (L.off_task_sched + 4 * n_nt + (slicing ? 4 * L.n_slice_tasks : 0))));
+      first_index_records(plan + L.off_task_sched, plan + L.off_task_sched_idx, n_nt, n_nt, col, T);
+      if (slicing) first_index_records(plan + L.off_slice_sched, plan + L.off_slice_sched_idx, table[(size_t)S], L.n_slice_tasks, col, T);
+    }
   }
 
   tp[5] = now();
@@ -822,6 +860,10 @@ extern "C" int hcspmm_plan_build(const int32_t* rowptr, const int32_t* col, int6
   h.panel_cols = rp.panel_cols;
   h.off_task_sched = (int32_t)L.off_task_sched;
   h.off_slice_sched = (int32_t)L.off_slice_sched;
+  h.off_task_sched_idx = (int32_t)L.off_task_sched_idx;
+  h.off_slice_sched_idx = (int32_t)L.off_slice_sched_idx;
+  if (L.off_slice_sched_idx && S == 8)
+    for (int s = 0; s <= S; ++s) h.slice_table_copy[s] = (int32_t)table[(size_t)s];
   static_assert(sizeof(hcspmm_plan_header) == HCSPMM_PLAN_HEADER_WORDS * 4, "header size");
   std::memcpy(plan, &h, sizeof(h));
   if (dbg) {
@@ -885,6 +927,25 @@ extern "C" int hcspmm_plan_check(const hcspmm_plan_header* h, int64_t N, int64_t
       (h->n_slices == 0 || h->off_task_sched == 0 || h->off_slice_sched < h->off_task_sched + 4 * n_nt || (h->off_slice_sched & 3) ||
        h->total_words < h->off_slice_sched + 4 * (int64_t)h->n_slice_tasks))
     return HCSPMM_EPLAN;
+  // the first-index records, each section absent (0) or with its schedule copy, behind both copies, on a 128-byte boundary
+  const int64_t sched_end = h->off_slice_sched != 0 ? h->off_slice_sched + 4 * (int64_t)h->n_slice_tasks : h->off_task_sched + 4 * n_nt;
+  if (h->off_task_sched_idx != 0 &&
+      (h->off_task_sched == 0 || h->off_task_sched_idx < sched_end || (h->off_task_sched_idx % kIdxWords) ||
+       h->total_words < h->off_task_sched_idx + kIdxWords * n_nt))
+    return HCSPMM_EPLAN;
+  if (h->off_slice_sched_idx != 0 &&
+      (h->off_slice_sched == 0 || h->off_task_sched_idx == 0 || h->off_slice_sched_idx < h->off_task_sched_idx + kIdxWords * n_nt ||
+       (h->off_slice_sched_idx % kIdxWords) || h->total_words < h->off_slice_sched_idx + kIdxWords * (int64_t)h->n_slice_tasks))
+    return HCSPMM_EPLAN;
+  // the table's copy: all zero, or (with the slice records of eight slices) offsets that end at n_slice_tasks
+  if (h->off_slice_sched_idx != 0 && h->n_slices == 8) {
+    if (h->slice_table_copy[0] != 0 || h->slice_table_copy[8] != h->n_slice_tasks) return HCSPMM_EPLAN;
+    for (int s = 0; s < 8; ++s)
+      if (h->slice_table_copy[s + 1] < h->slice_table_copy[s] || (h->slice_table_copy[s] % 64)) return HCSPMM_EPLAN;
+  } else {
+    for (int s = 0; s < 9; ++s)
+      if (h->slice_table_copy[s] != 0) return HCSPMM_EPLAN;
+  }
   if (words_available > 0 && h->total_words > words_available) return HCSPMM_EPLAN;
   if ((int64_t)h->nnz_sparse + h->nnz_dense != E) return HCSPMM_EPLAN;
   return HCSPMM_OK;

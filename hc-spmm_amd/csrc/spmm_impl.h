@@ -302,10 +302,21 @@ __device__ __forceinline__ const int* index_source(const int* __restrict__ col, 
 }
 
 // (IV indices per lane and chunk; nmax: the wave's longest task)
-template <typename E, int L, int VEC, bool WIDE, int UMAX, int IV>
+// FC: the caller may hand over the task's first chunk of indices -- `first`, valid when have_first (wave-uniform) is set: what
+// the lane would read from col[e0 + pos ...] with -1 in every place past the task.  The planned kernel loads it from the plan's
+// first-index records (hcspmm.h off_task_sched_idx) TOGETHER with the descriptor, whose e0 the address in col has to wait
+// for: one dependent round trip less before the first gather.  The chunk serves the first column pass; a further pass of the
+// same task asks for its first chunk again, so that `first` is dead once the first chunk is on its way.
+// rec (with have_first; null for a lane group without a task): the record itself.  On the one-index path every chunk that lies
+// inside the record's 32 entries comes from it, so a task of at most 32 entries asks for ONE line of indices -- its record --
+// and never for col's.  (With the first chunk alone from the record such a task fetches the record's line AND col's: measured
+// 1.5 % slower than no records on the Reddit-scale headline, profiles/r20/ab_sched_index.log.)
+template <typename E, int L, int VEC, bool WIDE, int UMAX, int IV, bool FC = false>
 __device__ __forceinline__ void sparse_task_body(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
                                                  float* __restrict__ dstP, const int* __restrict__ col, int nE, int e0, int n,
-                                                 int nmax, size_t ldx, int c0, int cend, int lane) {
+                                                 int nmax, size_t ldx, int c0, int cend, int lane, bool have_first = false,
+                                                 typename IntV<IV>::type first = typename IntV<IV>::type(-1),
+                                                 const int* __restrict__ rec = nullptr) {
   typedef Lane<E, VEC> Ln;
   typedef typename Ln::acc_t acc_t;
   constexpr int U = (L < UMAX) ? L : UMAX;  // loads in flight per lane
@@ -320,14 +331,29 @@ __device__ __forceinline__ void sparse_task_body(const typename E::T* __restrict
   const int s = lane & (L - 1);
   const int pos = WIDE ? lane : s * IV;
   const int gbase = lane & ~(L - 1);
+  // where the lane's indices of the chunk that starts at entry `at` (wave-uniform) of the tasks come from (index_source's contract)
+  auto chunk_source = [&](int at, idx_t& v) -> const int* {
+    if constexpr (FC && IV == 1 && !WIDE) {
+      static_assert(!FC || 32 % L == 0, "a chunk lies inside the record or behind it");
+      if (have_first && at < 32) return at + pos < n ? rec + at + pos : nullptr;
+    }
+    return index_source<IV>(col, e0 + at + pos, n - (at + pos), nE, v);
+  };
 
+  idx_t next = idx_t(-1);
+  if constexpr (FC) {
+    if (have_first) next = first;
+    else if (const int* p0 = chunk_source(0, next)) next = *reinterpret_cast<const idx_mem_t*>(p0);
+  }
   for (int pbase = c0; pbase < cend; pbase += L * VEC) {  // feature columns [c0, cend) of the rows
     const bool cok = pbase + s * VEC < cend;
     const int c = cok ? lane_col<VEC>(pbase + s * VEC, cend) : 0;
     const int csafe = c;
     acc_t acc = azero<VEC>();
-    idx_t next = idx_t(-1);
-    if (const int* p0 = index_source<IV>(col, e0 + pos, n - pos, nE, next)) next = *reinterpret_cast<const idx_mem_t*>(p0);
+    if constexpr (!FC) {
+      next = idx_t(-1);
+      if (const int* p0 = index_source<IV>(col, e0 + pos, n - pos, nE, next)) next = *reinterpret_cast<const idx_mem_t*>(p0);
+    }
     for (int base = 0; base < nmax; base += STRIDE) {
       idx_t myidx = next;
       if constexpr (IV > 1) {  // a lane's IV entries may run past its task
@@ -337,7 +363,7 @@ __device__ __forceinline__ void sparse_task_body(const typename E::T* __restrict
       next = idx_t(-1);
       const int cnt = min(WIDE ? L : STRIDE, nmax - base);  // longest lane group's share of this chunk
       // consumed by the chunk's first batch
-      const int* pf = index_source<IV>(col, e0 + base + STRIDE + pos, n - (base + STRIDE + pos), nE, next);
+      const int* pf = chunk_source(base + STRIDE, next);
       for (int j = 0; j < cnt;) {
         const int left = cnt - j;  // wave-uniform: short tasks (the bulk of a low-degree graph) get
         const int src = gbase + j / IV;  // j is a multiple of U here (and U of IV): see gather_batch
@@ -368,15 +394,25 @@ __device__ __forceinline__ void sparse_task_body(const typename E::T* __restrict
       if (dstZ != nullptr) Ln::store(dstZ + c, acc);
       else if (dstP != nullptr) Ln::store_partial(dstP + c, acc);
     }
+    if constexpr (FC) {  // the first chunk of the next column pass
+      if (pbase + L * VEC < cend) {
+        next = idx_t(-1);
+        if (const int* p0 = chunk_source(0, next)) next = *reinterpret_cast<const idx_mem_t*>(p0);
+      }
+    }
   }
 }
 
 // IVREQ: indices per lane the caller asks for where the 16-byte path applies (the planned kernel's ordinary and sliced tasks
 // pass HCSPMM_INDEX_VEC; the plan-free kernel, whose lane groups never see more than kPlanFreeWide = 64 entries, keeps 1)
-template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U, int IVREQ = 1>
+// FC, have_first, rec: sparse_task_body's; first4 is the first chunk of the 16-byte path (IV = 4; with the records every wave
+// of a build that has the path takes it), first1 of the one-index path (the builds without it)
+template <typename E, int L, int VEC, bool WIDE, int UMAX = HCSPMM_SPARSE_U, int IVREQ = 1, bool FC = false>
 __device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X, typename E::Z* __restrict__ dstZ,
                                             float* __restrict__ dstP, const int* __restrict__ col, int nE, int e0, int n,
-                                            size_t ldx, int c0, int cend, int lane) {
+                                            size_t ldx, int c0, int cend, int lane, bool have_first = false,
+                                            typename IntV<IVREQ>::type first4 = typename IntV<IVREQ>::type(-1), int first1 = -1,
+                                            const int* __restrict__ rec = nullptr) {
   int nmax = n;
   if (!WIDE) {
 #pragma unroll
@@ -385,12 +421,16 @@ __device__ __forceinline__ void sparse_task(const typename E::T* __restrict__ X,
   nmax = __builtin_amdgcn_readfirstlane(nmax);
   constexpr int IV = (!WIDE && L == 8 && sizeof(typename E::T) == 4) ? IVREQ : 1;
   if constexpr (IV > 1) {
-    if (nmax > HCSPMM_INDEX_VEC_MIN) {  // wave-uniform: the plan sorts tasks by length class
-      sparse_task_body<E, L, VEC, WIDE, UMAX, IV>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane);
+    // wave-uniform: the plan sorts tasks by length class.  With first-index records every wave takes the 16-byte path: a wave of
+    // short tasks then holds all its indices after ONE load per lane, from records that are aligned lines, and reads no col at
+    // all (-2.9 % on the Reddit-scale headline where records on the one-index path gave -1.5 %: profiles/r20/ab_sched_index.log)
+    if (nmax > HCSPMM_INDEX_VEC_MIN || (FC && have_first)) {
+      sparse_task_body<E, L, VEC, WIDE, UMAX, IV, FC>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane, have_first, first4);
       return;
     }
   }
-  sparse_task_body<E, L, VEC, WIDE, UMAX, 1>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane);
+  sparse_task_body<E, L, VEC, WIDE, UMAX, 1, FC>(X, dstZ, dstP, col, nE, e0, n, nmax, ldx, c0, cend, lane, IV == 1 && have_first,
+                                                 first1, rec);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -835,29 +875,63 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
       constexpr int R = 64 / L;
       const int g = lane / L;
       const int4* tp = nullptr;
+      // First-index records (PlanArgs::off_sched_idx): the task's first indices, at an address that -- like the descriptor's --
+      // follows from the wave's place in the grid, so both are requested before either is used and the gathers start one
+      // dependent round trip sooner.  A record is one line of 32 indices, so groups of up to 32 lanes read their first chunk
+      // from it (64-lane groups and the fused form keep reading col behind the descriptor).  The fp32 tasks of 8 lanes take
+      // the record's 32 indices with one 16-byte load per lane (sparse_task then runs the 16-byte path for every wave), the
+      // other builds one index per lane.
+      constexpr bool FC = !FUSED && L <= 32;
+      constexpr bool FC4 = FC && L == 8 && sizeof(elem_t) == 4 && HCSPMM_INDEX_VEC == 4;  // sparse_task's 16-byte index path
+      const int* rec = nullptr;
+      bool have_first = false;  // wave-uniform
       if (bf < 0) {
         // sliced region: workgroup b serves the slices s = b (mod 8) -- all workgroups that share its XCD's L2 gather from
         // the same 1/8 of the X rows.  The slice lists are padded to whole waves (64 descriptors), so a wave never straddles
         // two lists; padding descriptors have row -1.
-        cint_p tbl = (cint_p)(a.plan + a.off_slice_table);  // wave-uniform: scalar loads
         int j = ((b >> 3) * kWaves + wave) * R;             // first descriptor of this wave in its XCD's concatenated lists
-        for (int sl = b & 7; sl < a.n_slices; sl += 8) {
-          const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
-          if (j < cnt) {
-            tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + lo + j + g;
-            break;
+        int at = -1;                                        // ... and its place in the slice task section
+        if (FC && a.slice_tbl_n != 0) {  // eight slices, their table among the kernel arguments: one list per workgroup
+          const int lo = a.slice_tbl[b & 7], cnt = a.slice_tbl[(b & 7) + 1] - lo;
+          if (j < cnt) at = lo + j;
+        } else {
+          cint_p tbl = (cint_p)(a.plan + a.off_slice_table);  // wave-uniform: scalar loads
+          for (int sl = b & 7; sl < a.n_slices; sl += 8) {
+            const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
+            if (j < cnt) {
+              at = lo + j;
+              break;
+            }
+            j -= cnt;
           }
-          j -= cnt;
         }
+        if (at >= 0) {
+          tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + at + g;
+          if (FC && a.off_slice_idx != 0) rec = a.plan + a.off_slice_idx + (size_t)(at + g) * 32;
+        }
+        have_first = FC && a.off_slice_idx != 0;
       } else {
         const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_sched) + tid;
+        if (tid < a.n_tasks - a.n_tiny) {
+          tp = reinterpret_cast<const int4*>(a.plan + a.off_sched) + tid;
+          if (FC && a.off_sched_idx != 0) rec = a.plan + a.off_sched_idx + (size_t)tid * 32;
+        }
+        have_first = FC && a.off_sched_idx != 0;
       }
       int e0 = 0, n = 0;
       typename E::Z* dz = nullptr;
       float* dp = nullptr;
+      typename IntV<HCSPMM_INDEX_VEC>::type first4 = typename IntV<HCSPMM_INDEX_VEC>::type(-1);
+      int first1 = -1;
       if (tp != nullptr) {
         const int4 t = *tp;
+        if constexpr (FC) {  // (issued behind the descriptor's load, ahead of its first use)
+          if (rec != nullptr) {
+            const int sl = lane & (L - 1);
+            if constexpr (FC4) first4 = *reinterpret_cast<const typename IntV<HCSPMM_INDEX_VEC>::type*>(rec + 4 * sl);
+            else first1 = rec[sl];
+          }
+        }
         if (t.x >= 0) {
           e0 = t.y;
           n = t.z;
@@ -865,7 +939,8 @@ __global__ __launch_bounds__(kThreads, MINW) void hybrid_plan_kernel(PlanArgs a)
           else dp = a.partial + (size_t)t.w * (size_t)a.D;
         }
       }
-      sparse_task<E, L, VEC, false, UNROLL, HCSPMM_INDEX_VEC>(X, dz, dp, a.col, a.E, e0, n, a.ldx, c0, cend, lane);
+      sparse_task<E, L, VEC, false, UNROLL, HCSPMM_INDEX_VEC, FC>(X, dz, dp, a.col, a.E, e0, n, a.ldx, c0, cend, lane, have_first,
+                                                                  first4, first1, rec);
     }
   } else {
     if constexpr (FUSED) {  // fp32 only: dense windows aggregate AND multiply by the weights (one window per wave)

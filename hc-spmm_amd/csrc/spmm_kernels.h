@@ -53,6 +53,15 @@ struct PlanArgs {
   // where the wide and the ordinary regions of the binary product's launch read their descriptors: off_tasks, or the plan's
   // exact-length schedule copy of the non-tiny tasks (hcspmm.h off_task_sched).  (Last as well, for the same reason.)
   int off_sched;
+  // first-index records of the schedule copies (hcspmm.h off_task_sched_idx / off_slice_sched_idx), as word offsets into plan:
+  // record i of a section holds the first (at most 32) column indices of descriptor i, padded with -1, so the ordinary and the
+  // sliced waves of the binary product's launch ask for their first indices together with their descriptors.  0: the plan has
+  // none, or the launch does not use them; the waves then read col behind the descriptor.  (Last, like off_sched.)
+  int off_sched_idx, off_slice_idx;
+  // the slice table itself (hcspmm.h slice_table_copy) when slice_tbl_n != 0: the sliced waves then find their list's bounds
+  // in the kernel arguments instead of the plan
+  int slice_tbl_n;
+  int slice_tbl[9];
 };
 
 // Arguments of the row-tile fused launch (fused_rows.hip): the planned launch's arguments (Z = out2; W / out / H set) plus the

@@ -41,6 +41,28 @@ class Header(ctypes.Structure):
     def fingerprint(self):
         return (int(self.fingerprint_hi) << 32) | int(self.fingerprint_lo)
 
+    # The first-index records of the schedule copies took the first eleven of the sixteen words behind off_slice_sched.
+    # The fields above stay as they were declared (callers walk _fields_); the new ones are read through these names.
+    @property
+    def off_task_sched_idx(self):
+        return int(self.reserved[0])
+
+    @off_task_sched_idx.setter
+    def off_task_sched_idx(self, v):
+        self.reserved[0] = v
+
+    @property
+    def off_slice_sched_idx(self):
+        return int(self.reserved[1])
+
+    @off_slice_sched_idx.setter
+    def off_slice_sched_idx(self, v):
+        self.reserved[1] = v
+
+    @property
+    def slice_table_copy(self):
+        return [int(v) for v in self.reserved[2:11]]
+
 
 class PlanParams(ctypes.Structure):
     """hcspmm_plan_params."""

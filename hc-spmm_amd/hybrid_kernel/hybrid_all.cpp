@@ -1565,6 +1565,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["n_sparse_windows"] = h.n_sparse_windows; d["dense_k_sum"] = h.dense_k_sum; d["flags"] = h.flags; d["num_nodes"] = h.num_nodes; d["num_edges"] = h.num_edges;
     d["fingerprint"] = ((uint64_t)h.fingerprint_hi << 32) | h.fingerprint_lo;
     d["off_task_sched"] = h.off_task_sched; d["off_slice_sched"] = h.off_slice_sched;
+    d["off_task_sched_idx"] = h.off_task_sched_idx; d["off_slice_sched_idx"] = h.off_slice_sched_idx;
     return d;
   }, "fields of the launch plan carried in row_nzr ({} for the reference's [0] placeholder)");
 }

@@ -118,6 +118,7 @@ int hcspmm_edge_to_row_device(const int32_t* row_pointers_d, int64_t num_nodes, 
 #define HCSPMM_COMPACT2_K 80    /* wider windows up to this many (padded) columns use double records ... */
 #define HCSPMM_COMPACT2_WORDS 128 /* ... of this many words: [window, K/4, U[80], 20 x (mask lo, mask hi), pad] */
 #define HCSPMM_PLAN_HEADER_WORDS 64
+#define HCSPMM_SCHED_INDEX_WORDS 32 /* a first-index record of the schedule copies: one 128-byte line (off_task_sched_idx) */
 
 typedef struct hcspmm_plan_header {
   int32_t magic;            /* HCSPMM_PLAN_MAGIC */
@@ -188,7 +189,18 @@ typedef struct hcspmm_plan_header {
                                are still exactly the tasks longer than 16 << b.  0: absent */
   int32_t off_slice_sched;  /* n_slice_tasks descriptors under the same slice table: every list's real descriptors in that
                                order, its padding behind them.  0: absent (always when n_slices == 0) */
-  int32_t reserved[16];
+  /* First-index records of the schedule copies: one record of HCSPMM_SCHED_INDEX_WORDS int32 (128 bytes, 128-byte
+   * aligned inside the blob) per descriptor of a schedule copy, in the copy's order.  Record i holds
+   * column_index[first, first + min(length, 32)) of descriptor i, the rest -1; a padding descriptor's record is all -1.  A wave of
+   * the binary product's launch knows its records' address from its position in the grid alone, so it asks for them together
+   * with its descriptors instead of one memory round trip later.  Built with the schedule copies unless HCSPMM_SCHED_INDEX=0 is in
+   * the environment at plan build.  Both offsets are multiples of 32 words and 0 when absent; plans without them run as before. */
+  int32_t off_task_sched_idx;  /* n_tasks - n_tiny records, behind the schedule copies.  0: absent (always when off_task_sched == 0) */
+  int32_t off_slice_sched_idx; /* n_slice_tasks records behind them.  0: absent (always when off_slice_sched == 0) */
+  int32_t slice_table_copy[9]; /* with the records and n_slices == 8: the nine words at off_slice_table once more, so that a
+                                  launcher -- which holds the header, not the blob -- can pass the table as kernel arguments;
+                                  else 0 */
+  int32_t reserved[5];
 } hcspmm_plan_header;
 
 #define HCSPMM_PLAN_FUSE_IN_LAUNCH 1
