@@ -1,6 +1,6 @@
 // plan_layout.h -- the grid layout of the planned hybrid launch, computed in ONE place for every launcher that shares it:
 // launch_plan_LV (spmm_impl.h), launch_plan_w_LV (spmm_weighted_impl.h), launch_plan_wh_LV (spmm_weighted_heads_impl.h,
-// direct and indexed) and launch_extremum_LV (spmm_extremum.hip).  Their device decodes all read the fields filled here, so
+// direct and indexed) and csr_launch (csr_schedule.h).  Their device decodes all read the fields filled here, so
 // the fields must mean the same thing everywhere.  Plain host code: no templates, nothing of HIP beyond PlanArgs.
 #pragma once
 #include "spmm_kernels.h"

@@ -3,8 +3,7 @@
 //   Z[r][d] = sum over the entries e of row r of m(X[col(e)][d], F[fi(e)][d]),  fi(e) = findex ? findex[e] : e
 //   mul: fmaf(f, x, acc)    add_relu: acc + ((x + f) < 0 ? +0 : x + f)    copy: acc + f (X is not read)
 //
-// The schedule is the hybrid launch's (spmm_impl.h): sliced | wide | ordinary | tiny regions per column panel, then the
-// dense-tile windows, then the fix-up pass over split rows.  Only the per-entry step differs.
+// The schedule is csr_schedule.h's, then the fix-up pass over split rows.
 //  * Every entry issues two 16-byte loads per lane, the X row through col[e] and the F row through fi(e), both through the
 //    element-aligned lanes (Lane / lane_col), F in 64-bit addressing.  The lane that loads col[e] loads findex[e] behind it
 //    (or takes e itself) and both travel to the gathering lanes through ds_bpermute; a lane past its task's end holds
@@ -14,7 +13,7 @@
 //  * Sums run in hcspmm_forward_weighted's order: CSR order on ordinary and tiny tasks, the wide tasks' xor-shuffle tree, fp32
 //    partials of sliced and segmented rows added by the fix-up pass in fixup_kernel's order.  No atomics.
 //  * Gradient with respect to X: this launch on A^T's graph with findex = entry_index_t (hcspmm.h).
-#include "spmm_impl.h"
+#include "csr_schedule.h"
 
 #include "hcspmm.h"
 
@@ -155,19 +154,6 @@ __device__ __forceinline__ EDst task_dst(const EdgeMsgArgs& ea, int row, int slo
   return d;
 }
 
-// first CSR entry of the split-row segment that owns partial slot s (spmm_weighted_impl.h segment_entry)
-__device__ __forceinline__ int esegment_entry(const EdgeMsgArgs& ea, int s) {
-  const int4* fix = reinterpret_cast<const int4*>(ea.p.plan + ea.p.off_fixups);
-  int lo = 0, hi = ea.p.n_split_rows;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (fix[mid].y <= s) lo = mid;
-    else hi = mid;
-  }
-  const int4 f = fix[lo];
-  return ea.rowptr[f.x] + (s - f.y) * ea.segment_len;
-}
-
 // tiny_tasks_w (spmm_weighted_impl.h): T tasks of at most two entries per lane group, column ids inline in the descriptor;
 // the entry position (the F row, or the place in findex) comes from rowptr (a whole row) or the fix-up list (the last
 // segment of a split row)
@@ -198,7 +184,7 @@ __device__ __forceinline__ void etiny(const EdgeMsgArgs& ea, int first, int c0, 
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     int e = 0;
-    if (d[t].y >= 0) e = d[t].x >= 0 ? ea.rowptr[d[t].x] : esegment_entry(ea, -(d[t].x + 1));
+    if (d[t].y >= 0) e = d[t].x >= 0 ? ea.rowptr[d[t].x] : segment_entry(a, ea.rowptr, ea.segment_len, -(d[t].x + 1));
     f0[t] = f1[t] = 0;
     if (d[t].y >= 0) f0[t] = ea.findex != nullptr ? ea.findex[e] : e;
     if (d[t].w >= 0) f1[t] = ea.findex != nullptr ? ea.findex[e + 1] : e + 1;
@@ -237,95 +223,23 @@ __device__ __forceinline__ void etiny(const EdgeMsgArgs& ea, int first, int c0, 
   }
 }
 
-// the 16 rows of a window from CSR, R = 64 / L at a time (dense-tile windows of the plan)
-template <int OP, int L, int VEC>
-__device__ __forceinline__ void ewindow_rows(const EdgeMsgArgs& ea, int window, int c0, int cend, int lane) {
-  constexpr int R = 64 / L;
-  const int g = lane / L;
-  for (int rb = 0; rb < 16; rb += R) {
-    const int r = window * 16 + rb + g;
-    int e0 = 0, n = 0;
-    EDst o{nullptr, nullptr};
-    if (rb + g < 16 && r < ea.p.N) {
-      e0 = ea.rowptr[r];
-      n = ea.rowptr[r + 1] - e0;
-      o = task_dst(ea, r, -1);
-    }
-    etask<OP, L, VEC, false>(ea, o.z, o.p, e0, n, c0, cend, lane);
+// what csr_schedule.h's walks call
+template <int OP, int L, int VEC> struct EBody {
+  const EdgeMsgArgs& ea;
+  typedef EDst Dst;
+  __device__ __forceinline__ Dst dst(int row, int slot) const { return task_dst(ea, row, slot); }
+  template <bool WIDE> __device__ __forceinline__ void task(const Dst& o, int e0, int n, int c0, int cend, int lane) const {
+    etask<OP, L, VEC, WIDE>(ea, o.z, o.p, e0, n, c0, cend, lane);
   }
-}
+  __device__ __forceinline__ void tiny(int first, int c0, int cend, int lane) const {
+    etiny<OP, L, VEC, ETinyT<L>::value>(ea, first, c0, cend, lane);
+  }
+};
 
-// ------------------------------------------------------------------------------------------
-// Planned kernel: hybrid_plan_kernel's regions (sliced | wide | ordinary | tiny per column panel), then one wave per
-// (dense-tile window, column panel) serving the window's rows from CSR.  Tiny tasks always run in their region here.
-// ------------------------------------------------------------------------------------------
+// the planned kernel (csr_schedule.h)
 template <int OP, int L, int VEC, int MINW>
 __global__ __launch_bounds__(kThreads, MINW) void edge_messages_plan_kernel(EdgeMsgArgs ea) {
-  const PlanArgs& a = ea.p;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if ((int)blockIdx.x < a.sparse_wgs) {
-    const int p = (int)blockIdx.x / a.sparse_wgs_pp;
-    const int b = (int)blockIdx.x - p * a.sparse_wgs_pp;
-    const int c0 = p * a.panel_cols;
-    const int cend = min(a.D, c0 + a.panel_cols);
-    const int bf = b - a.slice_wgs;
-    if (bf >= 0 && bf < a.wide_wgs) {
-      const int tid = bf * kWaves + wave;
-      if (tid >= a.n_wide) return;
-      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      const EDst o = task_dst(ea, t.x, t.w);
-      etask<OP, L, VEC, true>(ea, o.z, o.p, __builtin_amdgcn_readfirstlane(t.y), __builtin_amdgcn_readfirstlane(t.z), c0, cend, lane);
-    } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
-      if (bf >= a.free_wgs_pp) return;
-      constexpr int R = 64 / L;
-      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * ETinyT<L>::value);
-      if (first >= a.n_tasks) return;
-      etiny<OP, L, VEC, ETinyT<L>::value>(ea, first, c0, cend, lane);
-    } else {
-      constexpr int R = 64 / L;
-      const int g = lane / L;
-      const int4* tp = nullptr;
-      if (bf < 0) {
-        cint_p tbl = (cint_p)(a.plan + a.off_slice_table);
-        int j = ((b >> 3) * kWaves + wave) * R;
-        for (int sl = b & 7; sl < a.n_slices; sl += 8) {
-          const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
-          if (j < cnt) {
-            tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + lo + j + g;
-            break;
-          }
-          j -= cnt;
-        }
-      } else {
-        const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
-      }
-      int e0 = 0, n = 0;
-      EDst o{nullptr, nullptr};
-      if (tp != nullptr) {
-        const int4 t = *tp;
-        if (t.x >= 0) {  // (slice padding: row -1)
-          e0 = t.y;
-          n = t.z;
-          o = task_dst(ea, t.x, t.w);
-        }
-      }
-      etask<OP, L, VEC, false>(ea, o.z, o.p, e0, n, c0, cend, lane);
-    }
-  } else {
-    const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-    const int unit = ((int)blockIdx.x - a.sparse_wgs) * kWaves + wave;
-    if (unit >= a.n_dense * n_col_panels) return;
-    const int p = unit / a.n_dense, di = unit - p * a.n_dense;
-    const int n_reg = a.n_dense - a.n_dense_compact - a.n_dense_compact2;
-    int window;
-    if (di < n_reg) window = ((cint_p)(a.plan + a.off_dense_index))[4 * di];
-    else if (di < n_reg + a.n_dense_compact2) window = ((cint_p)(a.plan + a.off_dense_compact2))[(di - n_reg) * HCSPMM_COMPACT2_WORDS];
-    else window = ((cint_p)(a.plan + a.off_dense_compact))[(di - n_reg - a.n_dense_compact2) * HCSPMM_COMPACT_WORDS];
-    const int c0 = p * a.panel_cols;
-    ewindow_rows<OP, L, VEC>(ea, window, c0, min(a.D, c0 + a.panel_cols), lane);
-  }
+  csr_plan_walk<L, ETinyT<L>::value>(ea.p, ea.rowptr, EBody<OP, L, VEC>{ea});
 }
 
 // Fix-up: Z[row] of a split row = the sum of its fp32 partial rows, in fixup_kernel's order (spmm_impl.h): one wave per row,
@@ -365,86 +279,19 @@ __global__ __launch_bounds__(kThreads) void edge_messages_fixup_kernel(PlanArgs 
   }
 }
 
-// Plan-free kernel: one workgroup per 16-row window, every window (dense-tile or not) served from CSR: rows up to
-// kPlanFreeWide entries by one lane group each, longer ones by whole waves (hybrid_window_w_kernel's sparse branch)
+// the plan-free kernel (csr_schedule.h)
 template <int OP, int L, int VEC>
 __global__ __launch_bounds__(kThreads) void edge_messages_window_kernel(EdgeMsgArgs ea) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = (int)blockDim.x >> 6;
-  const int r0 = (int)blockIdx.x * 16, r1 = min(r0 + 16, ea.p.N);
-  constexpr int R = 64 / L;
-  const int G = R * nwaves;
-  const int gi = wave * R + lane / L;
-  for (int rb = r0; rb < r1; rb += G) {
-    const int r = rb + gi;
-    int e0 = 0, n = 0;
-    EDst o{nullptr, nullptr};
-    if (r < r1) {
-      e0 = ea.rowptr[r];
-      n = ea.rowptr[r + 1] - e0;
-      if (R == 1 || n <= kPlanFreeWide) o = task_dst(ea, r, -1);
-      else n = 0;  // left to the whole-wave pass below
-    }
-    etask<OP, L, VEC, false>(ea, o.z, o.p, e0, n, 0, ea.p.D, lane);
-  }
-  if (R > 1) {
-    int k = 0;
-    for (int r = r0; r < r1; ++r) {
-      const int e0 = ea.rowptr[r];
-      const int n = ea.rowptr[r + 1] - e0;
-      if (n > kPlanFreeWide) {
-        if (k % nwaves == wave) {
-          const EDst o = task_dst(ea, r, -1);
-          etask<OP, L, VEC, true>(ea, o.z, o.p, e0, n, 0, ea.p.D, lane);
-        }
-        ++k;
-      }
-    }
-  }
-}
-
-template <int OP, int L, int VEC>
-hipError_t launch_edge_messages_LV(const EdgeMsgArgs& ea, hipStream_t stream) {
-  EdgeMsgArgs eb = ea;
-  PlanArgs& b = eb.p;
-  if (ea.p.plan == nullptr) {  // plan-free
-    const int W = (b.N + 15) / 16;
-    int waves = (16 * L + 63) / 64;
-    if (waves > kWaves) waves = kWaves;
-    if (W > 0) hipLaunchKernelGGL((edge_messages_window_kernel<OP, L, VEC>), dim3(W), dim3(waves * 64), 0, stream, eb);
-    return hipGetLastError();
-  }
-  b.fused = 0;
-  // the shared layout (plan_layout.h): no launch of their own for the tiny tasks, dense windows once per column panel
-  const int n_col_panels = plan_launch_layout(b, L, 0, 0, ETinyT<L>::value, false, 0);
-  const long long dense_wgs = ((long long)b.n_dense * n_col_panels + kWaves - 1) / kWaves;
-  const long long grid = (long long)b.sparse_wgs + dense_wgs;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (grid > 0)
-    hipLaunchKernelGGL((edge_messages_plan_kernel<OP, L, VEC, HCSPMM_MIN_WAVES_PER_SIMD>), dim3((unsigned)grid), dim3(kThreads), 0,
-                       stream, eb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || b.n_split_rows == 0) return e;
-  const int fg = (b.n_split_rows + kWaves - 1) / kWaves;
-  hipLaunchKernelGGL((edge_messages_fixup_kernel<VEC>), dim3(fg), dim3(kThreads), 0, stream, b);
-  return hipGetLastError();
+  csr_window_walk<L>(ea.p, ea.rowptr, EBody<OP, L, VEC>{ea});
 }
 
 template <int OP>
 hipError_t launch_edge_messages_op(const EdgeMsgArgs& a, int vec, hipStream_t stream) {
-  if (vec == 4) {
-    switch (pick_L(a.p.plan != nullptr ? a.p.panel_cols : a.p.D, 4)) {
-      case 4: return launch_edge_messages_LV<OP, 4, 4>(a, stream);
-      case 8: return launch_edge_messages_LV<OP, 8, 4>(a, stream);
-      case 16: return launch_edge_messages_LV<OP, 16, 4>(a, stream);
-      case 32: return launch_edge_messages_LV<OP, 32, 4>(a, stream);
-      default: return launch_edge_messages_LV<OP, 64, 4>(a, stream);
-    }
-  }
-  if (a.p.D > 4 * vec) return hipErrorInvalidValue;
-  if (vec == 2) return launch_edge_messages_LV<OP, 4, 2>(a, stream);
-  return launch_edge_messages_LV<OP, 4, 1>(a, stream);
+  return csr_dispatch(a.p, vec, [&](auto lv) {
+    constexpr int L = decltype(lv)::L, VEC = decltype(lv)::VEC;
+    return csr_launch(a, L, ETinyT<L>::value, edge_messages_window_kernel<OP, L, VEC>,
+                      edge_messages_plan_kernel<OP, L, VEC, HCSPMM_MIN_WAVES_PER_SIMD>, edge_messages_fixup_kernel<VEC>, stream);
+  });
 }
 
 }  // namespace

@@ -3,8 +3,7 @@
 //   forward   Z[r][d] = max (min) over the entries e of row r of X[col(e)][d],  arg[r][d] = the winning e
 //   backward  grad_X[j][d] = sum of grad_Z[i][d] over the entries e = (i, j) with arg[i][d] == e
 //
-// The schedule is the hybrid launch's (spmm_impl.h): sliced | wide | ordinary | tiny regions per column panel, then the
-// dense-tile windows, then a fix-up pass over split rows.  Only the reduction differs.
+// The schedule is csr_schedule.h's, then a fix-up pass over split rows.
 //  * The winner is a (value, position) pair under one strict order: NaN above every number, then the larger value, ties
 //    (-0 == +0, NaN against NaN) to the lower position.  The order is total on distinct positions, so every combine --
 //    a lane's CSR scan, the wide tasks' shuffle tree, the fix-up over slices and segments -- gives the bits of a
@@ -18,6 +17,7 @@
 //  * Backward: A^T of a pattern-symmetric graph is A's pattern, so row j's entry e_t gathers grad_Z[col(e_t)] and
 //    arg[col(e_t)] and adds the columns whose arg is perm[e_t].  Sums run in the plan's fixed order (CSR order, the wide
 //    shuffle tree, the binary fix-up pass over the fp32 workspace): deterministic, no atomics.
+#include "csr_schedule.h"
 #include "extremum_common.h"  // the (value, position) order, kNone, XTinyT, the int32 lane vectors
 
 namespace hcspmm {
@@ -209,19 +209,6 @@ __device__ __forceinline__ XDst task_dst(const XArgs& xa, int row, int slot) {
   return d;
 }
 
-// first CSR entry of the split-row segment that owns partial slot s (spmm_weighted_impl.h segment_entry)
-__device__ __forceinline__ int xsegment_entry(const XArgs& xa, int s) {
-  const int4* fix = reinterpret_cast<const int4*>(xa.p.plan + xa.p.off_fixups);
-  int lo = 0, hi = xa.p.n_split_rows;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (fix[mid].y <= s) lo = mid;
-    else hi = mid;
-  }
-  const int4 f = fix[lo];
-  return xa.rowptr[f.x] + (s - f.y) * xa.segment_len;
-}
-
 // tiny_tasks (spmm_impl.h): T tasks of at most two entries per lane group, indices inline in the descriptor; the entry
 // position comes from rowptr (a whole row) or the fix-up list (the last segment of a split row)
 template <int L, int VEC, int T, bool BWD>
@@ -250,7 +237,7 @@ __device__ __forceinline__ void xtiny(const XArgs& xa, int first, int c0, int ce
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     e[t] = 0;
-    if (d[t].y >= 0) e[t] = d[t].x >= 0 ? xa.rowptr[d[t].x] : xsegment_entry(xa, -(d[t].x + 1));
+    if (d[t].y >= 0) e[t] = d[t].x >= 0 ? xa.rowptr[d[t].x] : segment_entry(a, xa.rowptr, xa.segment_len, -(d[t].x + 1));
     p0[t] = (BWD && d[t].y >= 0) ? xa.perm[e[t]] : 0;
     p1[t] = (BWD && d[t].w >= 0) ? xa.perm[e[t] + 1] : 0;
   }
@@ -291,96 +278,23 @@ __device__ __forceinline__ void xtiny(const XArgs& xa, int first, int c0, int ce
   }
 }
 
-// the 16 rows of a window from CSR, R = 64 / L at a time (dense-tile windows of the plan; every window plan-free)
-template <int L, int VEC, bool BWD>
-__device__ __forceinline__ void xwindow_rows(const XArgs& xa, int window, int c0, int cend, int lane) {
-  constexpr int R = 64 / L;
-  const int g = lane / L;
-  for (int rb = 0; rb < 16; rb += R) {
-    const int r = window * 16 + rb + g;
-    int e0 = 0, n = 0;
-    XDst o{nullptr, nullptr, nullptr, nullptr};
-    if (rb + g < 16 && r < xa.p.N) {
-      e0 = xa.rowptr[r];
-      n = xa.rowptr[r + 1] - e0;
-      o = task_dst(xa, r, -1);
-    }
-    xtask<L, VEC, false, BWD>(xa, o.z, o.a, o.p, o.pp, e0, n, c0, cend, lane);
+// what csr_schedule.h's walks call
+template <int L, int VEC, bool BWD> struct XBody {
+  const XArgs& xa;
+  typedef XDst Dst;
+  __device__ __forceinline__ Dst dst(int row, int slot) const { return task_dst(xa, row, slot); }
+  template <bool WIDE> __device__ __forceinline__ void task(const Dst& o, int e0, int n, int c0, int cend, int lane) const {
+    xtask<L, VEC, WIDE, BWD>(xa, o.z, o.a, o.p, o.pp, e0, n, c0, cend, lane);
   }
-}
+  __device__ __forceinline__ void tiny(int first, int c0, int cend, int lane) const {
+    xtiny<L, VEC, XTinyT<L>::value, BWD>(xa, first, c0, cend, lane);
+  }
+};
 
-// ------------------------------------------------------------------------------------------
-// Planned kernel: hybrid_plan_kernel's regions (sliced | wide | ordinary | tiny per column panel), then one wave per
-// (dense-tile window, column panel) serving the window's rows from CSR.  Tiny tasks always run in their region here.
-// ------------------------------------------------------------------------------------------
+// the planned kernel (csr_schedule.h)
 template <int L, int VEC, bool BWD, int MINW>
 __global__ __launch_bounds__(kThreads, MINW) void extremum_plan_kernel(XArgs xa) {
-  const PlanArgs& a = xa.p;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if ((int)blockIdx.x < a.sparse_wgs) {
-    const int p = (int)blockIdx.x / a.sparse_wgs_pp;
-    const int b = (int)blockIdx.x - p * a.sparse_wgs_pp;
-    const int c0 = p * a.panel_cols;
-    const int cend = min(a.D, c0 + a.panel_cols);
-    const int bf = b - a.slice_wgs;
-    if (bf >= 0 && bf < a.wide_wgs) {
-      const int tid = bf * kWaves + wave;
-      if (tid >= a.n_wide) return;
-      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      const XDst o = task_dst(xa, t.x, t.w);
-      xtask<L, VEC, true, BWD>(xa, o.z, o.a, o.p, o.pp, __builtin_amdgcn_readfirstlane(t.y), __builtin_amdgcn_readfirstlane(t.z),
-                               c0, cend, lane);
-    } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
-      if (bf >= a.free_wgs_pp) return;
-      constexpr int R = 64 / L;
-      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * XTinyT<L>::value);
-      if (first >= a.n_tasks) return;
-      xtiny<L, VEC, XTinyT<L>::value, BWD>(xa, first, c0, cend, lane);
-    } else {
-      constexpr int R = 64 / L;
-      const int g = lane / L;
-      const int4* tp = nullptr;
-      if (bf < 0) {
-        cint_p tbl = (cint_p)(a.plan + a.off_slice_table);
-        int j = ((b >> 3) * kWaves + wave) * R;
-        for (int sl = b & 7; sl < a.n_slices; sl += 8) {
-          const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
-          if (j < cnt) {
-            tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + lo + j + g;
-            break;
-          }
-          j -= cnt;
-        }
-      } else {
-        const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
-      }
-      int e0 = 0, n = 0;
-      XDst o{nullptr, nullptr, nullptr, nullptr};
-      if (tp != nullptr) {
-        const int4 t = *tp;
-        if (t.x >= 0) {  // (slice padding: row -1)
-          e0 = t.y;
-          n = t.z;
-          o = task_dst(xa, t.x, t.w);
-        }
-      }
-      xtask<L, VEC, false, BWD>(xa, o.z, o.a, o.p, o.pp, e0, n, c0, cend, lane);
-    }
-  } else {
-    const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-    const int unit = ((int)blockIdx.x - a.sparse_wgs) * kWaves + wave;
-    if (unit >= a.n_dense * n_col_panels) return;
-    const int p = unit / a.n_dense, di = unit - p * a.n_dense;
-    const int n_reg = a.n_dense - a.n_dense_compact - a.n_dense_compact2;
-    int window;
-    if (di < n_reg) window = ((cint_p)(a.plan + a.off_dense_index))[4 * di];
-    else if (di < n_reg + a.n_dense_compact2) window = ((cint_p)(a.plan + a.off_dense_compact2))[(di - n_reg) * HCSPMM_COMPACT2_WORDS];
-    else window = ((cint_p)(a.plan + a.off_dense_compact))[(di - n_reg - a.n_dense_compact2) * HCSPMM_COMPACT_WORDS];
-    const int c0 = p * a.panel_cols;
-    xwindow_rows<L, VEC, BWD>(xa, window, c0, min(a.D, c0 + a.panel_cols), lane);
-  }
+  csr_plan_walk<L, XTinyT<L>::value>(xa.p, xa.rowptr, XBody<L, VEC, BWD>{xa});
 }
 
 // Forward fix-up: Z[row] and arg[row] of a split row = the best of its partial (value, position) pairs -- one wave per row,
@@ -434,87 +348,21 @@ __global__ __launch_bounds__(kThreads) void extremum_fixup_kernel(XArgs xa) {
   }
 }
 
-// Plan-free kernel: one workgroup per 16-row window, every window (dense-tile or not) served from CSR: rows up to
-// kPlanFreeWide entries by one lane group each, longer ones by whole waves (hybrid_window_kernel's sparse branch)
+// the plan-free kernel (csr_schedule.h)
 template <int L, int VEC, bool BWD>
 __global__ __launch_bounds__(kThreads) void extremum_window_kernel(XArgs xa) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = (int)blockDim.x >> 6;
-  const int r0 = (int)blockIdx.x * 16, r1 = min(r0 + 16, xa.p.N);
-  constexpr int R = 64 / L;
-  const int G = R * nwaves;
-  const int gi = wave * R + lane / L;
-  for (int rb = r0; rb < r1; rb += G) {
-    const int r = rb + gi;
-    int e0 = 0, n = 0;
-    XDst o{nullptr, nullptr, nullptr, nullptr};
-    if (r < r1) {
-      e0 = xa.rowptr[r];
-      n = xa.rowptr[r + 1] - e0;
-      if (R == 1 || n <= kPlanFreeWide) o = task_dst(xa, r, -1);
-      else n = 0;  // left to the whole-wave pass below
-    }
-    xtask<L, VEC, false, BWD>(xa, o.z, o.a, o.p, o.pp, e0, n, 0, xa.p.D, lane);
-  }
-  if (R > 1) {
-    int k = 0;
-    for (int r = r0; r < r1; ++r) {
-      const int e0 = xa.rowptr[r];
-      const int n = xa.rowptr[r + 1] - e0;
-      if (n > kPlanFreeWide) {
-        if (k % nwaves == wave) {
-          const XDst o = task_dst(xa, r, -1);
-          xtask<L, VEC, true, BWD>(xa, o.z, o.a, o.p, o.pp, e0, n, 0, xa.p.D, lane);
-        }
-        ++k;
-      }
-    }
-  }
-}
-
-template <int L, int VEC, bool BWD>
-hipError_t launch_extremum_LV(const XArgs& xa, hipStream_t stream) {
-  XArgs xb = xa;
-  PlanArgs& b = xb.p;
-  if (xa.p.plan == nullptr) {  // plan-free
-    const int W = (b.N + 15) / 16;
-    int waves = (16 * L + 63) / 64;
-    if (waves > kWaves) waves = kWaves;
-    if (W > 0) hipLaunchKernelGGL((extremum_window_kernel<L, VEC, BWD>), dim3(W), dim3(waves * 64), 0, stream, xb);
-    return hipGetLastError();
-  }
-  b.fused = 0;
-  // the shared layout (plan_layout.h): no launch of their own for the tiny tasks, dense windows once per column panel
-  const int n_col_panels = plan_launch_layout(b, L, 0, 0, XTinyT<L>::value, false, 0);
-  const long long dense_wgs = ((long long)b.n_dense * n_col_panels + kWaves - 1) / kWaves;
-  const long long grid = (long long)b.sparse_wgs + dense_wgs;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (grid > 0)
-    hipLaunchKernelGGL((extremum_plan_kernel<L, VEC, BWD, HCSPMM_MIN_WAVES_PER_SIMD>), dim3((unsigned)grid), dim3(kThreads), 0,
-                       stream, xb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || b.n_split_rows == 0) return e;
-  const int fg = (b.n_split_rows + kWaves - 1) / kWaves;
-  if (BWD) hipLaunchKernelGGL((fixup_kernel<F32, VEC>), dim3(fg), dim3(kThreads), 0, stream, b);  // fp32 sums: the binary pass
-  else hipLaunchKernelGGL((extremum_fixup_kernel<VEC>), dim3(fg), dim3(kThreads), 0, stream, xb);
-  return hipGetLastError();
+  csr_window_walk<L>(xa.p, xa.rowptr, XBody<L, VEC, BWD>{xa});
 }
 
 template <bool BWD>
 hipError_t launch_extremum_any(const XArgs& a, int vec, hipStream_t stream) {
-  if (vec == 4) {
-    switch (pick_L(a.p.plan != nullptr ? a.p.panel_cols : a.p.D, 4)) {
-      case 4: return launch_extremum_LV<4, 4, BWD>(a, stream);
-      case 8: return launch_extremum_LV<8, 4, BWD>(a, stream);
-      case 16: return launch_extremum_LV<16, 4, BWD>(a, stream);
-      case 32: return launch_extremum_LV<32, 4, BWD>(a, stream);
-      default: return launch_extremum_LV<64, 4, BWD>(a, stream);
-    }
-  }
-  if (a.p.D > 4 * vec) return hipErrorInvalidValue;
-  if (vec == 2) return launch_extremum_LV<4, 2, BWD>(a, stream);
-  return launch_extremum_LV<4, 1, BWD>(a, stream);
+  return csr_dispatch(a.p, vec, [&](auto lv) {
+    constexpr int L = decltype(lv)::L, VEC = decltype(lv)::VEC;
+    constexpr auto window = extremum_window_kernel<L, VEC, BWD>;
+    constexpr auto plan = extremum_plan_kernel<L, VEC, BWD, HCSPMM_MIN_WAVES_PER_SIMD>;
+    if constexpr (BWD) return csr_launch(a, L, XTinyT<L>::value, window, plan, fixup_kernel<F32, VEC>, stream);  // fp32 sums: the binary pass
+    else return csr_launch(a, L, XTinyT<L>::value, window, plan, extremum_fixup_kernel<VEC>, stream);
+  });
 }
 
 }  // namespace

@@ -4,9 +4,8 @@
 // over the entries e of row r, x_e = X[col(e)][d].  A PNA layer needs all four; as four launches each one gathers the same X
 // lines again, and every one of them is bound by those gathers.
 //
-// The schedule is spmm_extremum.hip's, which is the hybrid launch's (spmm_impl.h): sliced | wide | ordinary | tiny regions per
-// column panel, the dense-tile windows served from CSR by the sparse-row task body, a fix-up pass over split rows, and a
-// plan-free window kernel.  Only the per-lane state differs: six vectors instead of two.
+// The schedule is csr_schedule.h's: every row, a dense-tile window's included, is a sparse-row task; a fix-up pass over split
+// rows follows.  The per-lane state is six vectors.
 //  * sum and sumsq run in CSR order inside a lane group, through the fixed xor-shuffle tree on wide tasks and in slot order
 //    (then the tree) in the fix-up: deterministic, no atomics.  The square is rounded before it is added (__fmul_rn: never
 //    contracted into an fma), so a sequentially summed row has the bits of an fp32 scan.  A sum never holds -0: it starts at
@@ -15,6 +14,7 @@
 //    on distinct positions, so the combine works on partial slots unchanged and gives a sequential scan's bits on any split.
 //  * One build computes all four; which are stored is a run-time matter (a null output is skipped).  A partial slot always
 //    holds all six arrays.
+#include "csr_schedule.h"
 #include "extremum_common.h"
 
 namespace hcspmm {
@@ -183,19 +183,6 @@ __device__ __forceinline__ void mtask(const MArgs& ma, int row, int slot, int e0
   }
 }
 
-// first CSR entry of the split-row segment that owns partial slot s (spmm_weighted_impl.h segment_entry)
-__device__ __forceinline__ int msegment_entry(const MArgs& ma, int s) {
-  const int4* fix = reinterpret_cast<const int4*>(ma.p.plan + ma.p.off_fixups);
-  int lo = 0, hi = ma.p.n_split_rows;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (fix[mid].y <= s) lo = mid;
-    else hi = mid;
-  }
-  const int4 f = fix[lo];
-  return ma.rowptr[f.x] + (s - f.y) * ma.segment_len;
-}
-
 // tiny_tasks (spmm_impl.h): T tasks of at most two entries per lane group, indices inline in the descriptor; the entry
 // position comes from rowptr (a whole row) or the fix-up list (the last segment of a split row)
 template <int L, int VEC, int T>
@@ -224,7 +211,7 @@ __device__ __forceinline__ void mtiny(const MArgs& ma, int first, int c0, int ce
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     e[t] = 0;
-    if (d[t].y >= 0) e[t] = d[t].x >= 0 ? ma.rowptr[d[t].x] : msegment_entry(ma, -(d[t].x + 1));
+    if (d[t].y >= 0) e[t] = d[t].x >= 0 ? ma.rowptr[d[t].x] : segment_entry(a, ma.rowptr, ma.segment_len, -(d[t].x + 1));
   }
   for (int pbase = c0; pbase < cend; pbase += L * VEC) {
     const bool cok = pbase + s * VEC < cend;
@@ -253,94 +240,18 @@ __device__ __forceinline__ void mtiny(const MArgs& ma, int first, int c0, int ce
   }
 }
 
-// the 16 rows of a window from CSR, R = 64 / L at a time (dense-tile windows of the plan; every window plan-free)
-template <int L, int VEC>
-__device__ __forceinline__ void mwindow_rows(const MArgs& ma, int window, int c0, int cend, int lane) {
-  constexpr int R = 64 / L;
-  const int g = lane / L;
-  for (int rb = 0; rb < 16; rb += R) {
-    const int r = window * 16 + rb + g;
-    int e0 = 0, n = 0, row = -1;
-    if (rb + g < 16 && r < ma.p.N) {
-      e0 = ma.rowptr[r];
-      n = ma.rowptr[r + 1] - e0;
-      row = r;
-    }
-    mtask<L, VEC, false>(ma, row, -1, e0, n, c0, cend, lane);
+// what csr_schedule.h's walks call
+template <int L, int VEC> struct MBody {
+  const MArgs& ma;
+  typedef RowSlot Dst;  // mstore finds the place
+  __device__ __forceinline__ Dst dst(int row, int slot) const { return Dst{row, slot}; }
+  template <bool WIDE> __device__ __forceinline__ void task(const Dst& o, int e0, int n, int c0, int cend, int lane) const {
+    mtask<L, VEC, WIDE>(ma, o.row, o.slot, e0, n, c0, cend, lane);
   }
-}
-
-// ------------------------------------------------------------------------------------------
-// Planned kernel: extremum_plan_kernel's decode (sliced | wide | ordinary | tiny per column panel, then one wave per
-// (dense-tile window, column panel) serving the window's rows from CSR).  Tiny tasks always run in their region here.
-// ------------------------------------------------------------------------------------------
-template <int L, int VEC, int MINW>
-__global__ __launch_bounds__(kThreads, MINW) void multi_plan_kernel(MArgs ma) {
-  const PlanArgs& a = ma.p;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if ((int)blockIdx.x < a.sparse_wgs) {
-    const int p = (int)blockIdx.x / a.sparse_wgs_pp;
-    const int b = (int)blockIdx.x - p * a.sparse_wgs_pp;
-    const int c0 = p * a.panel_cols;
-    const int cend = min(a.D, c0 + a.panel_cols);
-    const int bf = b - a.slice_wgs;
-    if (bf >= 0 && bf < a.wide_wgs) {
-      const int tid = bf * kWaves + wave;
-      if (tid >= a.n_wide) return;
-      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      mtask<L, VEC, true>(ma, t.x, t.w, __builtin_amdgcn_readfirstlane(t.y), __builtin_amdgcn_readfirstlane(t.z), c0, cend, lane);
-    } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
-      if (bf >= a.free_wgs_pp) return;
-      constexpr int R = 64 / L;
-      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * XTinyT<L>::value);
-      if (first >= a.n_tasks) return;
-      mtiny<L, VEC, XTinyT<L>::value>(ma, first, c0, cend, lane);
-    } else {
-      constexpr int R = 64 / L;
-      const int g = lane / L;
-      const int4* tp = nullptr;
-      if (bf < 0) {
-        cint_p tbl = (cint_p)(a.plan + a.off_slice_table);
-        int j = ((b >> 3) * kWaves + wave) * R;
-        for (int sl = b & 7; sl < a.n_slices; sl += 8) {
-          const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
-          if (j < cnt) {
-            tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + lo + j + g;
-            break;
-          }
-          j -= cnt;
-        }
-      } else {
-        const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
-      }
-      int e0 = 0, n = 0, row = -1, slot = -1;
-      if (tp != nullptr) {
-        const int4 t = *tp;
-        if (t.x >= 0) {  // (slice padding: row -1)
-          e0 = t.y;
-          n = t.z;
-          row = t.x;
-          slot = t.w;
-        }
-      }
-      mtask<L, VEC, false>(ma, row, slot, e0, n, c0, cend, lane);
-    }
-  } else {
-    const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-    const int unit = ((int)blockIdx.x - a.sparse_wgs) * kWaves + wave;
-    if (unit >= a.n_dense * n_col_panels) return;
-    const int p = unit / a.n_dense, di = unit - p * a.n_dense;
-    const int n_reg = a.n_dense - a.n_dense_compact - a.n_dense_compact2;
-    int window;
-    if (di < n_reg) window = ((cint_p)(a.plan + a.off_dense_index))[4 * di];
-    else if (di < n_reg + a.n_dense_compact2) window = ((cint_p)(a.plan + a.off_dense_compact2))[(di - n_reg) * HCSPMM_COMPACT2_WORDS];
-    else window = ((cint_p)(a.plan + a.off_dense_compact))[(di - n_reg - a.n_dense_compact2) * HCSPMM_COMPACT_WORDS];
-    const int c0 = p * a.panel_cols;
-    mwindow_rows<L, VEC>(ma, window, c0, min(a.D, c0 + a.panel_cols), lane);
+  __device__ __forceinline__ void tiny(int first, int c0, int cend, int lane) const {
+    mtiny<L, VEC, XTinyT<L>::value>(ma, first, c0, cend, lane);
   }
-}
+};
 
 // Fix-up: the six results of a split row from its partial slots -- one wave per row, the 64/L lane groups taking every
 // (64/L)-th slot in slot order and combined by the xor-shuffle tree (extremum_fixup_kernel's shape; two slots in flight per
@@ -403,85 +314,26 @@ __global__ __launch_bounds__(kThreads) void multi_fixup_kernel(MArgs ma) {
   }
 }
 
-// Plan-free kernel: one workgroup per 16-row window, every window (dense-tile or not) served from CSR: rows up to
-// kPlanFreeWide entries by one lane group each, longer ones by whole waves (extremum_window_kernel's shape)
-template <int L, int VEC, int MINW>
-__global__ __launch_bounds__(kThreads, MINW) void multi_window_kernel(MArgs ma) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = (int)blockDim.x >> 6;
-  const int r0 = (int)blockIdx.x * 16, r1 = min(r0 + 16, ma.p.N);
-  constexpr int R = 64 / L;
-  const int G = R * nwaves;
-  const int gi = wave * R + lane / L;
-  for (int rb = r0; rb < r1; rb += G) {
-    const int r = rb + gi;
-    int e0 = 0, n = 0, row = -1;
-    if (r < r1) {
-      e0 = ma.rowptr[r];
-      n = ma.rowptr[r + 1] - e0;
-      if (R == 1 || n <= kPlanFreeWide) row = r;
-      else n = 0;  // left to the whole-wave pass below
-    }
-    mtask<L, VEC, false>(ma, row, -1, e0, n, 0, ma.p.D, lane);
-  }
-  if (R > 1) {
-    int k = 0;
-    for (int r = r0; r < r1; ++r) {
-      const int e0 = ma.rowptr[r];
-      const int n = ma.rowptr[r + 1] - e0;
-      if (n > kPlanFreeWide) {
-        if (k % nwaves == wave) mtask<L, VEC, true>(ma, r, -1, e0, n, 0, ma.p.D, lane);
-        ++k;
-      }
-    }
-  }
-}
-
 constexpr int kMultiMinWaves = 4;  // 128 registers per lane
 
-template <int L, int VEC>
-hipError_t launch_multi_LV(const MArgs& ma, hipStream_t stream) {
-  MArgs mb = ma;
-  PlanArgs& b = mb.p;
-  if (ma.p.plan == nullptr) {  // plan-free
-    const int W = (b.N + 15) / 16;
-    int waves = (16 * L + 63) / 64;
-    if (waves > kWaves) waves = kWaves;
-    if (W > 0) hipLaunchKernelGGL((multi_window_kernel<L, VEC, kMultiMinWaves>), dim3(W), dim3(waves * 64), 0, stream, mb);
-    return hipGetLastError();
-  }
-  b.fused = 0;
-  // the shared layout (plan_layout.h), in the extremum form: no launch of their own for the tiny tasks, dense windows once
-  // per column panel
-  const int n_col_panels = plan_launch_layout(b, L, 0, 0, XTinyT<L>::value, false, 0);
-  const long long dense_wgs = ((long long)b.n_dense * n_col_panels + kWaves - 1) / kWaves;
-  const long long grid = (long long)b.sparse_wgs + dense_wgs;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (grid > 0)
-    hipLaunchKernelGGL((multi_plan_kernel<L, VEC, kMultiMinWaves>), dim3((unsigned)grid), dim3(kThreads), 0, stream, mb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || b.n_split_rows == 0) return e;
-  const int fg = (b.n_split_rows + kWaves - 1) / kWaves;
-  hipLaunchKernelGGL((multi_fixup_kernel<VEC>), dim3(fg), dim3(kThreads), 0, stream, mb);
-  return hipGetLastError();
+// the planned and the plan-free kernel (csr_schedule.h)
+template <int L, int VEC, int MINW>
+__global__ __launch_bounds__(kThreads, MINW) void multi_plan_kernel(MArgs ma) {
+  csr_plan_walk<L, XTinyT<L>::value>(ma.p, ma.rowptr, MBody<L, VEC>{ma});
+}
+template <int L, int VEC, int MINW>
+__global__ __launch_bounds__(kThreads, MINW) void multi_window_kernel(MArgs ma) {
+  csr_window_walk<L>(ma.p, ma.rowptr, MBody<L, VEC>{ma});
 }
 
 }  // namespace
 
 hipError_t launch_multi_f32(const MArgs& a, int vec, hipStream_t stream) {
-  if (vec == 4) {
-    switch (pick_L(a.p.plan != nullptr ? a.p.panel_cols : a.p.D, 4)) {
-      case 4: return launch_multi_LV<4, 4>(a, stream);
-      case 8: return launch_multi_LV<8, 4>(a, stream);
-      case 16: return launch_multi_LV<16, 4>(a, stream);
-      case 32: return launch_multi_LV<32, 4>(a, stream);
-      default: return launch_multi_LV<64, 4>(a, stream);
-    }
-  }
-  if (a.p.D > 4 * vec) return hipErrorInvalidValue;
-  if (vec == 2) return launch_multi_LV<4, 2>(a, stream);
-  return launch_multi_LV<4, 1>(a, stream);
+  return csr_dispatch(a.p, vec, [&](auto lv) {
+    constexpr int L = decltype(lv)::L, VEC = decltype(lv)::VEC;
+    return csr_launch(a, L, XTinyT<L>::value, multi_window_kernel<L, VEC, kMultiMinWaves>, multi_plan_kernel<L, VEC, kMultiMinWaves>,
+                      multi_fixup_kernel<VEC>, stream);
+  });
 }
 
 }  // namespace hcspmm

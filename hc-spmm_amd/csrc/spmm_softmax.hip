@@ -4,9 +4,8 @@
 // over the entries e of row r (DeeperGCN's softmax aggregation: beta -> +-inf is max / min, beta = 0 the mean), with the
 // statistics its backward needs: M = max_e s_e, L = sum_e exp(s_e - M) and Q = sum_e p_e fl(x_e * x_e).
 //
-// The schedule is spmm_multi.hip's, which is the hybrid launch's (spmm_impl.h): sliced | wide | ordinary | tiny regions per
-// column panel, the dense-tile windows served from CSR by the sparse-row task body, a fix-up pass over split rows, and a
-// plan-free window kernel.  Only the per-lane state differs: the online-softmax quadruple (m, l, a, q) per column,
+// The schedule is csr_schedule.h's: every row, a dense-tile window's included, is a sparse-row task; a fix-up pass over split
+// rows follows.  The per-lane state is the online-softmax quadruple (m, l, a, q) per column,
 //   m = running max of s,  l = sum exp(s - m),  a = sum exp(s - m) x,  q = sum exp(s - m) fl(x x).
 //  * ONE exponential per gathered element: with d = s - m and t = exp(-|d|), a new maximum (d > 0) rescales the state by t and
 //    adds the element with weight 1; otherwise the element is added with weight t.  The exponent never sees a positive
@@ -20,6 +19,7 @@
 //    bit the maximum of fl(beta x); the square is rounded before it is weighted.
 //  * One build computes all four; which of M, L, Q are stored is a run-time matter (a null output is skipped).  A partial
 //    slot always holds the four raw state arrays.
+#include "csr_schedule.h"
 #include "extremum_common.h"
 
 namespace hcspmm {
@@ -226,94 +226,18 @@ __device__ __forceinline__ void stiny(const SArgs& sa, int first, int c0, int ce
   }
 }
 
-// the 16 rows of a window from CSR, R = 64 / L at a time (dense-tile windows of the plan; every window plan-free)
-template <int L, int VEC>
-__device__ __forceinline__ void swindow_rows(const SArgs& sa, int window, int c0, int cend, int lane) {
-  constexpr int R = 64 / L;
-  const int g = lane / L;
-  for (int rb = 0; rb < 16; rb += R) {
-    const int r = window * 16 + rb + g;
-    int e0 = 0, n = 0, row = -1;
-    if (rb + g < 16 && r < sa.p.N) {
-      e0 = sa.rowptr[r];
-      n = sa.rowptr[r + 1] - e0;
-      row = r;
-    }
-    stask<L, VEC, false>(sa, row, -1, e0, n, c0, cend, lane);
+// what csr_schedule.h's walks call
+template <int L, int VEC> struct SBody {
+  const SArgs& sa;
+  typedef RowSlot Dst;  // sstore finds the place
+  __device__ __forceinline__ Dst dst(int row, int slot) const { return Dst{row, slot}; }
+  template <bool WIDE> __device__ __forceinline__ void task(const Dst& o, int e0, int n, int c0, int cend, int lane) const {
+    stask<L, VEC, WIDE>(sa, o.row, o.slot, e0, n, c0, cend, lane);
   }
-}
-
-// ------------------------------------------------------------------------------------------
-// Planned kernel: multi_plan_kernel's decode (sliced | wide | ordinary | tiny per column panel, then one wave per
-// (dense-tile window, column panel) serving the window's rows from CSR).  Tiny tasks always run in their region here.
-// ------------------------------------------------------------------------------------------
-template <int L, int VEC, int MINW>
-__global__ __launch_bounds__(kThreads, MINW) void softmax_plan_kernel(SArgs sa) {
-  const PlanArgs& a = sa.p;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if ((int)blockIdx.x < a.sparse_wgs) {
-    const int p = (int)blockIdx.x / a.sparse_wgs_pp;
-    const int b = (int)blockIdx.x - p * a.sparse_wgs_pp;
-    const int c0 = p * a.panel_cols;
-    const int cend = min(a.D, c0 + a.panel_cols);
-    const int bf = b - a.slice_wgs;
-    if (bf >= 0 && bf < a.wide_wgs) {
-      const int tid = bf * kWaves + wave;
-      if (tid >= a.n_wide) return;
-      const int4 t = reinterpret_cast<const int4*>(a.plan + a.off_tasks)[tid];
-      stask<L, VEC, true>(sa, t.x, t.w, __builtin_amdgcn_readfirstlane(t.y), __builtin_amdgcn_readfirstlane(t.z), c0, cend, lane);
-    } else if (bf >= sparse_wgs_pp_ordinary_end(a)) {
-      if (bf >= a.free_wgs_pp) return;
-      constexpr int R = 64 / L;
-      const int first = a.n_tasks - a.n_tiny + ((bf - sparse_wgs_pp_ordinary_end(a)) * kWaves + wave) * (R * XTinyT<L>::value);
-      if (first >= a.n_tasks) return;
-      stiny<L, VEC, XTinyT<L>::value>(sa, first, c0, cend, lane);
-    } else {
-      constexpr int R = 64 / L;
-      const int g = lane / L;
-      const int4* tp = nullptr;
-      if (bf < 0) {
-        cint_p tbl = (cint_p)(a.plan + a.off_slice_table);
-        int j = ((b >> 3) * kWaves + wave) * R;
-        for (int sl = b & 7; sl < a.n_slices; sl += 8) {
-          const int lo = tbl[sl], cnt = tbl[sl + 1] - lo;
-          if (j < cnt) {
-            tp = reinterpret_cast<const int4*>(a.plan + a.off_slice_tasks) + lo + j + g;
-            break;
-          }
-          j -= cnt;
-        }
-      } else {
-        const int tid = a.n_wide + ((bf - a.wide_wgs) * kWaves + wave) * R + g;
-        if (tid < a.n_tasks - a.n_tiny) tp = reinterpret_cast<const int4*>(a.plan + a.off_tasks) + tid;
-      }
-      int e0 = 0, n = 0, row = -1, slot = -1;
-      if (tp != nullptr) {
-        const int4 t = *tp;
-        if (t.x >= 0) {  // (slice padding: row -1)
-          e0 = t.y;
-          n = t.z;
-          row = t.x;
-          slot = t.w;
-        }
-      }
-      stask<L, VEC, false>(sa, row, slot, e0, n, c0, cend, lane);
-    }
-  } else {
-    const int n_col_panels = (a.D + a.panel_cols - 1) / a.panel_cols;
-    const int unit = ((int)blockIdx.x - a.sparse_wgs) * kWaves + wave;
-    if (unit >= a.n_dense * n_col_panels) return;
-    const int p = unit / a.n_dense, di = unit - p * a.n_dense;
-    const int n_reg = a.n_dense - a.n_dense_compact - a.n_dense_compact2;
-    int window;
-    if (di < n_reg) window = ((cint_p)(a.plan + a.off_dense_index))[4 * di];
-    else if (di < n_reg + a.n_dense_compact2) window = ((cint_p)(a.plan + a.off_dense_compact2))[(di - n_reg) * HCSPMM_COMPACT2_WORDS];
-    else window = ((cint_p)(a.plan + a.off_dense_compact))[(di - n_reg - a.n_dense_compact2) * HCSPMM_COMPACT_WORDS];
-    const int c0 = p * a.panel_cols;
-    swindow_rows<L, VEC>(sa, window, c0, min(a.D, c0 + a.panel_cols), lane);
+  __device__ __forceinline__ void tiny(int first, int c0, int cend, int lane) const {
+    stiny<L, VEC, XTinyT<L>::value>(sa, first, c0, cend, lane);
   }
-}
+};
 
 // Fix-up: the state of a split row from its partial slots -- one wave per row, the 64/L lane groups taking every (64/L)-th
 // slot in slot order and merged by the xor-shuffle tree (multi_fixup_kernel's shape; two slots in flight per lane, eight
@@ -366,85 +290,26 @@ __global__ __launch_bounds__(kThreads) void softmax_fixup_kernel(SArgs sa) {
   }
 }
 
-// Plan-free kernel: one workgroup per 16-row window, every window (dense-tile or not) served from CSR: rows up to
-// kPlanFreeWide entries by one lane group each, longer ones by whole waves (multi_window_kernel's shape)
-template <int L, int VEC, int MINW>
-__global__ __launch_bounds__(kThreads, MINW) void softmax_window_kernel(SArgs sa) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nwaves = (int)blockDim.x >> 6;
-  const int r0 = (int)blockIdx.x * 16, r1 = min(r0 + 16, sa.p.N);
-  constexpr int R = 64 / L;
-  const int G = R * nwaves;
-  const int gi = wave * R + lane / L;
-  for (int rb = r0; rb < r1; rb += G) {
-    const int r = rb + gi;
-    int e0 = 0, n = 0, row = -1;
-    if (r < r1) {
-      e0 = sa.rowptr[r];
-      n = sa.rowptr[r + 1] - e0;
-      if (R == 1 || n <= kPlanFreeWide) row = r;
-      else n = 0;  // left to the whole-wave pass below
-    }
-    stask<L, VEC, false>(sa, row, -1, e0, n, 0, sa.p.D, lane);
-  }
-  if (R > 1) {
-    int k = 0;
-    for (int r = r0; r < r1; ++r) {
-      const int e0 = sa.rowptr[r];
-      const int n = sa.rowptr[r + 1] - e0;
-      if (n > kPlanFreeWide) {
-        if (k % nwaves == wave) stask<L, VEC, true>(sa, r, -1, e0, n, 0, sa.p.D, lane);
-        ++k;
-      }
-    }
-  }
-}
-
 constexpr int kSoftMinWaves = 4;  // 128 registers per lane
 
-template <int L, int VEC>
-hipError_t launch_softmax_LV(const SArgs& sa, hipStream_t stream) {
-  SArgs sb = sa;
-  PlanArgs& b = sb.p;
-  if (sa.p.plan == nullptr) {  // plan-free
-    const int W = (b.N + 15) / 16;
-    int waves = (16 * L + 63) / 64;
-    if (waves > kWaves) waves = kWaves;
-    if (W > 0) hipLaunchKernelGGL((softmax_window_kernel<L, VEC, kSoftMinWaves>), dim3(W), dim3(waves * 64), 0, stream, sb);
-    return hipGetLastError();
-  }
-  b.fused = 0;
-  // the shared layout (plan_layout.h), in the extremum form: no launch of their own for the tiny tasks, dense windows once
-  // per column panel
-  const int n_col_panels = plan_launch_layout(b, L, 0, 0, XTinyT<L>::value, false, 0);
-  const long long dense_wgs = ((long long)b.n_dense * n_col_panels + kWaves - 1) / kWaves;
-  const long long grid = (long long)b.sparse_wgs + dense_wgs;
-  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (grid > 0)
-    hipLaunchKernelGGL((softmax_plan_kernel<L, VEC, kSoftMinWaves>), dim3((unsigned)grid), dim3(kThreads), 0, stream, sb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || b.n_split_rows == 0) return e;
-  const int fg = (b.n_split_rows + kWaves - 1) / kWaves;
-  hipLaunchKernelGGL((softmax_fixup_kernel<VEC>), dim3(fg), dim3(kThreads), 0, stream, sb);
-  return hipGetLastError();
+// the planned and the plan-free kernel (csr_schedule.h)
+template <int L, int VEC, int MINW>
+__global__ __launch_bounds__(kThreads, MINW) void softmax_plan_kernel(SArgs sa) {
+  csr_plan_walk<L, XTinyT<L>::value>(sa.p, sa.rowptr, SBody<L, VEC>{sa});
+}
+template <int L, int VEC, int MINW>
+__global__ __launch_bounds__(kThreads, MINW) void softmax_window_kernel(SArgs sa) {
+  csr_window_walk<L>(sa.p, sa.rowptr, SBody<L, VEC>{sa});
 }
 
 }  // namespace
 
 hipError_t launch_softmax_f32(const SArgs& a, int vec, hipStream_t stream) {
-  if (vec == 4) {
-    switch (pick_L(a.p.plan != nullptr ? a.p.panel_cols : a.p.D, 4)) {
-      case 4: return launch_softmax_LV<4, 4>(a, stream);
-      case 8: return launch_softmax_LV<8, 4>(a, stream);
-      case 16: return launch_softmax_LV<16, 4>(a, stream);
-      case 32: return launch_softmax_LV<32, 4>(a, stream);
-      default: return launch_softmax_LV<64, 4>(a, stream);
-    }
-  }
-  if (a.p.D > 4 * vec) return hipErrorInvalidValue;
-  if (vec == 2) return launch_softmax_LV<4, 2>(a, stream);
-  return launch_softmax_LV<4, 1>(a, stream);
+  return csr_dispatch(a.p, vec, [&](auto lv) {
+    constexpr int L = decltype(lv)::L, VEC = decltype(lv)::VEC;
+    return csr_launch(a, L, XTinyT<L>::value, softmax_window_kernel<L, VEC, kSoftMinWaves>, softmax_plan_kernel<L, VEC, kSoftMinWaves>,
+                      softmax_fixup_kernel<VEC>, stream);
+  });
 }
 
 }  // namespace hcspmm

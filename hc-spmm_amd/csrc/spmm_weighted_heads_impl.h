@@ -164,12 +164,12 @@ __device__ __forceinline__ void tiny_tasks_wh(const WHPlanArgs& ha, int first, i
   for (int t = 0; t < T; ++t) {
     if constexpr (INDEXED) {
       int e = 0;
-      if (d[t].y >= 0) e = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(wa, -(d[t].x + 1));
+      if (d[t].y >= 0) e = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(a, wa.rowptr, wa.segment_len, -(d[t].x + 1));
       p0[t] = d[t].y >= 0 ? ha.vindex[e] : 0;
       p1[t] = d[t].w >= 0 ? ha.vindex[e + 1] : 0;
     } else {
       p0[t] = 0;
-      if (d[t].y >= 0) p0[t] = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(wa, -(d[t].x + 1));
+      if (d[t].y >= 0) p0[t] = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(a, wa.rowptr, wa.segment_len, -(d[t].x + 1));
     }
   }
   for (int pbase = c0; pbase < cend; pbase += L * VEC) {

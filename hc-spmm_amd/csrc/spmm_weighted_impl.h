@@ -21,7 +21,7 @@
 // that loads col[e] loads the scale behind it (one dependent 4-byte gather) and multiplies before the broadcast, so the
 // gathering lanes see one weight per entry, as in the fp32 / 16-bit builds.
 #pragma once
-#include "spmm_impl.h"
+#include "csr_schedule.h"  // segment_entry: a partial slot's first CSR entry
 
 namespace hcspmm {
 
@@ -162,20 +162,6 @@ __device__ __forceinline__ void sparse_task_w(const typename E::T* __restrict__ 
   }
 }
 
-// first CSR entry of the split row segment that owns partial slot s: the fix-up list (row, first slot, segment count) is
-// ascending in its first slot, and segment k of a row covers entries rowptr[row] + k*segment_len ... (plan_host.cpp)
-__device__ __forceinline__ int segment_entry(const WPlanArgs& wa, int s) {
-  const int4* fix = reinterpret_cast<const int4*>(wa.p.plan + wa.p.off_fixups);
-  int lo = 0, hi = wa.p.n_split_rows;  // largest i with fix[i].y <= s
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (fix[mid].y <= s) lo = mid;
-    else hi = mid;
-  }
-  const int4 f = fix[lo];
-  return wa.rowptr[f.x] + (s - f.y) * wa.segment_len;
-}
-
 // tiny_tasks (spmm_impl.h) with weights: the entry position comes from rowptr (a whole row) or the fix-up list (the last
 // segment of a split row); the value loads follow it, next to the row gathers
 template <typename E, int L, int VEC, int T>
@@ -206,7 +192,7 @@ __device__ __forceinline__ void tiny_tasks_w(const WPlanArgs& wa, int first, int
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     int e = 0;
-    if (d[t].y >= 0) e = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(wa, -(d[t].x + 1));
+    if (d[t].y >= 0) e = d[t].x >= 0 ? wa.rowptr[d[t].x] : segment_entry(a, wa.rowptr, wa.segment_len, -(d[t].x + 1));
     w0[t] = d[t].y >= 0 ? entry_weight(weights_of<E>(wa) + e, d[t].y) : 0.f;
     w1[t] = d[t].w >= 0 ? entry_weight(weights_of<E>(wa) + (e + 1), d[t].w) : 0.f;
   }
