@@ -1078,6 +1078,85 @@ class GENConv(torch.nn.Module):
         return _Update.apply(X + agg, self.weights)
 
 
+class GatedAggregate(torch.autograd.Function):
+    """Z[i] = sum over the entries (i, j) of sigmoid(P[i] + Q[j]) * V[j] (HCSPMM.forward_gated: one gather pass, no per-entry
+    tensor), with gradients for P, Q and V from the same launch -- no kernel beyond the forward's.  With G = dZ:
+      dP = G * T, T[i] = sum_j sigmoid'(P[i] + Q[j]) * V[j]: the forward launch's second output, asked for only when P needs a
+           gradient;
+      dV = Y_gate and dQ = V * Y_dgate of ONE two-output call on the graph the backward walks, with own rows Q and gathered
+           (P, G): fl(Q[j] + P[i]) has the bits of fl(P[i] + Q[j]), so the gates are the forward's.
+    A training step is two gather passes.  tail = the eight graph tensors of A followed by the eight of the graph the backward
+    walks (A itself when the pattern is symmetric, else transposed_graph's)."""
+
+    @staticmethod
+    def forward(ctx, P, Q, V, *tail):
+        need_p = ctx.needs_input_grad[0]
+        Z, T = HCSPMM.forward_gated(P, Q, V, *tail[:N_GRAPH], ("gate", "dgate") if need_p else ("gate",))
+        ctx.save_for_backward(P, Q, V, T, *tail[N_GRAPH:])
+        return Z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward is a launch, not a graph of differentiable ops
+    def backward(ctx, d_out):
+        P, Q, V, T, *graph_b = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_p = d_q = d_v = None
+        if ctx.needs_input_grad[0]:
+            d_p = d_out * T
+        need_q, need_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if need_q or need_v:
+            names = (("gate",) if need_v else ()) + (("dgate",) if need_q else ())
+            d_v, y_dgate = HCSPMM.forward_gated(Q, P, d_out, *graph_b, names)
+            if need_q:
+                d_q = V * y_dgate
+        return (d_p, d_q, d_v) + (None,) * (2 * N_GRAPH)
+
+
+def gated_aggregate(P, Q, V, graph, directed=False):
+    """Gated sum over each row's neighbours, Z[i] = sum_j sigmoid(P[i] + Q[j]) * V[j] per feature column, with autograd for P
+    [N, D], Q and V (float32 views with unit inner stride: column blocks of one projection pass as they are).  graph = the eight
+    graph tensors, whose pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True:
+    the backward then runs on transposed_graph(graph).  Rows without entries give 0."""
+    if directed:
+        return GatedAggregate.apply(P, Q, V, *graph, *transposed_graph(graph)[:N_GRAPH])
+    transpose_permutation_i32(graph[0], graph[1])  # an asymmetric pattern is refused before any launch (cached)
+    return GatedAggregate.apply(P, Q, V, *graph, *graph)
+
+
+class ResGatedGraphConv(torch.nn.Module):
+    """Residual gated graph convolution (Bresson & Laurent; PyG ResGatedGraphConv, the GatedGCN of the GNN benchmarks):
+      out[i] = X[i] W_s + sum_j sigmoid(X[i] W_k + X[j] W_q) * (X[j] W_v)
+    ONE product X [W_k | W_q | W_v | W_s] on _Update gives [N, 4H] -- Q and V sit side by side in a gathered row -- then
+    gated_aggregate on its column blocks, without a copy.  root_weight=False drops the X W_s term (weights [input_dim, 3H]);
+    bias=True adds a learnt [H] vector.  _Conv's call signature, so that Net builds it; edge_weight is refused.  The pattern
+    must be symmetric unless directed=True (the backward then runs on transposed_graph)."""
+
+    def __init__(self, input_dim, output_dim, directed=False, root_weight=True, bias=False):
+        super().__init__()
+        self.directed, self.root_weight, self.output_dim = bool(directed), bool(root_weight), int(output_dim)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, (4 if root_weight else 3) * output_dim))
+        self.bias = torch.nn.Parameter(torch.empty(output_dim)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.output_dim)
+        self.weights.data.uniform_(-stdv, stdv)
+        if self.bias is not None:
+            self.bias.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr,
+                col_nzr, output=None, edge_weight=None):
+        if edge_weight is not None:
+            raise ValueError("ResGatedGraphConv weighs its messages with its own gates: edge_weight is not accepted")
+        graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        H = self.output_dim
+        proj = _Update.apply(X, self.weights)
+        out = gated_aggregate(proj[:, :H], proj[:, H:2 * H], proj[:, 2 * H:3 * H], graph, self.directed)
+        if self.root_weight:
+            out = out + proj[:, 3 * H:]
+        return out if self.bias is None else out + self.bias
+
+
 class EdgeMessageAggregate(torch.autograd.Function):
     """Z[i] = sum over the entries e = (i, j) of m(X[j], F[e]) (HCSPMM.forward_edge_messages; op "mul" x * f, "add_relu"
     relu(x + f), "copy" f) with gradients for X and F [E, D].  dF is HCSPMM.edge_messages_grad; dX is the same forward on A^T:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GCN / GIN / GINE / GAT / GATv2 / SAGE / PNA / GEN training driver and single-kernel profiler over the HCSPMM operators -- counterpart
+"""GCN / GIN / GINE / GAT / GATv2 / SAGE / PNA / GEN / ResGated training driver and single-kernel profiler over the HCSPMM operators -- counterpart
 of the reference's HC-SpMM_main.py (same eight flags, HC-SpMM_main.py:18-27, same printed lines
 "Prep. (ms)" :54 and "=> SAG profiling avg (ms)" GNN_model.py:261, same model shape :66-110, same
 schedule: 9 untimed warm-up epochs then --epochs timed ones, Adam lr 0.01, nll_loss :114-158).
@@ -24,7 +24,7 @@ for _p in (HERE, os.path.join(HERE, "hybrid_kernel")):
 import HCSPMM  # noqa: E402  (the torch extension built in hybrid_kernel/)
 from config import BLK_H  # noqa: E402
 from dataset import HCSPMM_dataset  # noqa: E402
-from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, SAGEConv, sampled_graph, tqdm  # noqa: E402
+from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, ResGatedGraphConv, SAGEConv, sampled_graph, tqdm  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -35,7 +35,7 @@ def parse_args(argv=None):
     p.add_argument("--hidden", type=int, default=32, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage", "pna", "gen"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "gine", "gat", "gatv2", "sage", "pna", "gen", "resgated"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     # addition (the reference keeps this idea commented out, HC-SpMM_main.py:143-155): replay the whole
     # training step from a HIP graph -- on small graphs an epoch is launch-bound, not kernel-bound
@@ -92,6 +92,17 @@ def parse_args(argv=None):
         p.error("--aggr does not apply to --model gen: GENConv aggregates with its softmax weights")
     if args.model == "gen" and args.norm != "none":
         p.error("--norm does not apply to --model gen: its edge values are the softmax weights")
+    # addition: --model resgated (GNN_model.ResGatedGraphConv: out = x W_s + sum_j sigmoid(x W_k + x_j W_q) * x_j W_v, the sum one
+    # gated gather pass); its edge values are the gates
+    if args.model == "resgated":
+        if args.aggr is not None:
+            p.error("--aggr does not apply to --model resgated: ResGatedGraphConv sums its gated messages")
+        if args.norm != "none":
+            p.error("--norm does not apply to --model resgated: its edge values are the gates")
+        if args.fp8:
+            p.error("--fp8 does not apply to --model resgated: the gated aggregation is fp32")
+        if args.heads > 1:
+            p.error("--heads does not apply to --model resgated: the gate is per feature column")
     # addition: --model pna (GNN_model.PNAConv: mean / min / max / std of the neighbours from one gather pass, times degree scalers);
     # its aggregators are the layer's own, so --aggr is refused
     if args.model == "pna" and args.aggr is not None:
@@ -240,6 +251,9 @@ def main(argv=None):
     if args.model == "gen":
         def conv_cls(input_dim, output_dim, fixed):
             return GENConv(input_dim, output_dim, t=args.gen_t, learn_t=args.gen_learn_t, directed=directed)
+    if args.model == "resgated":
+        def conv_cls(input_dim, output_dim, fixed):
+            return ResGatedGraphConv(input_dim, output_dim, directed=directed)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated

@@ -691,6 +691,44 @@ extern "C" int hcspmm_softmax_backward(const float* grad_Z, const float* Z, cons
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+extern "C" size_t hcspmm_gated_workspace_bytes(const hcspmm_plan_header* ph, int D) { return 2 * hcspmm_workspace_bytes(ph, D); }
+
+// Gated neighbour aggregation (spmm_gated.hip): a plain-sum launch per output on the binary product's plan, P read by row, Q and V
+// gathered; one workspace area per output.
+extern "C" int hcspmm_forward_gated(const float* P, int64_t ldp, const float* Q, int64_t ldq, const float* V, int64_t ldv,
+                                    int64_t src_rows, float* Z_gate, float* Z_dgate, int64_t ldz, const int32_t* rowptr,
+                                    const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
+                                    const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
+                                    const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
+                                    size_t workspace_bytes, void* stream_v) {
+  if (N < 0 || E < 0 || src_rows < 0 || D <= 0 || ldp < D || ldq < D || ldv < D || ldz < D) return HCSPMM_EINVAL;
+  if (!Z_gate && !Z_dgate) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!P || !rowptr || (E > 0 && (!col || !Q || !V || src_rows == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::GatedArgs a{};
+  // workspace: two areas of hcspmm_workspace_bytes each, one per output (a single-output call uses the first)
+  const int rc = bind_graph(a.p, GRAPH_IN, D, src_rows, workspace, workspace_bytes, 2, HCSPMM_DTYPE_F32);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.plan) {
+    a.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+    a.segment_len = ph->segment_len;
+  }
+  a.outputs = (Z_gate ? 1 : 0) | (Z_dgate ? 2 : 0);
+  set_operands(a.p, nullptr, Z_gate ? Z_gate : Z_dgate, ldp, ldz);
+  a.z2 = Z_gate ? Z_dgate : nullptr;
+  a.rowptr = rowptr;
+  a.P = P;
+  a.Q = Q;
+  a.V = V;
+  a.ldp = (size_t)ldp;
+  a.ldq = (size_t)ldq;
+  a.ldv = (size_t)ldv;
+  const int vec = pick_vec(HCSPMM_DTYPE_F32, D, ldp, ldz, P, nullptr, nullptr);
+  const hipError_t e = hcspmm::launch_gated_f32(a, vec, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 // Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
 // every call.
 extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64_t ldx, const float* F, int64_t f_rows, int64_t ldf,

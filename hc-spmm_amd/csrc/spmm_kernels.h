@@ -355,5 +355,23 @@ struct EdgeMsgGradArgs {
 };
 hipError_t launch_edge_messages_grad_f32(const EdgeMsgGradArgs& a, int vec, hipStream_t stream);
 
+// Gated neighbour aggregation (spmm_gated.hip; include/hcspmm.h hcspmm_forward_gated), fp32: with z = fl(P[r] + Q[col(e)]),
+// Z_gate[r] = sum over the entries e of row r of sigma(z) * V[col(e)] and Z_dgate[r] the same sum with sigma'(z).  p as for
+// launch_softmax_backward_f32 with p.X unused: P holds the tasks' OWN rows (N of them), Q and V are gathered through the column
+// ids.  outputs: bit 0 = Z_gate, bit 1 = Z_dgate.  p.Z / p.partial take the first output that is asked for; with both, z2 and
+// the workspace area `area` floats behind p.partial take Z_dgate (same row stride p.ldz).
+struct GatedArgs {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  int outputs;
+  const float *P, *Q, *V;
+  size_t ldp, ldq, ldv;
+  float* z2;
+  size_t area;        // floats per workspace area
+};
+// vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
+hipError_t launch_gated_f32(const GatedArgs& a, int vec, hipStream_t stream);
+
 
 }  // namespace hcspmm

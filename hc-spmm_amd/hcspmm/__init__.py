@@ -30,7 +30,7 @@ __all__ = [
     "transpose_graph", "transpose_graph_device", "sample_row_pointers", "sample_neighbors", "plan_free_graph",
     "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
-    "forward_softmax", "softmax_backward",
+    "forward_softmax", "softmax_backward", "forward_gated",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
@@ -868,6 +868,59 @@ def softmax_backward(grad_Z, Z, M, L, X, beta, row_pointers, column_index, block
         check(lib().hcspmm_softmax_backward(_ptr(grad_Z), _ptr(Z), _ptr(M), _ptr(L), D, grad_Z.size(0), _ptr(X), X.stride(0),
                                             _ptr(b), _ptr(grad_X), D, *c.graph, *c.ws))
     return grad_X
+
+
+def _ws_bytes_gated(h, D):
+    return int(lib().hcspmm_gated_workspace_bytes(ctypes.byref(h), D))
+
+
+GATED_OUTPUTS = ("gate", "dgate")
+
+
+def forward_gated(P, Q, V, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                  outputs=("gate",)):
+    """Gated neighbour aggregation in one gather pass -> (Z_gate, Z_dgate) (hcspmm.h hcspmm_forward_gated): with
+    z = P[i] + Q[j] over the entries (i, j) of row i, Z_gate[i] = sum_j sigmoid(z) * V[j] and Z_dgate[i] = sum_j sigmoid'(z) * V[j],
+    contiguous float32 [N, D].  outputs names some of "gate", "dgate"; an output not asked for is None, and one asked for has
+    the same bits whether or not the other is.  P: float32 [N, D]; Q, V: float32 [rows, D] (rows >= the columns the graph refers
+    to); all three 2-D views with unit inner stride and their own row strides (column blocks of one projection pass as they
+    are).  Rows without entries give 0.  No per-entry tensor is built."""
+    outputs = (outputs,) if isinstance(outputs, (str, bytes)) else tuple(outputs)
+    for n in outputs:
+        if n not in GATED_OUTPUTS:
+            raise ValueError("outputs must name some of 'gate', 'dgate', got %r" % (n,))
+    if not outputs:
+        raise ValueError("outputs must name at least one of 'gate', 'dgate'")
+    want = [n in outputs for n in GATED_OUTPUTS]
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    for t in (P, Q, V):
+        if not t.is_cuda:
+            raise RuntimeError("P, Q and V must be CUDA tensors")
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+            raise RuntimeError("P, Q and V must be 2-D float32 views with unit inner stride (gated aggregation is float32 only)")
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), Q.size(1)
+    if D == 0:
+        raise RuntimeError("P, Q and V must have at least one column")
+    if P.size(1) != D or V.size(1) != D:
+        raise RuntimeError("P, Q and V must have the same width, got %d, %d and %d" % (P.size(1), D, V.size(1)))
+    if V.size(0) != Q.size(0):
+        raise RuntimeError("Q and V must have the same number of rows, got %d and %d" % (Q.size(0), V.size(0)))
+    if P.device != Q.device or V.device != Q.device:
+        raise RuntimeError("P, Q and V must be on one device")
+    if P.size(0) != N:
+        raise RuntimeError("P has %d rows but the graph has %d nodes" % (P.size(0), N))
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, Q.size(0),
+                      Q.device, ws_fn=_ws_bytes_gated)
+    if E > 0 and Q.size(0) == 0:
+        raise RuntimeError("Q and V have no rows but the graph has %d entries" % E)
+    Z = [torch.empty((N, D), dtype=torch.float32, device=Q.device) if w else None for w in want]
+    if N == 0:
+        return tuple(Z)
+    null = ctypes.c_void_p(0)
+    with c:
+        check(lib().hcspmm_forward_gated(_ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(V), V.stride(0), Q.size(0),
+                                         *(_ptr(z) if z is not None else null for z in Z), D, *c.graph, *c.ws))
+    return tuple(Z)
 
 
 EDGE_OPS = {"mul": 0, "add_relu": 1, "copy": 2}  # include/hcspmm.h HCSPMM_EDGE_OP_*

@@ -113,6 +113,9 @@ SYMBOLS = {
                                       _i64, _int, _vp, _sz, _vp]),
     "hcspmm_softmax_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp,
                                        _i64, _i64, _int, _vp, _sz, _vp]),
+    "hcspmm_gated_workspace_bytes": (_sz, [_hp, _int]),
+    "hcspmm_forward_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp,
+                                    _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_forward_edge_messages": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_edge_messages_grad": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _i64, _int, _vp]),

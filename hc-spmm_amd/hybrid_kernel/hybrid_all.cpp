@@ -545,6 +545,61 @@ spmm_forward_softmax(torch::Tensor input, pybind11::object beta, torch::Tensor n
   return {Z, stats[0], stats[1], stats[2]};
 }
 
+// Gated neighbour aggregation (hcspmm_forward_gated): P [num_nodes, D] read by row, Q and V [rows, D] gathered through the column
+// ids; float32 views with unit inner stride and independent row strides -> (Z_gate, Z_dgate), None for what `outputs` (some of
+// "gate", "dgate") leaves out
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> spmm_forward_gated(
+    torch::Tensor P, torch::Tensor Q, torch::Tensor V, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
+    torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
+    pybind11::object outputs) {
+  static const char* const kNames[2] = {"gate", "dgate"};
+  bool want[2] = {false, false};
+  if (pybind11::isinstance<pybind11::str>(outputs)) outputs = pybind11::make_tuple(outputs);
+  if (!pybind11::isinstance<pybind11::iterable>(outputs)) throw pybind11::value_error("outputs must name some of 'gate', 'dgate'");
+  for (const auto& item : outputs) {
+    if (!pybind11::isinstance<pybind11::str>(item)) throw pybind11::value_error("outputs must name some of 'gate', 'dgate'");
+    const std::string a = pybind11::cast<std::string>(item);
+    int k = 0;
+    while (k < 2 && a != kNames[k]) ++k;
+    if (k == 2) throw pybind11::value_error("outputs must name some of 'gate', 'dgate', got '" + a + "'");
+    want[k] = true;
+  }
+  if (!want[0] && !want[1]) throw pybind11::value_error("outputs must name at least one of 'gate', 'dgate'");
+  for (const torch::Tensor* t : {&P, &Q, &V}) {
+    TORCH_CHECK(t->is_cuda(), "P, Q and V must be CUDA tensors");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
+                "P, Q and V must be 2-D float32 views with unit inner stride (gated aggregation is float32 only)");
+  }
+  TORCH_CHECK(Q.size(1) > 0, "P, Q and V must have at least one column");
+  TORCH_CHECK(P.size(1) == Q.size(1) && V.size(1) == Q.size(1), "P, Q and V must have the same width, got ", P.size(1), ", ",
+              Q.size(1), " and ", V.size(1));
+  TORCH_CHECK(V.size(0) == Q.size(0), "Q and V must have the same number of rows, got ", Q.size(0), " and ", V.size(0));
+  TORCH_CHECK(P.device() == Q.device() && V.device() == Q.device(), "P, Q and V must be on one device");
+  CallOptions o;
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_gated_workspace_bytes;  // one area of partial slots per output
+  PlannedCall c(&Q, Q, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  TORCH_CHECK(P.size(0) == c.N, "P has ", P.size(0), " rows but the graph has ", c.N, " nodes");
+  TORCH_CHECK(c.E == 0 || Q.size(0) > 0, "Q and V have no rows but the graph has ", c.E, " entries");
+  c10::optional<torch::Tensor> out[2];
+  float* zp[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    if (!want[k]) continue;
+    auto t = torch::empty({c.N, (int64_t)c.D}, Q.options());
+    zp[k] = c.N > 0 ? t.data_ptr<float>() : nullptr;
+    out[k] = t;
+  }
+  if (c.N > 0) {
+    const bool any = Q.size(0) > 0;
+    const int rc = invoke(hcspmm_forward_gated,
+                          std::make_tuple(P.data_ptr<float>(), P.stride(0), any ? Q.data_ptr<float>() : nullptr, Q.stride(0),
+                                          any ? V.data_ptr<float>() : nullptr, V.stride(0), Q.size(0), zp[0], zp[1], c.D),
+                          c.graph(), c.ws());
+    check_rc(rc, "forward_gated");
+  }
+  return {out[0], out[1]};
+}
+
 // Its gradient with respect to X (hcspmm_softmax_backward) on the graph the backward walks: grad_Z, Z, M, L contiguous float32
 // [rows, D] of the forward, input the float32 [num_nodes, D] view the forward gathered
 torch::Tensor spmm_softmax_backward(torch::Tensor grad_Z, torch::Tensor Z, torch::Tensor M, torch::Tensor L, torch::Tensor input,
@@ -1439,6 +1494,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_backward", &spmm_softmax_backward,
         "gradient of forward_softmax with respect to X -> grad_X, on the graph the backward walks (A^T's tensors, or A's own for a "
         "symmetric pattern); the weights are recomputed from M and L (gfx950)");
+  m.def("forward_gated", &spmm_forward_gated,
+        "gated neighbour aggregation in one gather pass -> (Z_gate, Z_dgate): Z_gate[i] = sum_j sigmoid(P[i] + Q[j]) * V[j], "
+        "Z_dgate the same sum with the sigmoid's derivative; an output `outputs` leaves out is None (gfx950)",
+        pybind11::arg("P"), pybind11::arg("Q"), pybind11::arg("V"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("outputs") = pybind11::make_tuple("gate"));
   m.def("forward_extremum_backward", &spmm_forward_extremum_backward,
         "backward of forward_max / forward_min -> grad_X: a square, pattern-symmetric graph with perm = int32 transpose_permutation, "
         "or any square graph's A^T (transpose_graph's tensors and their preprocessing) with perm = entry_index_t (gfx950)");

@@ -35,7 +35,8 @@ extern "C" {
  * hcspmm_wide_threshold_fp8 (round 13); hcspmm_forward_edge_messages, hcspmm_edge_messages_grad (round 14);
  * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15); hcspmm_softmax_workspace_bytes, hcspmm_forward_softmax,
  * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
- * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19).
+ * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
+ * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -548,6 +549,44 @@ int hcspmm_softmax_backward(const float* grad_Z_d, const float* Z_d, const float
                             const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
                             const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
                             int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Gated neighbour aggregation (residual gated graph convolution, Bresson & Laurent; PyG ResGatedGraphConv): a message that
+ * depends on the DESTINATION row as well as on the gathered one, with no per-entry tensor.  For entry e = (r, c) of row r,
+ * c = column_index[e], and z = fl32(P[r][d] + Q[c][d]) (one fp32 add, never contracted):
+ *   Z_gate [r][d] = sum_e sigma (z) * V[c][d]        sigma (z) = 1 / (1 + exp(-z))
+ *   Z_dgate[r][d] = sum_e sigma'(z) * V[c][d]        sigma'(z) = sigma(z) (1 - sigma(z))
+ * The exponential never takes a positive argument: t = exp(-|z|), r = 1 / (1 + t), sigma = z >= 0 ? r : t r, sigma' = t r r,
+ * each product rounded once, then acc = fmaf(sigma, v, acc).  Where exp(-|z|) underflows to 0 (|z| >= 104) sigma is EXACTLY 1
+ * for z > 0 and exactly 0 for z < 0, and sigma' is exactly 0; a NaN in z propagates; +-inf behaves as the limit.
+ *   P_d      fp32 [num_nodes][ldp], indexed by the row itself
+ *   Q_d, V_d fp32 [src_rows][ldq] / [src_rows][ldv], indexed by column ids (src_rows may differ from num_nodes: a rectangular
+ *            block).  The three strides are independent: three column blocks of one projection pass as they are
+ *   Z_gate_d, Z_dgate_d  fp32 [num_nodes][ldz]; either may be NULL and is then neither computed nor written, at least one
+ *            must be set.  With both set, both sums come out of ONE gather pass, and each has the bits of its single-output call
+ * It runs on the binary product's preprocessing and plan, or plan-free, every row served from CSR as in
+ * hcspmm_forward_extremum (a matrix core takes no per-column gate).  Each (r, d) is summed in hcspmm_forward_weighted's order:
+ * CSR order on ordinary and tiny tasks and on the rows of dense-tile windows, the wide tasks' shuffle tree on wide tasks, fp32
+ * partials and a fix-up pass in fixed order for sliced and segmented rows.  No atomics: two calls give the same bits.  Rows
+ * without entries get +0.0 in every set output.  A column stored twice in a row counts twice.
+ * workspace_d >= hcspmm_gated_workspace_bytes() (one area of partial slots per output).  Every embedding_dim
+ * hcspmm_forward_extremum serves.  NULL P_d / Q_d / V_d with rows to serve, both outputs NULL, ldp / ldq / ldv / ldz <
+ * embedding_dim, embedding_dim <= 0, negative sizes and NULL graph arrays are HCSPMM_EINVAL before any device call; plan and
+ * workspace errors as hcspmm_forward_softmax (src_rows against the rows the plan gathers).  num_nodes == 0 returns HCSPMM_OK
+ * without a launch.  Asynchronous on `stream`, allocates nothing, capturable.  Separate kernels (spmm_gated.hip).
+ * The gradients need no further kernel and no per-entry tensor.  With G = grad_Z_gate:
+ *   grad_P = G * Z_dgate(P, Q, V)                      (element-wise; ask the forward call for both outputs)
+ *   on the graph the backward walks (A^T's tensors and plan, or A's own for a symmetric pattern), one two-output call with
+ *   own rows P := Q and gathered (Q, V) := (P, G):   grad_V = Y_gate,   grad_Q = V * Y_dgate
+ * fl32(Q[j] + P[i]) has the bits of fl32(P[i] + Q[j]), so the gates are the forward's.
+ * ---------------------------------------------------------------------------------------- */
+size_t hcspmm_gated_workspace_bytes(const hcspmm_plan_header* header_h, int embedding_dim); /* 2 x hcspmm_workspace_bytes */
+int hcspmm_forward_gated(const float* P_d, int64_t ldp, const float* Q_d, int64_t ldq, const float* V_d, int64_t ldv,
+                         int64_t src_rows, float* Z_gate_d, float* Z_dgate_d, int64_t ldz, const int32_t* row_pointers_d,
+                         const int32_t* column_index_d, const int32_t* blockPartition_d, const int32_t* edgeToColumn_d,
+                         const int32_t* edgeToRow_d, const int32_t* hybrid_type_d, const int32_t* plan_d,
+                         const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                         void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge-feature messages (GINE, SchNet / CFConv continuous filters, edge-gated convolutions, "sum the incident edge vectors"):
