@@ -10,6 +10,8 @@ sibling files (1 200 - 16 000 rows) every one of these decisions falls the same 
   D  automatic column slices (plan_host.cpp): the XCD-affine sliced region without being asked;
   E  GATv2 backward tiles (gatv2_attention.hip kGradMaxBlocks): more than 4096 tiles -> a workgroup walks several;
   F  edge_norm grid cap (spmm_weighted.hip): more than 65 536 * 256 entries -> second round of the grid-stride loop.
+Gates B, C and D for the other users of the shared CSR walk (multi-aggregate, softmax aggregation and its backward, edge
+messages, gated aggregation) are test_z_scale_walk_gpu.py's, on this module's power-law graph.
 
 The coverage tests assert, through the library's own queries, that every graph below really is on the far side of its gate
 (no environment override: the shipped defaults are the subject).  The value tests restate the criteria of the sibling files
