@@ -1112,15 +1112,69 @@ class GatedAggregate(torch.autograd.Function):
         return (d_p, d_q, d_v) + (None,) * (2 * N_GRAPH)
 
 
-def gated_aggregate(P, Q, V, graph, directed=False):
+GATHER_DTYPES = (None, torch.bfloat16, torch.float16)
+
+
+def _cast_blocks(dtype, *blocks):
+    """16-bit copies of 2-D views.  Adjacent column blocks of one buffer (the layer's [N, 3H] projection) are cast in ONE
+    node-sized pass and stay column-block views of the copy; anything else is cast block by block."""
+    first = blocks[0]
+    D, step = first.size(1), first.element_size()
+    if first.dim() == 2 and first.stride(1) == 1 and first.stride(0) >= len(blocks) * D and all(
+            b.size() == first.size() and b.stride() == first.stride() and b.data_ptr() == first.data_ptr() + k * D * step
+            for k, b in enumerate(blocks)):
+        whole = first.as_strided((first.size(0), len(blocks) * D), (first.stride(0), 1)).to(dtype)
+        return tuple(whole[:, k * D:(k + 1) * D] for k in range(len(blocks)))
+    return tuple(b.to(dtype) for b in blocks)
+
+
+class GatedAggregate16(torch.autograd.Function):
+    """GatedAggregate with the operands gathered in float16 / bfloat16 (HCSPMM.forward_gated on 16-bit views: half the gathered
+    bytes, float32 sums): Z = f(r(P), r(Q), r(V)) with r the rounding to `dtype`, and the gradients of f at the rounded operands,
+    straight through the casts.  The forward casts the operands once (one pass when they are the layer's column blocks); the
+    backward casts G once and makes the single two-output call with own rows r(Q) and gathered (r(P), r(G)):
+      dP = G * T with the unrounded G,   dV = Y_gate,   dQ = widen(r(V)) * Y_dgate."""
+
+    @staticmethod
+    def forward(ctx, P, Q, V, dtype, *tail):
+        need_p = ctx.needs_input_grad[0]
+        P16, Q16, V16 = _cast_blocks(dtype, P, Q, V)
+        Z, T = HCSPMM.forward_gated(P16, Q16, V16, *tail[:N_GRAPH], ("gate", "dgate") if need_p else ("gate",))
+        ctx.save_for_backward(P16, Q16, V16, T, *tail[N_GRAPH:])
+        return Z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        P16, Q16, V16, T, *graph_b = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_p = d_q = d_v = None
+        if ctx.needs_input_grad[0]:
+            d_p = d_out * T
+        need_q, need_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if need_q or need_v:
+            names = (("gate",) if need_v else ()) + (("dgate",) if need_q else ())
+            d_v, y_dgate = HCSPMM.forward_gated(Q16, P16, d_out.to(Q16.dtype), *graph_b, names)
+            if need_q:
+                d_q = V16.to(y_dgate.dtype) * y_dgate
+        return (d_p, d_q, d_v, None) + (None,) * (2 * N_GRAPH)
+
+
+def gated_aggregate(P, Q, V, graph, directed=False, gather_dtype=None):
     """Gated sum over each row's neighbours, Z[i] = sum_j sigmoid(P[i] + Q[j]) * V[j] per feature column, with autograd for P
     [N, D], Q and V (float32 views with unit inner stride: column blocks of one projection pass as they are).  graph = the eight
     graph tensors, whose pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True:
-    the backward then runs on transposed_graph(graph).  Rows without entries give 0."""
+    the backward then runs on transposed_graph(graph).  Rows without entries give 0.
+    gather_dtype=torch.bfloat16 / torch.float16: the operands (and, in the backward, dZ) are rounded to that type once and gathered
+    in it -- half the gathered bytes; sums and results stay float32, and the gradients are those of the function of the rounded
+    operands (GatedAggregate16).  Even widths of at least 4."""
+    if gather_dtype not in GATHER_DTYPES:
+        raise ValueError("gather_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (gather_dtype,))
+    fn = GatedAggregate.apply if gather_dtype is None else (lambda *a: GatedAggregate16.apply(*a[:3], gather_dtype, *a[3:]))
     if directed:
-        return GatedAggregate.apply(P, Q, V, *graph, *transposed_graph(graph)[:N_GRAPH])
+        return fn(P, Q, V, *graph, *transposed_graph(graph)[:N_GRAPH])
     transpose_permutation_i32(graph[0], graph[1])  # an asymmetric pattern is refused before any launch (cached)
-    return GatedAggregate.apply(P, Q, V, *graph, *graph)
+    return fn(P, Q, V, *graph, *graph)
 
 
 class ResGatedGraphConv(torch.nn.Module):
@@ -1129,10 +1183,18 @@ class ResGatedGraphConv(torch.nn.Module):
     ONE product X [W_k | W_q | W_v | W_s] on _Update gives [N, 4H] -- Q and V sit side by side in a gathered row -- then
     gated_aggregate on its column blocks, without a copy.  root_weight=False drops the X W_s term (weights [input_dim, 3H]);
     bias=True adds a learnt [H] vector.  _Conv's call signature, so that Net builds it; edge_weight is refused.  The pattern
-    must be symmetric unless directed=True (the backward then runs on transposed_graph)."""
+    must be symmetric unless directed=True (the backward then runs on transposed_graph).  gather_dtype=torch.bfloat16 /
+    torch.float16: the [N, 3H] block of the product is rounded to that type once and gathered in it (gated_aggregate); the
+    X W_s term and the output stay float32.  H must then be even."""
 
-    def __init__(self, input_dim, output_dim, directed=False, root_weight=True, bias=False):
+    def __init__(self, input_dim, output_dim, directed=False, root_weight=True, bias=False, gather_dtype=None):
         super().__init__()
+        if gather_dtype not in GATHER_DTYPES:
+            raise ValueError("gather_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (gather_dtype,))
+        if gather_dtype is not None and (output_dim % 2 or output_dim < 4):
+            raise ValueError("gather_dtype needs an even output_dim of at least 4 (16-bit rows sit on a 4-byte grid), got %d"
+                             % output_dim)
+        self.gather_dtype = gather_dtype
         self.directed, self.root_weight, self.output_dim = bool(directed), bool(root_weight), int(output_dim)
         self.weights = torch.nn.Parameter(torch.empty(input_dim, (4 if root_weight else 3) * output_dim))
         self.bias = torch.nn.Parameter(torch.empty(output_dim)) if bias else None
@@ -1151,7 +1213,7 @@ class ResGatedGraphConv(torch.nn.Module):
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         H = self.output_dim
         proj = _Update.apply(X, self.weights)
-        out = gated_aggregate(proj[:, :H], proj[:, H:2 * H], proj[:, 2 * H:3 * H], graph, self.directed)
+        out = gated_aggregate(proj[:, :H], proj[:, H:2 * H], proj[:, 2 * H:3 * H], graph, self.directed, self.gather_dtype)
         if self.root_weight:
             out = out + proj[:, 3 * H:]
         return out if self.bias is None else out + self.bias

@@ -62,6 +62,9 @@ def parse_args(argv=None):
     p.add_argument("--aggr", type=str, default=None, choices=["max", "min", "mean"], help="aggregation of --model sage (default max)")
     p.add_argument("--gat-concat", action="store_true",
                    help="--model gat / gatv2: concatenate the heads of the first and hidden layers (hidden / heads features per head)")
+    # addition: the element type --model resgated gathers its projections in (GNN_model.ResGatedGraphConv gather_dtype)
+    p.add_argument("--gated-dtype", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
+                   help="--model resgated: gather the gate and value projections in this type (sums stay fp32)")
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
     p.add_argument("--directed", action="store_true",
                    help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
@@ -103,6 +106,8 @@ def parse_args(argv=None):
             p.error("--fp8 does not apply to --model resgated: the gated aggregation is fp32")
         if args.heads > 1:
             p.error("--heads does not apply to --model resgated: the gate is per feature column")
+    elif args.gated_dtype != "fp32":
+        p.error("--gated-dtype applies to --model resgated only")
     # addition: --model pna (GNN_model.PNAConv: mean / min / max / std of the neighbours from one gather pass, times degree scalers);
     # its aggregators are the layer's own, so --aggr is refused
     if args.model == "pna" and args.aggr is not None:
@@ -253,7 +258,10 @@ def main(argv=None):
             return GENConv(input_dim, output_dim, t=args.gen_t, learn_t=args.gen_learn_t, directed=directed)
     if args.model == "resgated":
         def conv_cls(input_dim, output_dim, fixed):
-            return ResGatedGraphConv(input_dim, output_dim, directed=directed)
+            # 16-bit rows sit on a 4-byte grid: a layer of odd width (the classes) keeps fp32 operands
+            gather = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[args.gated_dtype]
+            return ResGatedGraphConv(input_dim, output_dim, directed=directed,
+                                     gather_dtype=gather if output_dim % 2 == 0 and output_dim >= 4 else None)
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated

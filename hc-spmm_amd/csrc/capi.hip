@@ -729,6 +729,48 @@ extern "C" int hcspmm_forward_gated(const float* P, int64_t ldp, const float* Q,
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// The same aggregation on operands of one element type (fp32: the call above; fp16 / bf16: spmm_gate16.hip, rows on the dword grid,
+// fp32 outputs and partial slots, 64-column panels).
+extern "C" int hcspmm_forward_gated_typed(const void* P, int64_t ldp, const void* Q, int64_t ldq, const void* V, int64_t ldv,
+                                          int64_t src_rows, int dtype, float* Z_gate, float* Z_dgate, int64_t ldz,
+                                          const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                          const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                          const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                          void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_forward_gated(static_cast<const float*>(P), ldp, static_cast<const float*>(Q), ldq, static_cast<const float*>(V),
+                                ldv, src_rows, Z_gate, Z_dgate, ldz, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
+                                hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v);
+  if (N < 0 || E < 0 || src_rows < 0 || D <= 0 || ldp < D || ldq < D || ldv < D || ldz < D) return HCSPMM_EINVAL;
+  if (!Z_gate && !Z_dgate) return HCSPMM_EINVAL;
+  // rows on the dword grid: an even width of at least 4 columns, even strides, 4-byte aligned bases
+  if (D < 4 || ((D | ldp | ldq | ldv) & 1) != 0 || !aligned(P, 4) || !aligned(Q, 4) || !aligned(V, 4)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!P || !rowptr || (E > 0 && (!col || !Q || !V || src_rows == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::Gate16Args a{};
+  // workspace: two areas of hcspmm_workspace_bytes each, one per output; the operands' type decides the panel width
+  const int rc = bind_graph(a.p, GRAPH_IN, D, src_rows, workspace, workspace_bytes, 2, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.plan) {
+    a.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+    a.segment_len = ph->segment_len;
+  }
+  a.outputs = (Z_gate ? 1 : 0) | (Z_dgate ? 2 : 0);
+  set_operands(a.p, nullptr, Z_gate ? Z_gate : Z_dgate, ldp, ldz);
+  a.z2 = Z_gate ? Z_dgate : nullptr;
+  a.rowptr = rowptr;
+  a.P = static_cast<const unsigned short*>(P);
+  a.Q = static_cast<const unsigned short*>(Q);
+  a.V = static_cast<const unsigned short*>(V);
+  a.ldp = (size_t)ldp;
+  a.ldq = (size_t)ldq;
+  a.ldv = (size_t)ldv;
+  const hipError_t e = hcspmm::launch_gate16(a, dtype, D >= 32 ? 8 : 4, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 // Edge-feature messages (spmm_edge_messages.hip): the plan, checks and launch decisions of hcspmm_forward_weighted in fp32, F read on
 // every call.
 extern "C" int hcspmm_forward_edge_messages(const void* X, int64_t x_rows, int64_t ldx, const float* F, int64_t f_rows, int64_t ldf,

@@ -373,5 +373,20 @@ struct GatedArgs {
 // vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
 hipError_t launch_gated_f32(const GatedArgs& a, int vec, hipStream_t stream);
 
+// The same aggregation on fp16 / bf16 operands (spmm_gate16.hip; the 16-bit dtypes of the typed entry point): P, Q and V hold
+// 16-bit elements on the dword grid (even D, even strides, 4-byte aligned bases), widened exactly in registers; both outputs, the
+// partial slots and every other field are GatedArgs' -- fp32, p.ldz their row stride.
+struct Gate16Args {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;
+  int outputs;        // bit 0 = Z_gate, bit 1 = Z_dgate
+  const unsigned short *P, *Q, *V;
+  size_t ldp, ldq, ldv;  // in elements
+  float* z2;
+  size_t area;        // floats per workspace area
+};
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16; vec: 8 (D >= 32) or 4 (4 <= D < 32) elements per lane
+hipError_t launch_gate16(const Gate16Args& a, int dtype, int vec, hipStream_t stream);
 
 }  // namespace hcspmm

@@ -884,7 +884,10 @@ def forward_gated(P, Q, V, row_pointers, column_index, blockPartition, edgeToCol
     contiguous float32 [N, D].  outputs names some of "gate", "dgate"; an output not asked for is None, and one asked for has
     the same bits whether or not the other is.  P: float32 [N, D]; Q, V: float32 [rows, D] (rows >= the columns the graph refers
     to); all three 2-D views with unit inner stride and their own row strides (column blocks of one projection pass as they
-    are).  Rows without entries give 0.  No per-entry tensor is built."""
+    are).  Rows without entries give 0.  No per-entry tensor is built.
+    P, Q and V may instead ALL be float16 or all bfloat16 (hcspmm_forward_gated_typed): they are widened exactly, the gates and
+    sums are the float32 call's and Z stays float32, at half the gathered bytes.  That form serves even widths of at least 4 with
+    even row strides and 4-byte aligned views: pad anything else to an even width."""
     outputs = (outputs,) if isinstance(outputs, (str, bytes)) else tuple(outputs)
     for n in outputs:
         if n not in GATED_OUTPUTS:
@@ -896,11 +899,14 @@ def forward_gated(P, Q, V, row_pointers, column_index, blockPartition, edgeToCol
     for t in (P, Q, V):
         if not t.is_cuda:
             raise RuntimeError("P, Q and V must be CUDA tensors")
-        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
-            raise RuntimeError("P, Q and V must be 2-D float32 views with unit inner stride (gated aggregation is float32 only)")
+        if t.dtype != Q.dtype or t.dtype not in _DTYPES or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+            raise RuntimeError("P, Q and V must be 2-D views with unit inner stride, all float32, all float16 or all bfloat16")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), Q.size(1)
     if D == 0:
         raise RuntimeError("P, Q and V must have at least one column")
+    if Q.dtype != torch.float32 and (D < 4 or any(t.size(1) % 2 or t.stride(0) % 2 or t.data_ptr() % 4 for t in (P, Q, V))):
+        raise RuntimeError("16-bit gated aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: "
+                           "pad P, Q and V to an even width")
     if P.size(1) != D or V.size(1) != D:
         raise RuntimeError("P, Q and V must have the same width, got %d, %d and %d" % (P.size(1), D, V.size(1)))
     if V.size(0) != Q.size(0):
@@ -918,8 +924,9 @@ def forward_gated(P, Q, V, row_pointers, column_index, blockPartition, edgeToCol
         return tuple(Z)
     null = ctypes.c_void_p(0)
     with c:
-        check(lib().hcspmm_forward_gated(_ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(V), V.stride(0), Q.size(0),
-                                         *(_ptr(z) if z is not None else null for z in Z), D, *c.graph, *c.ws))
+        check(lib().hcspmm_forward_gated_typed(_ptr(P), P.stride(0), _ptr(Q), Q.stride(0), _ptr(V), V.stride(0), Q.size(0),
+                                               _DTYPES[Q.dtype], *(_ptr(z) if z is not None else null for z in Z), D, *c.graph,
+                                               *c.ws))
     return tuple(Z)
 
 

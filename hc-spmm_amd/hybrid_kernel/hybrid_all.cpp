@@ -8,6 +8,7 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -547,7 +548,8 @@ spmm_forward_softmax(torch::Tensor input, pybind11::object beta, torch::Tensor n
 
 // Gated neighbour aggregation (hcspmm_forward_gated): P [num_nodes, D] read by row, Q and V [rows, D] gathered through the column
 // ids; float32 views with unit inner stride and independent row strides -> (Z_gate, Z_dgate), None for what `outputs` (some of
-// "gate", "dgate") leaves out
+// "gate", "dgate") leaves out.  All three float16 or all three bfloat16 (hcspmm_forward_gated_typed): widened exactly, float32
+// outputs; even widths of at least 4, even row strides, 4-byte aligned views
 std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> spmm_forward_gated(
     torch::Tensor P, torch::Tensor Q, torch::Tensor V, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
     torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
@@ -567,17 +569,25 @@ std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> spmm_forw
   if (!want[0] && !want[1]) throw pybind11::value_error("outputs must name at least one of 'gate', 'dgate'");
   for (const torch::Tensor* t : {&P, &Q, &V}) {
     TORCH_CHECK(t->is_cuda(), "P, Q and V must be CUDA tensors");
-    TORCH_CHECK(t->scalar_type() == torch::kFloat && t->dim() == 2 && t->stride(1) == 1 && t->stride(0) >= t->size(1),
-                "P, Q and V must be 2-D float32 views with unit inner stride (gated aggregation is float32 only)");
+    TORCH_CHECK(feature_dtype(*t) >= 0 && t->scalar_type() == Q.scalar_type() && t->dim() == 2 && t->stride(1) == 1 &&
+                    t->stride(0) >= t->size(1),
+                "P, Q and V must be 2-D views with unit inner stride, all float32, all float16 or all bfloat16");
   }
   TORCH_CHECK(Q.size(1) > 0, "P, Q and V must have at least one column");
+  const int dtype = feature_dtype(Q);
+  if (dtype != HCSPMM_DTYPE_F32) {
+    for (const torch::Tensor* t : {&P, &Q, &V})
+      TORCH_CHECK(Q.size(1) >= 4 && t->size(1) % 2 == 0 && t->stride(0) % 2 == 0 && reinterpret_cast<uintptr_t>(t->data_ptr()) % 4 == 0,
+                  "16-bit gated aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: pad P, Q and V "
+                  "to an even width");
+  }
   TORCH_CHECK(P.size(1) == Q.size(1) && V.size(1) == Q.size(1), "P, Q and V must have the same width, got ", P.size(1), ", ",
               Q.size(1), " and ", V.size(1));
   TORCH_CHECK(V.size(0) == Q.size(0), "Q and V must have the same number of rows, got ", Q.size(0), " and ", V.size(0));
   TORCH_CHECK(P.device() == Q.device() && V.device() == Q.device(), "P, Q and V must be on one device");
-  CallOptions o;
+  CallOptions o(CallOptions::kTyped);
   o.rect = o.strided = true;
-  o.workspace_bytes = hcspmm_gated_workspace_bytes;  // one area of partial slots per output
+  o.workspace_bytes = hcspmm_gated_workspace_bytes;  // one area of partial slots per output, float32 whatever the operands are
   PlannedCall c(&Q, Q, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
   TORCH_CHECK(P.size(0) == c.N, "P has ", P.size(0), " rows but the graph has ", c.N, " nodes");
   TORCH_CHECK(c.E == 0 || Q.size(0) > 0, "Q and V have no rows but the graph has ", c.E, " entries");
@@ -585,15 +595,15 @@ std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> spmm_forw
   float* zp[2] = {nullptr, nullptr};
   for (int k = 0; k < 2; ++k) {
     if (!want[k]) continue;
-    auto t = torch::empty({c.N, (int64_t)c.D}, Q.options());
+    auto t = torch::empty({c.N, (int64_t)c.D}, Q.options().dtype(torch::kFloat));
     zp[k] = c.N > 0 ? t.data_ptr<float>() : nullptr;
     out[k] = t;
   }
   if (c.N > 0) {
     const bool any = Q.size(0) > 0;
-    const int rc = invoke(hcspmm_forward_gated,
-                          std::make_tuple(P.data_ptr<float>(), P.stride(0), any ? Q.data_ptr<float>() : nullptr, Q.stride(0),
-                                          any ? V.data_ptr<float>() : nullptr, V.stride(0), Q.size(0), zp[0], zp[1], c.D),
+    const int rc = invoke(hcspmm_forward_gated_typed,
+                          std::make_tuple(P.data_ptr(), P.stride(0), any ? Q.data_ptr() : nullptr, Q.stride(0),
+                                          any ? V.data_ptr() : nullptr, V.stride(0), Q.size(0), dtype, zp[0], zp[1], c.D),
                           c.graph(), c.ws());
     check_rc(rc, "forward_gated");
   }

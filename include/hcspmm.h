@@ -36,7 +36,7 @@ extern "C" {
  * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15); hcspmm_softmax_workspace_bytes, hcspmm_forward_softmax,
  * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
- * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22).
+ * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -587,6 +587,26 @@ int hcspmm_forward_gated(const float* P_d, int64_t ldp, const float* Q_d, int64_
                          const int32_t* edgeToRow_d, const int32_t* hybrid_type_d, const int32_t* plan_d,
                          const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
                          void* workspace_d, size_t workspace_bytes, void* stream);
+/* hcspmm_forward_gated_typed: the same aggregation with P_d, Q_d and V_d ALL of element type `dtype`; the outputs stay fp32.
+ *   HCSPMM_DTYPE_F32           forwards to hcspmm_forward_gated
+ *   HCSPMM_DTYPE_F16 / _BF16   p, q, v = the elements widened to fp32 (exact), then z = fl32(p + q) and the gate arithmetic,
+ *                              the summation orders and every guarantee above, on the widened values: exact saturation from
+ *                              |z| = 104 on, NaN propagation, +0.0 rows, nullable outputs whose bits do not depend on the other
+ *                              output, no atomics.  Half the gathered bytes of both streams (kernels of their own,
+ *                              spmm_gate16.hip); the column panels of a planned call are 64 columns wide.
+ * ldp / ldq / ldv count elements.  The 16-bit types serve every EVEN embedding_dim >= 4 with even ldp / ldq / ldv and 4-byte
+ * aligned P_d / Q_d / V_d (rows on the dword grid: three column blocks of one [N, 3H] 16-bit projection pass as they are); an odd
+ * width or stride, embedding_dim == 2 or a misaligned base is HCSPMM_EINVAL before any device call -- pad to an even width.
+ * A dtype outside F32 ... BF16 is HCSPMM_EINVAL; every other argument, plan and workspace error is hcspmm_forward_gated's, raised
+ * before HIP is touched.  workspace_d >= hcspmm_gated_workspace_bytes() as above (partial slots are fp32 whatever the operands
+ * are).  num_nodes == 0 returns HCSPMM_OK without a launch.  Asynchronous on `stream`, allocates nothing, capturable.
+ * The gradient recipe above holds with the 16-bit operands in the places of P, Q, V and a 16-bit copy of G gathered. */
+int hcspmm_forward_gated_typed(const void* P_d, int64_t ldp, const void* Q_d, int64_t ldq, const void* V_d, int64_t ldv,
+                               int64_t src_rows, int dtype, float* Z_gate_d, float* Z_dgate_d, int64_t ldz,
+                               const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                               const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                               const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                               int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Edge-feature messages (GINE, SchNet / CFConv continuous filters, edge-gated convolutions, "sum the incident edge vectors"):
