@@ -208,6 +208,37 @@ class _Update(torch.autograd.Function):
         return d_x, d_w
 
 
+class _Update16(torch.autograd.Function):
+    """X16 W for a 16-bit activation X16 (fp16 / bf16) and the fp32 parameter W, in X16's dtype: W is rounded once per call
+    (D x H elements), the products run on the library's 16-bit MFMA kernels with fp32 accumulation (HCSPMM.update /
+    HCSPMM.weight_grad on 16-bit operands) -- d_x = d_out W16^T through the strided view, d_w = X16^T d_out in fp32.  Below 4096
+    rows, or for a shape the kernels do not serve, torch.mm on the same operands (as _mm / _weight_grad)."""
+
+    @staticmethod
+    def _mm16(X, W16):
+        out = HCSPMM.update(X, W16) if X.size(0) >= 4096 else None
+        return out if out is not None else torch.mm(X, W16)
+
+    @staticmethod
+    def forward(ctx, X, W):
+        X = X.contiguous()
+        W16 = W.detach().to(X.dtype)
+        ctx.save_for_backward(X, W16)
+        return _Update16._mm16(X, W16)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, W16 = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        d_x = _Update16._mm16(d_out, W16.transpose(0, 1)) if ctx.needs_input_grad[0] else None
+        d_w = None
+        if ctx.needs_input_grad[1]:
+            d_w = HCSPMM.weight_grad(X, d_out) if X.size(0) >= 4096 else None
+            if d_w is None:
+                d_w = torch.mm(X.transpose(0, 1).float(), d_out.float())
+        return d_x, d_w
+
+
 _TRANSPOSED = {}  # (row_pointers, column_index) pointers and sizes -> (weak refs, perm): the host pass runs once per graph
 
 
@@ -323,6 +354,37 @@ def weighted_aggregate(X, edge_weight, graph, directed=False):
         return EdgeWeightedAggregateDirected.apply(X, edge_weight, *graph, *transposed_graph(graph))
     values_t = edge_weight.detach()[transpose_permutation(graph[0], graph[1])].contiguous()
     return HCSPMMFunction_Weighted.apply(X, edge_weight, values_t, *graph)
+
+
+class WeightedAggregateDirected16(torch.autograd.Function):
+    """A_w X on any square graph for fp16 / bf16 X: EdgeWeightedAggregateDirected's backward goes through the indexed kernels, which
+    take fp32 features only, so here A^T's values are gathered once (values_t = edge_weight[entry_index_t], E floats) and
+    dX = A_w^T dY is forward_weighted's 16-bit kernel on A^T's own graph tensors and plan.  tail = the eight graph tensors of A
+    followed by A^T's eight."""
+
+    @staticmethod
+    def forward(ctx, X, values, values_t, *tail):
+        ctx.save_for_backward(values_t, *tail[N_GRAPH:])
+        return HCSPMM.forward_weighted(X.contiguous(), values, *tail[:N_GRAPH])[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        values_t, *graph_t = ctx.saved_tensors
+        d_x = HCSPMM.forward_weighted(d_out.contiguous(), values_t, *graph_t)[0] if ctx.needs_input_grad[0] else None
+        return (d_x, None, None) + (None,) * (2 * N_GRAPH)
+
+
+def weighted_aggregate16(X, edge_weight, graph, directed=False):
+    """weighted_aggregate for fp16 / bf16 X (Z in X's dtype, fp32 sums): the symmetric path is weighted_aggregate's own function,
+    which is dtype-agnostic; directed=True takes WeightedAggregateDirected16."""
+    if not directed:
+        return weighted_aggregate(X, edge_weight, graph)
+    if edge_weight.requires_grad:
+        raise NotImplementedError("HCSPMM: the gradient with respect to the edge values (an SDDMM) is not implemented for 16-bit "
+                                  "features; pass values that do not require grad")
+    graph_t = transposed_graph(graph)
+    values_t = edge_weight.detach()[graph_t[N_GRAPH].long()].contiguous()
+    return WeightedAggregateDirected16.apply(X, edge_weight.contiguous(), values_t, *graph, *graph_t[:N_GRAPH])
 
 
 class HCSPMMFunction_WeightedFP8(HCSPMMFunction_Weighted):
@@ -670,13 +732,17 @@ class _Conv(torch.nn.Module):
     first_fn = hidden_fn = last_fn = None
     last_takes_output = False
 
-    def __init__(self, input_dim, output_dim, fixed=0, directed=False):
+    def __init__(self, input_dim, output_dim, fixed=0, directed=False, activation_dtype=None):
         super().__init__()
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
         self.fixed = fixed
         self.directed = bool(directed)  # the edge_weight path only: the binary layer functions aggregate with A, as the reference
         # "fp8": the edge_weight path aggregates 8-bit codes of its input (aggregate_fp8: quantised forward, exact fp32 backward)
         self.feature_storage = "fp32"
+        # torch.bfloat16 / torch.float16: the edge_weight path runs on 16-bit activations end to end -- X is taken in that dtype (an
+        # fp32 X is rounded once on entry), aggregated by forward_weighted's 16-bit kernels, multiplied by _Update16, and the
+        # layer returns that dtype; the parameter and its gradient stay fp32
+        self.activation_dtype = activation_dtype
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights.size(1))
@@ -691,6 +757,20 @@ class _Conv(torch.nn.Module):
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         if self.feature_storage not in ("fp32", "fp8"):
             raise ValueError("feature_storage must be 'fp32' or 'fp8', got %r" % (self.feature_storage,))
+        if self.activation_dtype is not None:
+            if self.activation_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (self.activation_dtype,))
+            if edge_weight is None:
+                raise ValueError("activation_dtype needs an edge_weight: the fused binary layer functions stay fp32")
+            if self.feature_storage == "fp8":
+                raise ValueError("activation_dtype and feature_storage = 'fp8' exclude each other")
+            if self.weights.size(0) % 2 or self.weights.size(1) % 2:
+                raise ValueError("activation_dtype needs even widths (16-bit rows on the dword grid), got %d -> %d"
+                                 % tuple(self.weights.shape))
+            X = X.to(self.activation_dtype)
+            if self.aggregate_first:
+                return _Update16.apply(weighted_aggregate16(X, edge_weight, graph, self.directed), self.weights)
+            return weighted_aggregate16(_Update16.apply(X, self.weights), edge_weight, graph, self.directed)
         if self.feature_storage == "fp8":
             if edge_weight is None:
                 raise ValueError("feature_storage = 'fp8' needs an edge_weight: the fused binary layer functions stay fp32")

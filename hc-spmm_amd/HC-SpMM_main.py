@@ -65,6 +65,10 @@ def parse_args(argv=None):
     # addition: the element type --model resgated gathers its projections in (GNN_model.ResGatedGraphConv gather_dtype)
     p.add_argument("--gated-dtype", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
                    help="--model resgated: gather the gate and value projections in this type (sums stay fp32)")
+    # addition: 16-bit activations end to end (GNN_model._Conv activation_dtype: 16-bit aggregation and the 16-bit update / weight
+    # gradient kernels; parameters, their gradients and the loss stay fp32)
+    p.add_argument("--activation-dtype", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
+                   help="--model gcn / gin with --norm sym|mean: run the layers on activations of this type")
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
     p.add_argument("--directed", action="store_true",
                    help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
@@ -185,7 +189,7 @@ class Net(nn.Module):
         for conv in self.hidden_layers:
             x = self.relu(conv(x, *self.graph, self.output, **self.ew))
         x = self.conv2(x, *self.graph, self.output, **self.ew)
-        return F.log_softmax(x, dim=1)
+        return F.log_softmax(x.float(), dim=1)  # (16-bit logits of an activation_dtype model are widened before the loss)
 
 
 def set_feature_storage(model, storage):
@@ -285,6 +289,12 @@ def main(argv=None):
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight, edge_attr).to(device)
     if args.fp8:
         set_feature_storage(model, "fp8")
+    if args.activation_dtype != "fp32":
+        if args.model not in ("gcn", "gin") or edge_weight is None:
+            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean")
+        for m in model.modules():
+            if isinstance(m, (GCNConv, GINConv)):
+                m.activation_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.activation_dtype]
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 
     epoch = [0]

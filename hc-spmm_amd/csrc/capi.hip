@@ -1178,4 +1178,61 @@ extern "C" int hcspmm_weight_grad(const float* A, int64_t lda, const float* B, i
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// The update GEMM and its weight gradient on operands of a stated element type (fp32: the calls above; fp16 / bf16:
+// update_kernels_h16.hip).  Everything the 16-bit kernels do not serve is refused before any device call.
+extern "C" int hcspmm_dense_update_typed(const void* in, int64_t ld_in, int in_dtype, const void* weights, int w_dtype, int64_t ldr,
+                                         int64_t ldc, void* out, int64_t ld_out, int out_dtype, int64_t N, int D, int H,
+                                         void* stream_v) {
+  if (in_dtype == HCSPMM_DTYPE_F32) {
+    if (w_dtype != HCSPMM_DTYPE_F32 || out_dtype != HCSPMM_DTYPE_F32 || ld_in != D || ld_out != H) return HCSPMM_EINVAL;
+    return hcspmm_dense_update(static_cast<const float*>(in), static_cast<const float*>(weights), ldr, ldc, static_cast<float*>(out),
+                               N, D, H, stream_v);
+  }
+  if (in_dtype != HCSPMM_DTYPE_F16 && in_dtype != HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if ((w_dtype != in_dtype && w_dtype != HCSPMM_DTYPE_F32) || (out_dtype != in_dtype && out_dtype != HCSPMM_DTYPE_F32))
+    return HCSPMM_EINVAL;
+  if (N < 0 || D <= 0 || H <= 0 || ld_in < D || ld_out < H) return HCSPMM_EINVAL;
+  // rows of `in` on the dword grid; the staged weights within the LDS budget
+  if (((D | ld_in) & 1) != 0 || !aligned(in, 4) || !hcspmm::update16_supported(D, H)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!in || !weights || !out) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16) return HCSPMM_ERANGE;
+  hcspmm::Update16Args a{};
+  a.in = in;
+  a.ld_in = (long long)ld_in;
+  a.W = weights;
+  a.w_f32 = w_dtype == HCSPMM_DTYPE_F32;
+  a.ldr = (long long)ldr;
+  a.ldc = (long long)ldc;
+  a.out = out;
+  a.ld_out = (long long)ld_out;
+  a.out16 = out_dtype != HCSPMM_DTYPE_F32;
+  a.N = (int)N;
+  a.D = D;
+  a.H = H;
+  const hipError_t e = hcspmm::launch_update16(a, in_dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" size_t hcspmm_weight_grad_typed_workspace(int64_t N, int D, int H) {
+  if (N <= 0 || !hcspmm::weight_grad16_supported(D, H)) return 0;
+  return (size_t)hcspmm::weight_grad_groups(N) * (size_t)D * (size_t)H * sizeof(float);
+}
+
+extern "C" int hcspmm_weight_grad_typed(const void* A, int64_t lda, const void* B, int64_t ldb, int dtype, float* out, int64_t N,
+                                        int D, int H, void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_weight_grad(static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb, out, N, D, H, workspace,
+                              workspace_bytes, stream_v);
+  if (dtype != HCSPMM_DTYPE_F16 && dtype != HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (N <= 0 || D <= 0 || H <= 0 || lda < D || ldb < H || !A || !B || !out) return HCSPMM_EINVAL;
+  if (!hcspmm::weight_grad16_supported(D, H)) return HCSPMM_EINVAL;
+  if (((D | H | lda | ldb) & 1) != 0 || !aligned(A, 4) || !aligned(B, 4)) return HCSPMM_EINVAL;  // rows on the dword grid
+  if (N > INT32_MAX - 128) return HCSPMM_ERANGE;  // a workgroup's block (at most N rounded up to 128 rows, with one group) is an int
+  if (!workspace || workspace_bytes < hcspmm_weight_grad_typed_workspace(N, D, H)) return HCSPMM_EWORKSPACE;
+  const hipError_t e = hcspmm::launch_weight_grad16(A, lda, B, ldb, dtype, out, reinterpret_cast<float*>(workspace), N, D, H,
+                                                    reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 #undef GRAPH_IN

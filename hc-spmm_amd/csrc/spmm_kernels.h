@@ -158,6 +158,31 @@ int weight_grad_groups(long long N);
 hipError_t launch_weight_grad(const float* A, long long lda, const float* B, long long ldb, float* out, float* partial,
                               long long N, int D, int H, hipStream_t stream);
 
+// the final sum of launch_weight_grad on its own: out[e] = sum over the G partials of DH floats each, in partial order
+hipError_t launch_weight_grad_reduce(const float* partial, float* out, int G, int DH, hipStream_t stream);
+
+// The dense update and the weight gradient on fp16 / bf16 operands (update_kernels_h16.hip, v_mfma_f32_16x16x32_{f16,bf16}).
+struct Update16Args {
+  const void* in;      // [N, D] 16-bit, rows ld_in elements apart (even, base on the dword grid)
+  long long ld_in;
+  const void* W;       // [D, H], element strides ldr / ldc; 16-bit of in's type, or fp32 (w_f32) rounded as it is staged
+  int w_f32;
+  long long ldr, ldc;
+  void* out;           // [N, H] fp32, or in's type (out16), rows ld_out elements apart
+  long long ld_out;
+  int out16;
+  int N, D, H;
+};
+size_t update16_lds_bytes(int D, int H);
+bool update16_supported(int D, int H);  // D even, 1 <= H <= 128, the staged weights within the LDS budget
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_update16(const Update16Args& a, int dtype, hipStream_t stream);
+// dW = A^T B on 16-bit A [N, D] and B [N, H] (even row strides, bases on the dword grid); `partial` as launch_weight_grad, shapes
+// weight_grad16_supported: launch_weight_grad's and the rest of ceil(D/16) <= 8, ceil(H/16) <= 4
+bool weight_grad16_supported(int D, int H);
+hipError_t launch_weight_grad16(const void* A, long long lda, const void* B, long long ldb, int dtype, float* out, float* partial,
+                                long long N, int D, int H, hipStream_t stream);
+
 // out[N x H] = in[N x D] * W (D x H, element strides ldr / ldc), fp32 MFMA.  tile_list (device, n_tiles ids of
 // 16-row tiles) restricts the product to those tiles (the windows a fused launch has not already multiplied);
 // nullptr = every tile.

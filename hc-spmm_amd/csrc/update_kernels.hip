@@ -427,6 +427,11 @@ static hipError_t launch_wg(const float* A, long long lda, const float* B, long 
   return hipGetLastError();
 }
 
+hipError_t launch_weight_grad_reduce(const float* partial, float* out, int G, int DH, hipStream_t stream) {
+  hipLaunchKernelGGL(weight_grad_reduce_kernel, dim3((DH + 63) / 64), dim3(kUpdWaves * 64), 0, stream, partial, out, G, DH);
+  return hipGetLastError();
+}
+
 hipError_t launch_weight_grad(const float* A, long long lda, const float* B, long long ldb, float* out, float* partial,
                               long long N, int D, int H, hipStream_t stream) {
   const int dt = (D + 15) / 16, ht = (H + 15) / 16;

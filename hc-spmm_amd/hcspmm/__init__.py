@@ -1462,10 +1462,49 @@ def gatv2_scores_backward_directed(grad_logits, H_dst, H_src, att, row_pointers,
                                   entry_index_t, negative_slope)
 
 
-def update(X, W):
+_DTYPE16 = {torch.float16: 1, torch.bfloat16: 2}  # HCSPMM_DTYPE_F16 / _BF16
+
+
+def _rows16(t):
+    """a 16-bit matrix whose rows lie on the dword grid: unit inner stride, even width and row stride, 4-byte aligned base"""
+    return (t.dim() == 2 and t.stride(1) == 1 and t.size(1) % 2 == 0 and t.stride(0) % 2 == 0 and t.stride(0) >= t.size(1)
+            and t.data_ptr() % 4 == 0)
+
+
+def _update16(X, W, out_dtype, out):
+    """update() on fp16 / bf16 rows (hcspmm_dense_update_typed): None for whatever that entry point refuses"""
+    out_dtype = out_dtype or (out.dtype if out is not None else X.dtype)
+    if X.dim() != 2 or W.dim() != 2:
+        return None
+    N, D, H = X.size(0), X.size(1), W.size(1)
+    if not (W.is_cuda and W.dtype in (X.dtype, torch.float32) and out_dtype in (X.dtype, torch.float32)
+            and _rows16(X) and W.size(0) == D and N > 0 and 1 <= H <= 128 and 32 * -(-H // 16) * (32 * -(-D // 32) + 8) <= 160 * 1024):
+        return None
+    if out is None:
+        out = torch.empty((N, H), dtype=out_dtype, device=X.device)
+    elif not (out.is_cuda and out.dim() == 2 and out.dtype == out_dtype and tuple(out.shape) == (N, H) and out.stride(1) == 1
+              and out.stride(0) >= H):
+        return None
+    stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    with _on_device(X.device):
+        check(lib().hcspmm_dense_update_typed(_ptr(X), X.stride(0), _DTYPE16[X.dtype], _ptr(W), _DTYPE16.get(W.dtype, 0), W.stride(0),
+                                              W.stride(1), _ptr(out), out.stride(0), _DTYPE16.get(out_dtype, 0), N, D, H, stream))
+    return out
+
+
+def update(X, W, out_dtype=None, out=None):
     """X @ W for X [N, D] (fp32, contiguous) and W [D, H] (any strides: a transposed view needs no copy) through the
     library's streaming MFMA update kernel (hcspmm_dense_update) -- the layers' torch.mm(X, weights), which for N in the
-    millions and D, H of a few dozen is a stream over X.  Returns None when the operands are not of that kind (caller: torch.mm)."""
+    millions and D, H of a few dozen is a stream over X.  Returns None when the operands are not of that kind (caller: torch.mm).
+
+    X fp16 / bf16 (unit inner stride, even width and row stride, so a column block passes as a view) with W of X's dtype or
+    fp32 -- rounded to X's dtype as it is staged -- runs on the 16-bit MFMA kernel (hcspmm_dense_update_typed) with fp32
+    accumulation and returns out_dtype: X's dtype (the default, rounded once) or torch.float32.  `out` (16-bit X only) is an
+    [N, H] matrix of that dtype with unit inner stride to write into, e.g. a column block of a wider matrix."""
+    if X.is_cuda and X.dtype in _DTYPE16:
+        return _update16(X, W, out_dtype, out)
+    if out_dtype not in (None, torch.float32) or out is not None:
+        return None
     if not (X.is_cuda and W.is_cuda and X.dtype == W.dtype == torch.float32 and X.dim() == W.dim() == 2
             and X.size(1) == W.size(0) and X.is_contiguous() and X.size(0) > 0 and X.size(1) > 0 and W.size(1) > 0):
         return None
@@ -1479,8 +1518,24 @@ def update(X, W):
 def weight_grad(A, B):
     """dW = A^T B for A [N, D], B [N, H] (fp32, unit inner stride): the weight gradient of the update GEMM in the
     layers' backward passes (reference: torch.mm(X.t(), d_out), GNN_model.py:79,101,...) through the split-K MFMA
-    kernel of hcspmm_weight_grad.  Returns None when the shape is outside the kernel's range (caller: library GEMM)."""
+    kernel of hcspmm_weight_grad.  Returns None when the shape is outside the kernel's range (caller: library GEMM).
+    A and B both fp16 or both bf16 (rows on the dword grid) run on the 16-bit MFMA kernel of hcspmm_weight_grad_typed; dW is
+    fp32 either way."""
     L = lib()
+    if A.is_cuda and B.is_cuda and A.dtype == B.dtype and A.dtype in _DTYPE16:
+        if not (_rows16(A) and _rows16(B) and A.size(0) == B.size(0)):
+            return None
+        N, D, H = A.size(0), A.size(1), B.size(1)
+        ws_bytes = int(L.hcspmm_weight_grad_typed_workspace(N, D, H))
+        if ws_bytes == 0:
+            return None
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=A.device)
+        out = torch.empty((D, H), dtype=torch.float32, device=A.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        with _on_device(A.device):
+            check(L.hcspmm_weight_grad_typed(_ptr(A), A.stride(0), _ptr(B), B.stride(0), _DTYPE16[A.dtype], _ptr(out), N, D, H,
+                                             _ptr(ws), ws_bytes, stream))
+        return out
     if not (A.is_cuda and B.is_cuda and A.dtype == B.dtype == torch.float32 and A.dim() == B.dim() == 2
             and A.size(0) == B.size(0) and A.stride(1) == 1 and B.stride(1) == 1
             and A.stride(0) >= A.size(1) and B.stride(0) >= B.size(1)):  # (rows that overlap, e.g. an expanded row: not taken)

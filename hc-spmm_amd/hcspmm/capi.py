@@ -153,6 +153,9 @@ SYMBOLS = {
     "hcspmm_dense_update": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _int, _int, _vp]),
     "hcspmm_weight_grad_workspace": (_sz, [_i64, _int, _int]),
     "hcspmm_weight_grad": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _sz, _vp]),
+    "hcspmm_dense_update_typed": (_int, [_vp, _i64, _int, _vp, _int, _i64, _i64, _vp, _i64, _int, _i64, _int, _int, _vp]),
+    "hcspmm_weight_grad_typed_workspace": (_sz, [_i64, _int, _int]),
+    "hcspmm_weight_grad_typed": (_int, [_vp, _i64, _vp, _i64, _int, _vp, _i64, _int, _int, _vp, _sz, _vp]),
     "hcspmm_loi_reorder": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64)]),
     "hcspmm_loi_reorder_variant": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, ctypes.POINTER(_i64)]),
     "hcspmm_loi_reorder_fast": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64)]),

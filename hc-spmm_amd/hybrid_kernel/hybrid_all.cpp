@@ -153,6 +153,12 @@ int feature_dtype(const torch::Tensor& t) {
   }
 }
 
+// a 16-bit matrix whose rows lie on the dword grid: unit inner stride, even width and row stride, 4-byte aligned base
+bool rows16(const torch::Tensor& t) {
+  return t.dim() == 2 && t.stride(1) == 1 && t.size(1) % 2 == 0 && t.stride(0) % 2 == 0 && t.stride(0) >= t.size(1) &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 4 == 0;
+}
+
 // fn(parts...): a C-ABI call put together from runs of arguments -- the entry point's own operands and PlannedCall's
 // graph() / plan() / ws().  Every argument is still converted to the prototype in hcspmm.h at compile time.
 template <class Fn, class... Parts>
@@ -1590,9 +1596,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              "apply_permutation");
     return std::vector<torch::Tensor>{rp2, col2};
   }, "relabel a CSR graph with a LOI permutation -> [row_pointers, column_index]");
-  m.def("update", [](torch::Tensor X, torch::Tensor W) -> torch::Tensor {
+  m.def("update", [](torch::Tensor X, torch::Tensor W, c10::optional<torch::ScalarType> out_dtype,
+                     c10::optional<torch::Tensor> out_arg) -> torch::Tensor {
     // X * W through the library's streaming update kernel (hcspmm.h hcspmm_dense_update); an undefined tensor (None) when
     // the operands are not fp32 device matrices of that kind, so that the caller can use torch.mm
+    const int xdt = feature_dtype(X);
+    if (X.is_cuda() && (xdt == HCSPMM_DTYPE_F16 || xdt == HCSPMM_DTYPE_BF16)) {
+      // 16-bit rows on the dword grid (hcspmm_dense_update_typed): W of X's type or fp32, the result in X's type or fp32
+      const auto odt = out_dtype ? *out_dtype : (out_arg ? out_arg->scalar_type() : X.scalar_type());
+      if (X.dim() != 2 || W.dim() != 2) return torch::Tensor();
+      const int64_t N = X.size(0), D = X.size(1), H = W.size(1);
+      if (!(W.is_cuda() && (W.scalar_type() == X.scalar_type() || W.scalar_type() == torch::kFloat) &&
+            (odt == X.scalar_type() || odt == torch::kFloat) && rows16(X) && W.size(0) == D && N > 0 && H >= 1 && H <= 128 &&
+            32 * ((H + 15) / 16) * (32 * ((D + 31) / 32) + 8) <= 160 * 1024))
+        return torch::Tensor();
+      torch::Tensor out;
+      if (!out_arg) {
+        out = torch::empty({N, H}, X.options().dtype(odt));
+      } else {
+        out = *out_arg;
+        if (!(out.is_cuda() && out.dim() == 2 && out.scalar_type() == odt && out.size(0) == N && out.size(1) == H &&
+              out.stride(1) == 1 && out.stride(0) >= H))
+          return torch::Tensor();
+      }
+      const c10::DeviceGuard guard(X.device());
+      check_rc(hcspmm_dense_update_typed(X.data_ptr(), X.stride(0), xdt, W.data_ptr(), feature_dtype(W), W.stride(0), W.stride(1),
+                                         out.data_ptr(), out.stride(0), feature_dtype(out), N, (int)D, (int)H, current_stream(X)),
+               "update");
+      return out;
+    }
+    if ((out_dtype && *out_dtype != torch::kFloat) || out_arg) return torch::Tensor();
     if (!(X.is_cuda() && W.is_cuda() && X.scalar_type() == torch::kFloat && W.scalar_type() == torch::kFloat && X.dim() == 2 &&
           W.dim() == 2 && X.size(1) == W.size(0) && X.is_contiguous() && X.size(0) > 0 && X.size(1) > 0 && W.size(1) > 0))
       return torch::Tensor();
@@ -1602,10 +1635,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                  (int)X.size(1), (int)W.size(1), current_stream(X)),
              "update");
     return out;
-  }, "X * W (the layers' update GEMM; W may be a transposed view); None if the operands are not contiguous fp32 device matrices");
+  }, "X * W (the layers' update GEMM; W may be a transposed view); None if the operands are not contiguous fp32 device matrices, "
+     "or fp16 / bf16 rows on the dword grid (W of that type or fp32; out_dtype X's or float32; out: a matrix to write into)",
+     pybind11::arg("X"), pybind11::arg("W"), pybind11::arg("out_dtype") = pybind11::none(), pybind11::arg("out") = pybind11::none());
   m.def("weight_grad", [](torch::Tensor A, torch::Tensor B) -> torch::Tensor {
     // dW = A^T B with K = number of nodes (hcspmm.h hcspmm_weight_grad); an undefined tensor (None) when the
     // shape is outside the kernel's range, so that the caller can use a library GEMM
+    const int adt = feature_dtype(A);
+    if (A.is_cuda() && B.is_cuda() && A.scalar_type() == B.scalar_type() && (adt == HCSPMM_DTYPE_F16 || adt == HCSPMM_DTYPE_BF16)) {
+      // both 16-bit (hcspmm_weight_grad_typed): fp32 dW
+      if (!(rows16(A) && rows16(B) && A.size(0) == B.size(0))) return torch::Tensor();
+      const int64_t N = A.size(0);
+      const int D = (int)A.size(1), H = (int)B.size(1);
+      const size_t need = hcspmm_weight_grad_typed_workspace(N, D, H);
+      if (need == 0) return torch::Tensor();
+      auto ws = torch::empty({(int64_t)(need / 4)}, A.options().dtype(torch::kFloat));
+      auto out = torch::empty({(int64_t)D, (int64_t)H}, A.options().dtype(torch::kFloat));
+      const c10::DeviceGuard guard(A.device());
+      check_rc(hcspmm_weight_grad_typed(A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), adt, out.data_ptr<float>(), N, D, H,
+                                        ws.data_ptr(), need, current_stream(A)),
+               "weight_grad");
+      return out;
+    }
     if (!(A.is_cuda() && B.is_cuda() && A.scalar_type() == torch::kFloat && B.scalar_type() == torch::kFloat &&
           A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0) && A.stride(1) == 1 && B.stride(1) == 1 &&
           A.stride(0) >= A.size(1) && B.stride(0) >= B.size(1)))  // (rows that overlap, e.g. an expanded row: not taken)

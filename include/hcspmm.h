@@ -952,6 +952,34 @@ int hcspmm_weight_grad(const float* A_d, int64_t lda, const float* B_d, int64_t 
                        int H, void* workspace_d, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same two products on operands of a stated element type (HCSPMM_DTYPE_*).  All-fp32 arguments forward to the entry
+ * points above (contiguous rows only: ld_in == D, ld_out == H).  fp16 / bf16 run on v_mfma_f32_16x16x32_{f16,bf16} with fp32
+ * accumulation (update_kernels_h16.hip):
+ *
+ *   hcspmm_dense_update_typed   out = in * W.  in [N, D] of in_dtype, rows ld_in elements apart; W [D, H] of w_dtype = in_dtype
+ *     or HCSPMM_DTYPE_F32 with element strides ldr / ldc -- fp32 weights are rounded to in_dtype (nearest even) as they are
+ *     staged, the result is that of W.to(in_dtype); out [N, H] of out_dtype = HCSPMM_DTYPE_F32 or in_dtype (rounded once from
+ *     the fp32 accumulator, nearest even, NaN stays NaN), rows ld_out elements apart.  Served: D even, ld_in even and in_d
+ *     4-byte aligned (rows on the dword grid; D % 8 == 0 takes 16-byte loads), 1 <= H <= 128, the staged weights
+ *     16*ceil(H/16) * (32*ceil(D/32) + 8) * 2 bytes within 160 KiB.  Anything else -- and any other dtype combination, ld_in < D,
+ *     ld_out < H -- is HCSPMM_EINVAL before any device call.  N == 0 returns HCSPMM_OK without a launch.
+ *
+ *   hcspmm_weight_grad_typed    dW = A^T * B.  A [N, D] and B [N, H] of `dtype`, unit inner stride, rows lda / ldb elements apart;
+ *     dW fp32 [D, H] row-major.  16-bit: D, H, lda, ldb even and both bases 4-byte aligned, else HCSPMM_EINVAL; served are
+ *     hcspmm_weight_grad's shapes and the rest of ceil(D/16) <= 8, ceil(H/16) <= 4 (16-bit operands leave registers for 32
+ *     accumulator tiles) -- hcspmm_weight_grad_typed_workspace is 0 outside that range, and an fp32 call inside it but outside
+ *     hcspmm_weight_grad's is HCSPMM_EINVAL.  Workspace (HCSPMM_EWORKSPACE when short) and determinism as hcspmm_weight_grad.
+ *
+ * Asynchronous on `stream`, allocate nothing, capturable.
+ * ---------------------------------------------------------------------------------------- */
+int hcspmm_dense_update_typed(const void* in_d, int64_t ld_in, int in_dtype, const void* weights_d, int w_dtype,
+                              int64_t ldr, int64_t ldc, void* out_d, int64_t ld_out, int out_dtype,
+                              int64_t N, int D, int H, void* stream);
+size_t hcspmm_weight_grad_typed_workspace(int64_t N, int D, int H); /* bytes; 0 if the shape is unsupported */
+int hcspmm_weight_grad_typed(const void* A_d, int64_t lda, const void* B_d, int64_t ldb, int dtype, float* dW_d,
+                             int64_t N, int D, int H, void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * LOI layout reorder (host).  Replaces reorder_plus_new_direct LOI.cpp:660-805 with the in-CSR
  * construction and output ordering of its main (LOI.cpp:826-841, :873-891): perm_out_h[N] lists
  * old vertex ids in their new order (full 16-row groups first, then short groups, then vertices
