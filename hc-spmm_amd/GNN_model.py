@@ -672,7 +672,7 @@ class ExtremumAggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         arg, perm32, *graph = ctx.saved_tensors
-        d_x = HCSPMM.forward_extremum_backward(d_out.contiguous(), arg, perm32, *graph) if ctx.needs_input_grad[0] else None
+        d_x = _extremum_backward(d_out, arg, perm32, graph) if ctx.needs_input_grad[0] else None
         return (d_x, None, None) + (None,) * N_GRAPH
 
 
@@ -693,14 +693,22 @@ class ExtremumAggregateDirected(torch.autograd.Function):
     def backward(ctx, d_out):
         arg, *rest = ctx.saved_tensors
         graph_t, eid_t = rest[:N_GRAPH], rest[N_GRAPH]
-        d_x = HCSPMM.forward_extremum_backward(d_out.contiguous(), arg, eid_t, *graph_t) if ctx.needs_input_grad[0] else None
+        d_x = _extremum_backward(d_out, arg, eid_t, graph_t) if ctx.needs_input_grad[0] else None
         return (d_x, None) + (None,) * (2 * N_GRAPH + 1)
+
+
+def _extremum_backward(d_out, arg, index, graph):
+    """HCSPMM.forward_extremum_backward in d_out's dtype: the kernel is fp32 (it gathers an int32 arg beside every value), so a
+    16-bit d_out is widened (exact) and the fp32 sums are rounded once into that dtype"""
+    d_x = HCSPMM.forward_extremum_backward(d_out.float().contiguous(), arg, index, *graph)
+    return d_x if d_out.dtype == torch.float32 else d_x.to(d_out.dtype)
 
 
 def extremum_aggregate(X, graph, reduce="max", directed=False):
     """max / min over each row's neighbours with autograd for X (float32 [N, D]); graph = the eight graph tensors, whose
     pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then
-    runs on transposed_graph(graph).  Rows without entries give 0."""
+    runs on transposed_graph(graph).  Rows without entries give 0.  A float16 / bfloat16 X (even D >= 4) runs the forward on
+    the 16-bit kernels -- Z in X's dtype, the winners' own bits -- and gets its gradient in that dtype."""
     if reduce not in ("max", "min"):
         raise ValueError("reduce must be 'max' or 'min', got %r" % (reduce,))
     if directed:
@@ -919,17 +927,28 @@ class SAGEConv(torch.nn.Module):
       "mean"         edge_weighted_aggregate with HCSPMM.edge_norm(..., "mean") values, computed once per graph.
     Both products run on _Update (the library's update and weight-gradient kernels).  _Conv's call signature, so that Net
     builds it; the aggregation is fixed by `aggr`, so edge_weight is refused.  The pattern must be symmetric unless
-    directed=True (the backward then runs on transposed_graph)."""
+    directed=True (the backward then runs on transposed_graph).
+    activation_dtype = torch.bfloat16 / torch.float16 (_Conv's convention): X is taken in that dtype (an fp32 X is rounded once
+    on entry), aggregated by the 16-bit kernels (extremum_aggregate / weighted_aggregate16), both products run on _Update16 and
+    the layer returns that dtype; the parameters and their gradients stay fp32.  Even widths."""
 
-    def __init__(self, input_dim, output_dim, fixed=0, aggr="max", directed=False):
+    def __init__(self, input_dim, output_dim, fixed=0, aggr="max", directed=False, activation_dtype=None):
         super().__init__()
         if aggr not in ("max", "min", "mean"):
             raise ValueError("SAGEConv aggr must be 'max', 'min' or 'mean', got %r" % (aggr,))
-        self.fixed, self.aggr, self.directed = fixed, aggr, bool(directed)
+        self.fixed, self.aggr, self.directed, self.activation_dtype = fixed, aggr, bool(directed), activation_dtype
         self.weights_root = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self.weights_neigh = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self._mean = None  # (row_pointers, column_index, values) of the last graph
+        self._check_activation_dtype()
         self.reset_parameters()
+
+    def _check_activation_dtype(self):
+        if self.activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (self.activation_dtype,))
+        if self.activation_dtype is not None and (self.weights_root.size(0) % 2 or self.weights_root.size(1) % 2):
+            raise ValueError("activation_dtype needs even widths (16-bit rows on the dword grid), got %d -> %d"
+                             % tuple(self.weights_root.shape))
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights_root.size(1))
@@ -947,6 +966,14 @@ class SAGEConv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("SAGEConv aggregates with its own `aggr`: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if self.activation_dtype is not None:
+            self._check_activation_dtype()  # (the attribute may have been set after construction, as the driver does for _Conv)
+            X = X.to(self.activation_dtype)
+            if self.aggr == "mean":
+                agg = weighted_aggregate16(X, self._mean_values(row_pointers, column_index), graph, self.directed)
+            else:
+                agg = extremum_aggregate(X, graph, self.aggr, self.directed)
+            return _Update16.apply(X, self.weights_root) + _Update16.apply(agg, self.weights_neigh)
         if self.aggr == "mean":
             agg = edge_weighted_aggregate(X, self._mean_values(row_pointers, column_index), graph, self.directed)
         else:

@@ -68,7 +68,7 @@ def parse_args(argv=None):
     # addition: 16-bit activations end to end (GNN_model._Conv activation_dtype: 16-bit aggregation and the 16-bit update / weight
     # gradient kernels; parameters, their gradients and the loss stay fp32)
     p.add_argument("--activation-dtype", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
-                   help="--model gcn / gin with --norm sym|mean: run the layers on activations of this type")
+                   help="--model gcn / gin with --norm sym|mean, or --model sage: run the layers on activations of this type")
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
     p.add_argument("--directed", action="store_true",
                    help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
@@ -249,9 +249,10 @@ def main(argv=None):
     if args.model in ("gcn", "gin"):
         def conv_cls(input_dim, output_dim, fixed):
             return (GCNConv if args.model == "gcn" else GINConv)(input_dim, output_dim, fixed, directed=directed)
+    activation_dtype = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[args.activation_dtype]
     if args.model == "sage":
         def conv_cls(input_dim, output_dim, fixed):
-            return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed)
+            return SAGEConv(input_dim, output_dim, fixed, aggr=args.aggr, directed=directed, activation_dtype=activation_dtype)
     if args.model == "pna":
         def conv_cls(input_dim, output_dim, fixed):
             if fixed == 2:  # the last layer, as for sage
@@ -289,12 +290,12 @@ def main(argv=None):
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight, edge_attr).to(device)
     if args.fp8:
         set_feature_storage(model, "fp8")
-    if args.activation_dtype != "fp32":
+    if args.activation_dtype != "fp32" and args.model != "sage":  # (SAGEConv took it where it was built)
         if args.model not in ("gcn", "gin") or edge_weight is None:
-            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean")
+            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean, or --model sage")
         for m in model.modules():
             if isinstance(m, (GCNConv, GINConv)):
-                m.activation_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.activation_dtype]
+                m.activation_dtype = activation_dtype
     optimizer = torch.optim.Adam(model.parameters(), lr=0.01, capturable=args.graph)
 
     epoch = [0]

@@ -577,6 +577,42 @@ extern "C" int hcspmm_forward_extremum(const void* X, int64_t x_rows, int64_t ld
                        workspace, workspace_bytes, stream_v, reduce, arg_out, nullptr, ldarg, nullptr);
 }
 
+// The forward on features of element type `dtype` (fp32: the call above; fp16 / bf16: spmm_extremum16.hip, rows on the dword grid,
+// Z of X's type, fp32 / int32 partial slots, 64-column panels).
+extern "C" int hcspmm_forward_extremum_typed(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                             const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                             const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                             const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                             void* workspace, size_t workspace_bytes, void* stream_v, int reduce, int32_t* arg_out,
+                                             int64_t ldarg) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_forward_extremum(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                                   plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, reduce, arg_out, ldarg);
+  if (reduce != HCSPMM_REDUCE_MAX && reduce != HCSPMM_REDUCE_MIN) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D || (arg_out && ldarg < D)) return HCSPMM_EINVAL;
+  // rows on the dword grid: an even width of at least 4 columns, even strides, 4-byte aligned bases
+  if (D < 4 || ((D | ldx | ldz) & 1) != 0 || !aligned(X, 4) || !aligned(Z, 4)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::XArgs x{};
+  // workspace: the fp32 unit's two areas -- fp32 values, then int32 positions; the features' type decides the panel width
+  const int rc = bind_graph(x.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 2, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (x.p.plan) {
+    x.ppos = x.p.partial ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + hcspmm_workspace_bytes(ph, D)) : nullptr;
+    x.segment_len = ph->segment_len;
+  }
+  set_operands(x.p, X, Z, ldx, ldz);
+  x.rowptr = rowptr;
+  x.flip = reduce == HCSPMM_REDUCE_MIN ? 0x80000000u : 0u;
+  x.arg = arg_out;
+  x.ldarg = (size_t)ldarg;
+  const hipError_t e = hcspmm::launch_extremum16(x, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_forward_extremum_backward(const float* grad_Z, int64_t ldg, const int32_t* arg, int64_t ldarg, float* grad_X,
                                                 int64_t ldgx, const int32_t* rowptr, const int32_t* col,
                                                 const int32_t* blockPartition, const int32_t* edgeToColumn,

@@ -309,6 +309,11 @@ struct XArgs {
 // vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
 hipError_t launch_extremum_f32(const XArgs& a, int vec, hipStream_t stream);
 hipError_t launch_extremum_backward_f32(const XArgs& a, int vec, hipStream_t stream);
+// The forward on fp16 / bf16 features (spmm_extremum16.hip; the 16-bit dtypes of hcspmm_forward_extremum_typed): p.X and p.Z hold
+// 16-bit elements on the dword grid (even D >= 4, even strides, 4-byte aligned bases); arg, the partial slots (fp32 values, int32
+// positions) and every other field are the fp32 forward's.  The unit picks its own lanes: 8 elements from 32 columns per panel
+// on, 4 below.  dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_extremum16(const XArgs& a, int dtype, hipStream_t stream);
 
 // Sum, sum of squares, max and min of each row's neighbours in one gather pass (spmm_multi.hip; include/hcspmm.h
 // hcspmm_forward_multi), fp32.  p as for launch_extremum_f32 with p.Z unused: the six outputs below share the row stride p.ldz

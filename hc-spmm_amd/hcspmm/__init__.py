@@ -676,15 +676,22 @@ def _extremum(X, graph, reduce, return_arg):
     _check_graph(*graph[:5])
     if not X.is_cuda:
         raise RuntimeError("input must be a CUDA tensor")
-    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
-        raise RuntimeError("input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)")
+    if X.dtype not in _DTYPES or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("input must be a 2-D float32 / float16 / bfloat16 view with unit inner stride")
     N, D = graph[0].size(0) - 1, X.size(1)
+    if X.dtype != torch.float32 and (D < 4 or D % 2 or X.stride(0) % 2 or X.data_ptr() % 4):
+        raise RuntimeError("16-bit max / min aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: "
+                           "pad the input to an even width")
     c = _planned_call(graph[:6], row_nzr, D, X.size(0), X.device, ws_fn=_ws_bytes_extremum)
-    Z = torch.empty((N, D), dtype=torch.float32, device=X.device)
+    Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
     arg = torch.empty((N, D), dtype=torch.int32, device=X.device) if return_arg else None
+    parg = _ptr(arg) if arg is not None else ctypes.c_void_p(0)
     with c:
-        check(lib().hcspmm_forward_extremum(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, 0, *c.graph, *c.ws, reduce,
-                                            _ptr(arg) if arg is not None else ctypes.c_void_p(0), D))
+        if X.dtype == torch.float32:
+            check(lib().hcspmm_forward_extremum(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, 0, *c.graph, *c.ws, reduce, parg, D))
+        else:
+            check(lib().hcspmm_forward_extremum_typed(_ptr(X), X.size(0), X.stride(0), _ptr(Z), D, _DTYPES[X.dtype], *c.graph,
+                                                      *c.ws, reduce, parg, D))
     return [Z, arg] if return_arg else [Z]
 
 
@@ -693,7 +700,9 @@ def forward_max(X, row_pointers, column_index, blockPartition, edgeToColumn, edg
     """Max over each row's neighbours -> [Z, arg] ([Z] with return_arg=False): Z[r][d] = max of X[col(e)][d] over the
     entries e of row r, arg[r][d] = the winning e (int32).  Ties go to the lowest e, NaN wins, rows without entries give 0
     and -1 (hcspmm.h hcspmm_forward_extremum).  X: float32 [rows, D] view with unit inner stride (rows >= the columns the
-    graph refers to)."""
+    graph refers to), or a float16 / bfloat16 one (hcspmm_forward_extremum_typed): Z then has X's dtype and holds the winner's own
+    16 bits, arg is that of the widened values, at half the gathered bytes.  That form serves even widths of at least 4 with an
+    even row stride and a 4-byte aligned view: pad anything else to an even width."""
     return _extremum(X, (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr),
                      0, return_arg)
 

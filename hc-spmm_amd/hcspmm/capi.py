@@ -103,6 +103,8 @@ SYMBOLS = {
     "hcspmm_extremum_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_extremum": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
                                        _vp, _sz, _vp, _int, _vp, _i64]),
+    "hcspmm_forward_extremum_typed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
+                                             _int, _vp, _sz, _vp, _int, _vp, _i64]),
     "hcspmm_forward_extremum_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
                                                 _int, _vp, _vp, _sz, _vp]),
     "hcspmm_multi_workspace_bytes": (_sz, [_hp, _int]),

@@ -422,23 +422,30 @@ std::vector<torch::Tensor> spmm_forward_weighted_indexed(torch::Tensor input, to
 }
 
 // Max / min aggregation (hcspmm_forward_extremum): float32 X, a strided view with unit inner stride whose rows the column ids
-// index -> {Z, arg} ({Z} without arg)
+// index -> {Z, arg} ({Z} without arg).  float16 / bfloat16 X (hcspmm_forward_extremum_typed): Z in X's type, the winner's own 16
+// bits; even widths of at least 4, an even row stride, a 4-byte aligned view
 std::vector<torch::Tensor> spmm_forward_extremum(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
                                                  torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
                                                  torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
                                                  bool return_arg, int reduce) {
   CHECK_CUDA(input);
-  TORCH_CHECK(input.scalar_type() == torch::kFloat && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
-              "input must be a 2-D float32 view with unit inner stride (max / min aggregation is float32 only)");
-  CallOptions o;
+  const int dtype = feature_dtype(input);
+  TORCH_CHECK(dtype >= 0 && input.dim() == 2 && input.stride(1) == 1 && input.stride(0) >= input.size(1),
+              "input must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
+  if (dtype != HCSPMM_DTYPE_F32)
+    TORCH_CHECK(input.size(1) >= 4 && rows16(input),
+                "16-bit max / min aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: pad the input "
+                "to an even width");
+  CallOptions o(CallOptions::kTyped);
   o.rect = o.strided = true;
   o.workspace_bytes = hcspmm_extremum_workspace_bytes;  // values and positions of the split rows' partial slots
   PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
   auto output = torch::empty({c.N, (int64_t)c.D}, input.options());
   torch::Tensor arg;
   if (return_arg) arg = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kInt));
-  const int rc = invoke(hcspmm_forward_extremum,
-                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, HCSPMM_DTYPE_F32),
+  // float32 takes the entry point it always took; the 16-bit types the typed one
+  const int rc = invoke(dtype == HCSPMM_DTYPE_F32 ? hcspmm_forward_extremum : hcspmm_forward_extremum_typed,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, dtype),
                         c.graph(), c.ws(), std::make_tuple(reduce, return_arg ? mptr(arg) : nullptr, c.D));
   check_rc(rc, reduce == HCSPMM_REDUCE_MAX ? "forward_max" : "forward_min");
   if (return_arg) return {output, arg};

@@ -36,7 +36,8 @@ extern "C" {
  * hcspmm_multi_workspace_bytes, hcspmm_forward_multi (round 15); hcspmm_softmax_workspace_bytes, hcspmm_forward_softmax,
  * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
- * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23).
+ * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
+ * hcspmm_forward_extremum_typed (round 25).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -462,6 +463,26 @@ int hcspmm_forward_extremum(const void* X_d, int64_t x_rows, int64_t ldx, void* 
                             const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                             int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                             int reduce, int32_t* arg_out_d, int64_t ldarg);
+/* hcspmm_forward_extremum_typed: the same aggregation with `dtype` honoured; Z_d has X_d's element type.
+ *   HCSPMM_DTYPE_F32           forwards to hcspmm_forward_extremum
+ *   HCSPMM_DTYPE_F16 / _BF16   the order and every guarantee above on the elements widened to fp32 (exact): arg is the arg of
+ *                              hcspmm_forward_extremum on a widened copy of X, and Z holds the winning entry's own 16 bits (a
+ *                              NaN's payload and the sign of a zero included; +0 and -1 for rows without entries).  A maximum
+ *                              selects: nothing is rounded.  Half the gathered bytes (kernels of their own, spmm_extremum16.hip);
+ *                              the column panels of a planned call are 64 columns wide.
+ * ldx / ldz count elements.  The 16-bit types serve every EVEN embedding_dim >= 4 with even ldx / ldz and 4-byte aligned X_d /
+ * Z_d (rows on the dword grid: a column block of a wider 16-bit matrix passes as it is); an odd width or stride, embedding_dim
+ * == 2, a misaligned base, ldarg < embedding_dim with arg_out_d set or a bad reduce is HCSPMM_EINVAL before any device call --
+ * pad to an even width.  A dtype outside F32 ... BF16 is HCSPMM_EINVAL; every other argument, plan and workspace error is
+ * hcspmm_forward_extremum's.  workspace_d >= hcspmm_extremum_workspace_bytes() as above (the partial slots are fp32 values and
+ * int32 positions whatever the features are).  arg_out_d is what hcspmm_forward_extremum_backward takes.  num_nodes == 0
+ * returns HCSPMM_OK without a launch.  Asynchronous on `stream`, allocates nothing, capturable. */
+int hcspmm_forward_extremum_typed(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype,
+                                  const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* blockPartition_d,
+                                  const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
+                                  const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
+                                  int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
+                                  int reduce, int32_t* arg_out_d, int64_t ldarg);
 
 /* Backward of hcspmm_forward_extremum on a square, pattern-symmetric graph:
  *   grad_X[j][d] = sum of grad_Z[i][d] over the entries e = (i, j) with arg[i][d] == e
