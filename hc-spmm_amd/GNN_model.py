@@ -1142,16 +1142,57 @@ class SoftmaxAggregate(torch.autograd.Function):
         return (d_x, d_t) + (None,) * (2 * N_GRAPH)
 
 
-def softmax_aggregate(X, graph, t=1.0, directed=False):
+class SoftmaxAggregate16(torch.autograd.Function):
+    """SoftmaxAggregate on a float16 / bfloat16 X (HCSPMM.forward_softmax16 / softmax_backward16): Z in X's dtype, and what is
+    saved for the backward is X16, Z16 and the fp32 log-sum-exp LSE -- 8 bytes per element against SoftmaxAggregate's 16 -- plus,
+    when t needs a gradient, the fp32 softmax-weighted variance Var (12 against 20):
+      dX = HCSPMM.softmax_backward16 on the graph the backward walks, with dZ rounded once to X's dtype; fp32 sums, returned in
+           X's dtype;
+      dt = sum_i dZ[i] * Var[i] -- the kernel takes Var from the unrounded mean, where Q - Z^2 on a 16-bit Z would cancel.
+    t and tail as for SoftmaxAggregate."""
+
+    @staticmethod
+    def forward(ctx, X, t, *tail):
+        X = X.contiguous()
+        learnt = isinstance(t, torch.Tensor)
+        beta = t.detach().float() if learnt else float(t)
+        need_t = learnt and ctx.needs_input_grad[1]
+        Z, LSE, Var = HCSPMM.forward_softmax16(X, beta, *tail[:N_GRAPH], ("lse", "var") if need_t else ("lse",))
+        ctx.beta = None if learnt else beta
+        ctx.save_for_backward(X, Z, LSE, Var, beta if learnt else None, *tail[N_GRAPH:])
+        return Z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # the backward is a launch, not a graph of differentiable ops
+    def backward(ctx, d_out):
+        X, Z, LSE, Var, beta, *graph_b = ctx.saved_tensors
+        d_x = d_t = None
+        if ctx.needs_input_grad[0]:
+            d_x = HCSPMM.softmax_backward16(d_out.to(X.dtype).contiguous(), Z, LSE, X, ctx.beta if beta is None else beta,
+                                            *graph_b).to(X.dtype)
+        if ctx.needs_input_grad[1]:
+            per_column = (d_out.float() * Var).sum(0)
+            d_t = (per_column.sum() if beta.numel() == 1 else per_column).reshape(beta.shape)
+        return (d_x, d_t) + (None,) * (2 * N_GRAPH)
+
+
+def softmax_aggregate(X, graph, t=1.0, directed=False, activation_dtype=None):
     """Softmax aggregation over each row's neighbours (DeeperGCN; PyG SoftmaxAggregation), per feature column:
     Z[i] = sum_j softmax_j(t * X[j]) X[j], with autograd for X (float32 [N, D]) and for t when it is a tensor that requires grad
     (1 or D elements; a float otherwise).  t -> +-inf approaches max / min, t = 0 is the mean.  graph = the eight graph tensors,
     whose pattern must be symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then
-    runs on transposed_graph(graph).  Rows without entries give 0."""
+    runs on transposed_graph(graph).  Rows without entries give 0.
+    activation_dtype = torch.bfloat16 / torch.float16: X is taken in that dtype (an fp32 X is rounded once, and so is dZ in the
+    backward), the 16-bit kernels run (SoftmaxAggregate16) and Z has that dtype; even D >= 4.  A 16-bit X selects them as well."""
+    if activation_dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+    if activation_dtype is not None:
+        X = X.to(activation_dtype)
+    fn = SoftmaxAggregate16 if X.dtype in (torch.bfloat16, torch.float16) else SoftmaxAggregate
     if directed:
-        return SoftmaxAggregate.apply(X, t, *graph, *transposed_graph(graph)[:N_GRAPH])
+        return fn.apply(X, t, *graph, *transposed_graph(graph)[:N_GRAPH])
     transpose_permutation_i32(graph[0], graph[1])  # an asymmetric pattern is refused before any launch (cached)
-    return SoftmaxAggregate.apply(X, t, *graph, *graph)
+    return fn.apply(X, t, *graph, *graph)
 
 
 class GENConv(torch.nn.Module):
@@ -1160,15 +1201,27 @@ class GENConv(torch.nn.Module):
     one softmax_aggregate pass and one product on _Update.  t is the inverse temperature: a float, or with learn_t=True a scalar
     Parameter initialised to it (its gradient costs no kernel: SoftmaxAggregate).  _Conv's call signature, so that Net builds
     it; edge_weight is refused.  The pattern must be symmetric unless directed=True (the backward then runs on
-    transposed_graph)."""
+    transposed_graph).
+    activation_dtype = torch.bfloat16 / torch.float16 (_Conv's convention): X is taken in that dtype (an fp32 X is rounded once
+    on entry), relu(X) + eps and X + agg run in it, the aggregation on the 16-bit kernels (SoftmaxAggregate16: 8 saved bytes per
+    element against 16), the product on _Update16, and the layer returns that dtype; W, t and their gradients stay fp32.  Even
+    widths."""
 
-    def __init__(self, input_dim, output_dim, t=1.0, learn_t=False, eps=1e-7, directed=False):
+    def __init__(self, input_dim, output_dim, t=1.0, learn_t=False, eps=1e-7, directed=False, activation_dtype=None):
         super().__init__()
-        self.directed, self.eps = bool(directed), float(eps)
+        self.directed, self.eps, self.activation_dtype = bool(directed), float(eps), activation_dtype
         self.weights = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self.initial_t = float(t)
         self.t = torch.nn.Parameter(torch.empty(())) if learn_t else self.initial_t
+        self._check_activation_dtype()
         self.reset_parameters()
+
+    def _check_activation_dtype(self):
+        if self.activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (self.activation_dtype,))
+        if self.activation_dtype is not None and (self.weights.size(0) % 2 or self.weights.size(1) % 2):
+            raise ValueError("activation_dtype needs even widths (16-bit rows on the dword grid), got %d -> %d"
+                             % tuple(self.weights.shape))
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights.size(1))
@@ -1181,6 +1234,11 @@ class GENConv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("GENConv aggregates with its own softmax weights: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if self.activation_dtype is not None:
+            self._check_activation_dtype()  # (the attribute may have been set after construction)
+            X = X.to(self.activation_dtype)
+            agg = softmax_aggregate(torch.relu(X) + self.eps, graph, self.t, self.directed)
+            return _Update16.apply(X + agg, self.weights)
         agg = softmax_aggregate(torch.relu(X) + self.eps, graph, self.t, self.directed)
         return _Update.apply(X + agg, self.weights)
 

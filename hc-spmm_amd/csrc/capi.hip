@@ -727,6 +727,67 @@ extern "C" int hcspmm_softmax_backward(const float* grad_Z, const float* Z, cons
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// The aggregation on fp16 / bf16 features (spmm_softmax16.hip): rows on the dword grid, Z of X's type, one fp32 statistic (and the
+// variance when the temperature learns), the fp32 unit's four partial areas, 64-column panels.  fp32 is refused: its outputs differ.
+extern "C" int hcspmm_forward_softmax_typed(const void* X, int64_t x_rows, int64_t ldx, int dtype, const float* beta, void* Z,
+                                            int64_t ldz, float* LSE, float* Var, int64_t ld_stat, const int32_t* rowptr,
+                                            const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
+                                            const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
+                                            const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
+                                            size_t workspace_bytes, void* stream_v) {
+  if (dtype != HCSPMM_DTYPE_F16 && dtype != HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D || ((LSE || Var) && ld_stat < D)) return HCSPMM_EINVAL;
+  if (!Z || !beta) return HCSPMM_EINVAL;
+  // rows on the dword grid: an even width of at least 4 columns, even strides, 4-byte aligned bases
+  if (D < 4 || ((D | ldx | ldz) & 1) != 0 || !aligned(X, 4) || !aligned(Z, 4)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::S16Args s{};
+  // workspace: four areas of hcspmm_workspace_bytes each -- m, l, a, q; the features' type decides the panel width
+  const int rc = bind_graph(s.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 4, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (s.p.plan) s.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+  set_operands(s.p, X, Z, ldx, ldz);
+  s.rowptr = rowptr;
+  s.beta = beta;
+  s.lse = LSE;
+  s.var = Var;
+  s.ld_stat = (size_t)ld_stat;
+  const hipError_t e = hcspmm::launch_softmax16(s, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+// Its gradient with respect to X (softmax_aggr_grad16.hip) on the graph the backward walks: a plain-sum launch, one partial area.
+extern "C" int hcspmm_softmax_backward_typed(const void* grad_Z, const void* Z, int64_t ld_in, const float* LSE, int64_t ld_stat,
+                                             int64_t src_rows, const void* X, int64_t ldx, int dtype, const float* beta,
+                                             float* grad_X, int64_t ldgx, const int32_t* rowptr, const int32_t* col,
+                                             const int32_t* blockPartition, const int32_t* edgeToColumn, const int32_t* edgeToRow,
+                                             const int32_t* hybrid_type, const int32_t* plan_d, const hcspmm_plan_header* ph,
+                                             int64_t N, int64_t E, int D, void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype != HCSPMM_DTYPE_F16 && dtype != HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (N < 0 || E < 0 || src_rows < 0 || D <= 0 || ld_in < D || ld_stat < D || ldx < D || ldgx < D) return HCSPMM_EINVAL;
+  if (!grad_X || !beta) return HCSPMM_EINVAL;
+  // every 16-bit operand on the dword grid
+  if (D < 4 || ((D | ld_in | ldx) & 1) != 0 || !aligned(grad_Z, 4) || !aligned(Z, 4) || !aligned(X, 4)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && (!col || !grad_Z || !Z || !LSE || src_rows == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::SGrad16Args a{};
+  const int rc = bind_graph(a.p, GRAPH_IN, D, src_rows, workspace, workspace_bytes, 1, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  set_operands(a.p, X, grad_X, ldx, ldgx);
+  a.rowptr = rowptr;
+  a.beta = beta;
+  a.G = static_cast<const unsigned short*>(grad_Z);
+  a.Zh = static_cast<const unsigned short*>(Z);
+  a.LSE = LSE;
+  a.ld_in = (size_t)ld_in;
+  a.ld_stat = (size_t)ld_stat;
+  const hipError_t e = hcspmm::launch_softmax_backward16(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" size_t hcspmm_gated_workspace_bytes(const hcspmm_plan_header* ph, int D) { return 2 * hcspmm_workspace_bytes(ph, D); }
 
 // Gated neighbour aggregation (spmm_gated.hip): a plain-sum launch per output on the binary product's plan, P read by row, Q and V

@@ -358,6 +358,33 @@ struct SGradArgs {
 };
 hipError_t launch_softmax_backward_f32(const SGradArgs& a, int vec, hipStream_t stream);
 
+// The softmax aggregation on fp16 / bf16 features (spmm_softmax16.hip; hcspmm_forward_softmax_typed): p.X and p.Z hold 16-bit
+// elements on the dword grid (even D >= 4, even strides, 4-byte aligned bases); lse = m + ln l and var = q / l - zf^2 are fp32
+// with the row stride ld_stat, and a null one is not written (a null var selects the builds without the q state).  p.partial =
+// the fp32 unit's four areas of `area` floats.  The unit picks its own lanes: 8 elements from 32 columns per panel on, 4 below.
+struct S16Args {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  const float* beta;  // [D]
+  float *lse, *var;
+  size_t ld_stat;
+  size_t area;        // floats per workspace area
+};
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_softmax16(const S16Args& a, int dtype, hipStream_t stream);
+// its gradient with respect to X (softmax_aggr_grad16.hip, hcspmm_softmax_backward_typed): row j sums exp(beta x_j - LSE_i) * G_i *
+// (1 + beta (x_j - Z_i)) over its entries (j, i).  p.X = X (the tasks' OWN rows, 16-bit, stride p.ldx), p.Z = grad_X (fp32); G and
+// Zh (16-bit, row stride ld_in) and LSE (fp32, row stride ld_stat) are gathered through the column ids; partial = fp32 sums.
+struct SGrad16Args {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  const float* beta;  // [D]
+  const unsigned short *G, *Zh;
+  const float* LSE;
+  size_t ld_in, ld_stat;
+};
+hipError_t launch_softmax_backward16(const SGrad16Args& a, int dtype, hipStream_t stream);
+
 // Edge-feature messages (spmm_edge_messages.hip; include/hcspmm.h hcspmm_forward_edge_messages), fp32: Z[r] = sum over the entries
 // e of row r of m(X[col(e)], F[fi(e)]), fi(e) = findex ? findex[e] : e.  p as for launch_extremum_f32 (p.plan == nullptr: plan-free;
 // p.X may be null for the copy op); partial = fp32 sums of the split rows.

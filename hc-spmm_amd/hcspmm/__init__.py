@@ -30,7 +30,7 @@ __all__ = [
     "transpose_graph", "transpose_graph_device", "sample_row_pointers", "sample_neighbors", "plan_free_graph",
     "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
-    "forward_softmax", "softmax_backward", "forward_gated",
+    "forward_softmax", "softmax_backward", "forward_softmax16", "softmax_backward16", "forward_gated",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
@@ -876,6 +876,85 @@ def softmax_backward(grad_Z, Z, M, L, X, beta, row_pointers, column_index, block
     with c:
         check(lib().hcspmm_softmax_backward(_ptr(grad_Z), _ptr(Z), _ptr(M), _ptr(L), D, grad_Z.size(0), _ptr(X), X.stride(0),
                                             _ptr(b), _ptr(grad_X), D, *c.graph, *c.ws))
+    return grad_X
+
+
+def _check_softmax16(t, name):
+    """a 16-bit operand of the softmax aggregation: float16 / bfloat16 rows on the dword grid"""
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+    if t.dtype not in (torch.float16, torch.bfloat16) or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+        raise RuntimeError("%s must be a 2-D float16 / bfloat16 view with unit inner stride, got %s" % (name, t.dtype))
+    if t.size(1) < 4 or t.size(1) % 2 or t.stride(0) % 2 or t.data_ptr() % 4:
+        raise RuntimeError("16-bit softmax aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: "
+                           "pad %s to an even width" % name)
+
+
+def forward_softmax16(X, beta, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                      stats=("lse",)):
+    """forward_softmax on float16 / bfloat16 features -> (Z16, LSE, Var) (hcspmm.h hcspmm_forward_softmax_typed): Z[r][d] = the
+    fp32 softmax-weighted mean of the widened X[col(e)][d], rounded once to X's dtype; LSE = log sum_e exp(beta x_e) and Var = the
+    softmax-weighted variance (from the unrounded mean), contiguous float32 [N, D].  stats: some of "lse", "var"; a statistic not
+    asked for is None, and without "var" the kernels carry no state for it.  LSE is all the backward needs (softmax_backward16);
+    the gradient with respect to beta is (grad_Z * Var).sum(0).  beta as for forward_softmax.  Rows without entries give Z = Var =
+    0, LSE = -inf.  X: even widths of at least 4 with an even row stride and a 4-byte aligned view: pad anything else to an even
+    width."""
+    if isinstance(stats, (str, bytes)):
+        stats = (stats,)
+    names = tuple(stats)
+    for n in names:
+        if n not in ("lse", "var"):
+            raise ValueError("stats must name some of 'lse', 'var', got %r" % (n,))
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    _check_softmax16(X, "input")
+    N, D = row_pointers.size(0) - 1, X.size(1)
+    b = _beta_vector(beta, D, X.device)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, X.size(0),
+                      X.device, ws_fn=_ws_bytes_softmax)
+    Z = torch.empty((N, D), dtype=X.dtype, device=X.device)
+    out = [torch.empty((N, D), dtype=torch.float32, device=X.device) if n in names else None for n in ("lse", "var")]
+    if N == 0:
+        return (Z, *out)
+    null = ctypes.c_void_p(0)
+    with c:
+        check(lib().hcspmm_forward_softmax_typed(_ptr(X), X.size(0), X.stride(0), _DTYPES[X.dtype], _ptr(b), _ptr(Z), D,
+                                                 *(_ptr(t) if t is not None else null for t in out), D, *c.graph, *c.ws))
+    return (Z, *out)
+
+
+def softmax_backward16(grad_Z, Z, LSE, X, beta, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                       row_nzr, col_nzr):
+    """Gradient of forward_softmax16 with respect to X -> float32 [n, D], on the graph the backward WALKS (as softmax_backward):
+    dX[j] = sum over the entries (j, i) of row j of exp(beta x_j - LSE[i]) * grad_Z[i] * (1 + beta (x_j - Z[i])).  grad_Z, Z:
+    contiguous [rows, D] of X's 16-bit dtype; LSE: contiguous float32 [rows, D]; X: the 16-bit [n, D] view the forward gathered.  8
+    gathered bytes per column against softmax_backward's 16 (hcspmm.h hcspmm_softmax_backward_typed).  Deterministic, no atomics."""
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    for t, name in ((X, "input"), (grad_Z, "grad_Z"), (Z, "Z")):
+        _check_softmax16(t, name)
+    _check_input(LSE, "LSE")
+    if grad_Z.dtype != X.dtype or Z.dtype != X.dtype:
+        raise RuntimeError("grad_Z, Z and the input must have one dtype, got %s, %s and %s" % (grad_Z.dtype, Z.dtype, X.dtype))
+    n, D = row_pointers.size(0) - 1, X.size(1)
+    if X.size(0) != n:
+        raise RuntimeError("input has %d rows but the walked graph has %d nodes" % (X.size(0), n))
+    if not (grad_Z.is_contiguous() and Z.is_contiguous()) or grad_Z.size(1) != D or Z.shape != grad_Z.shape:
+        raise RuntimeError("grad_Z and Z must be contiguous [rows, D] tensors with D = %d, got %s and %s"
+                           % (D, tuple(grad_Z.shape), tuple(Z.shape)))
+    if LSE.dtype != torch.float32 or LSE.shape != grad_Z.shape:
+        raise RuntimeError("LSE must be a float32 tensor of grad_Z's shape")
+    if not (grad_Z.device == Z.device == LSE.device == X.device):
+        raise RuntimeError("grad_Z, Z and LSE must be on the device of the input")
+    b = _beta_vector(beta, D, X.device)
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D,
+                      grad_Z.size(0), X.device)
+    if c.E > 0 and grad_Z.size(0) == 0:
+        raise RuntimeError("grad_Z has no rows but the walked graph has %d entries" % c.E)
+    grad_X = torch.empty((n, D), dtype=torch.float32, device=X.device)
+    if n == 0:
+        return grad_X
+    with c:
+        check(lib().hcspmm_softmax_backward_typed(_ptr(grad_Z), _ptr(Z), D, _ptr(LSE), D, grad_Z.size(0), _ptr(X), X.stride(0),
+                                                  _DTYPES[X.dtype], _ptr(b), _ptr(grad_X), D, *c.graph, *c.ws))
     return grad_X
 
 

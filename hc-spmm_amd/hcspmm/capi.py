@@ -115,6 +115,10 @@ SYMBOLS = {
                                       _i64, _int, _vp, _sz, _vp]),
     "hcspmm_softmax_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp,
                                        _i64, _i64, _int, _vp, _sz, _vp]),
+    "hcspmm_forward_softmax_typed": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp,
+                                            _i64, _i64, _int, _vp, _sz, _vp]),
+    "hcspmm_softmax_backward_typed": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_gated_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_gated": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp,
                                     _i64, _i64, _int, _vp, _sz, _vp]),

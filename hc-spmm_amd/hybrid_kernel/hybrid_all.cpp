@@ -508,7 +508,7 @@ torch::Tensor beta_vector(const pybind11::object& beta, int64_t D, const torch::
                 t.scalar_type(), " ", t.sizes(), " on ", t.device());
     return t.detach().reshape({-1}).expand({D}).contiguous();
   }
-  return torch::full({D}, pybind11::cast<double>(beta), input.options());
+  return torch::full({D}, pybind11::cast<double>(beta), input.options().dtype(torch::kFloat));  // (the 16-bit calls' input is not)
 }
 
 // Per-channel softmax aggregation in one gather pass (hcspmm_forward_softmax): forward_max's input contract -> (Z, M, L, Q),
@@ -656,6 +656,96 @@ torch::Tensor spmm_softmax_backward(torch::Tensor grad_Z, torch::Tensor Z, torch
                                         input.data_ptr<float>(), input.stride(0), b.data_ptr<float>(), grad_X.data_ptr<float>(), D),
                         c.graph(), c.ws());
   check_rc(rc, "softmax_backward");
+  return grad_X;
+}
+
+// a 16-bit operand of the softmax aggregation: float16 / bfloat16 rows on the dword grid
+void check_softmax16(const torch::Tensor& t, const char* name) {
+  CHECK_CUDA(t);
+  TORCH_CHECK((t.scalar_type() == torch::kHalf || t.scalar_type() == torch::kBFloat16) && t.dim() == 2 && t.stride(1) == 1 &&
+                  t.stride(0) >= t.size(1),
+              name, " must be a 2-D float16 / bfloat16 view with unit inner stride, got ", t.scalar_type());
+  TORCH_CHECK(t.size(1) >= 4 && rows16(t), "16-bit softmax aggregation serves even widths >= 4 with even row strides and 4-byte "
+              "aligned views: pad ", name, " to an even width");
+}
+
+// Softmax aggregation on float16 / bfloat16 features (hcspmm_forward_softmax_typed) -> (Z16, LSE, Var): Z in the input's type, the
+// float32 log-sum-exp and softmax-weighted variance as `stats` (some of "lse", "var") asks, None otherwise
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> spmm_forward_softmax16(
+    torch::Tensor input, pybind11::object beta, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
+    torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
+    pybind11::object stats) {
+  static const char* const kNames[2] = {"lse", "var"};
+  bool want[2] = {false, false};
+  if (pybind11::isinstance<pybind11::str>(stats)) stats = pybind11::make_tuple(stats);
+  if (!pybind11::isinstance<pybind11::iterable>(stats)) throw pybind11::value_error("stats must name some of 'lse', 'var'");
+  for (const auto& item : stats) {
+    if (!pybind11::isinstance<pybind11::str>(item)) throw pybind11::value_error("stats must name some of 'lse', 'var'");
+    const std::string a = pybind11::cast<std::string>(item);
+    int k = 0;
+    while (k < 2 && a != kNames[k]) ++k;
+    if (k == 2) throw pybind11::value_error("stats must name some of 'lse', 'var', got '" + a + "'");
+    want[k] = true;
+  }
+  check_softmax16(input, "input");
+  CallOptions o(CallOptions::kTyped);
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_softmax_workspace_bytes;  // four float32 arrays per partial slot of a split row
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  const torch::Tensor b = beta_vector(beta, c.D, input);
+  auto Z = torch::empty({c.N, (int64_t)c.D}, input.options());
+  c10::optional<torch::Tensor> out[2];
+  float* sp[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    if (!want[k]) continue;
+    auto t = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kFloat));
+    sp[k] = c.N > 0 ? t.data_ptr<float>() : nullptr;
+    out[k] = t;
+  }
+  if (c.N > 0) {
+    const int rc = invoke(hcspmm_forward_softmax_typed,
+                          std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), feature_dtype(input), b.data_ptr<float>(),
+                                          Z.data_ptr(), c.D, sp[0], sp[1], c.D),
+                          c.graph(), c.ws());
+    check_rc(rc, "forward_softmax16");
+  }
+  return {Z, out[0], out[1]};
+}
+
+// Its gradient with respect to X (hcspmm_softmax_backward_typed) on the graph the backward walks: grad_Z and Z contiguous [rows, D]
+// of the input's 16-bit type, LSE contiguous float32 [rows, D], input the 16-bit [num_nodes, D] view the forward gathered -> float32
+torch::Tensor spmm_softmax_backward16(torch::Tensor grad_Z, torch::Tensor Z, torch::Tensor LSE, torch::Tensor input,
+                                      pybind11::object beta, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                      torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                      torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr) {
+  check_softmax16(input, "input");
+  check_softmax16(grad_Z, "grad_Z");
+  check_softmax16(Z, "Z");
+  CHECK_INPUT(LSE);
+  TORCH_CHECK(grad_Z.scalar_type() == input.scalar_type() && Z.scalar_type() == input.scalar_type(),
+              "grad_Z, Z and the input must have one dtype, got ", grad_Z.scalar_type(), ", ", Z.scalar_type(), " and ",
+              input.scalar_type());
+  const int64_t n = nodePointer.size(0) - 1, D = input.size(1);
+  TORCH_CHECK(input.size(0) == n, "input has ", input.size(0), " rows but the walked graph has ", n, " nodes");
+  TORCH_CHECK(grad_Z.is_contiguous() && Z.is_contiguous() && grad_Z.size(1) == D && Z.sizes() == grad_Z.sizes(),
+              "grad_Z and Z must be contiguous [rows, D] tensors with D = ", D, ", got ", grad_Z.sizes(), " and ", Z.sizes());
+  TORCH_CHECK(LSE.scalar_type() == torch::kFloat && LSE.sizes() == grad_Z.sizes(), "LSE must be a float32 tensor of grad_Z's shape");
+  TORCH_CHECK(grad_Z.device() == input.device() && Z.device() == input.device() && LSE.device() == input.device(),
+              "grad_Z, Z and LSE must be on the device of the input");
+  CallOptions o(CallOptions::kTyped);
+  o.rect = true;  // grad_Z's rows are indexed by the walked graph's column ids
+  PlannedCall c(&grad_Z, grad_Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  TORCH_CHECK(c.E == 0 || grad_Z.size(0) > 0, "grad_Z has no rows but the walked graph has ", c.E, " entries");
+  const torch::Tensor b = beta_vector(beta, D, input);
+  auto grad_X = torch::empty({n, D}, input.options().dtype(torch::kFloat));
+  if (n == 0) return grad_X;
+  const bool any = grad_Z.numel() > 0;
+  const int rc = invoke(hcspmm_softmax_backward_typed,
+                        std::make_tuple(any ? grad_Z.data_ptr() : nullptr, any ? Z.data_ptr() : nullptr, D,
+                                        any ? LSE.data_ptr<float>() : nullptr, D, grad_Z.size(0), input.data_ptr(), input.stride(0),
+                                        feature_dtype(input), b.data_ptr<float>(), grad_X.data_ptr<float>(), D),
+                        c.graph(), c.ws());
+  check_rc(rc, "softmax_backward16");
   return grad_X;
 }
 
@@ -1517,6 +1607,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_backward", &spmm_softmax_backward,
         "gradient of forward_softmax with respect to X -> grad_X, on the graph the backward walks (A^T's tensors, or A's own for a "
         "symmetric pattern); the weights are recomputed from M and L (gfx950)");
+  m.def("forward_softmax16", &spmm_forward_softmax16,
+        "softmax aggregation on float16 / bfloat16 features in one gather pass -> (Z16, LSE, Var): Z rounded once to the input's type, "
+        "the float32 log-sum-exp and softmax-weighted variance that `stats` names, None otherwise (gfx950)",
+        pybind11::arg("input"), pybind11::arg("beta"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("stats") = pybind11::make_tuple("lse"));
+  m.def("softmax_backward16", &spmm_softmax_backward16,
+        "gradient of forward_softmax16 with respect to X -> float32 grad_X, on the graph the backward walks; the weights are "
+        "recomputed from LSE, 16-bit grad_Z and Z are gathered (gfx950)");
   m.def("forward_gated", &spmm_forward_gated,
         "gated neighbour aggregation in one gather pass -> (Z_gate, Z_dgate): Z_gate[i] = sum_j sigmoid(P[i] + Q[j]) * V[j], "
         "Z_dgate the same sum with the sigmoid's derivative; an output `outputs` leaves out is None (gfx950)",

@@ -37,7 +37,7 @@ extern "C" {
  * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
  * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
- * hcspmm_forward_extremum_typed (round 25).
+ * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -570,6 +570,43 @@ int hcspmm_softmax_backward(const float* grad_Z_d, const float* Z_d, const float
                             const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
                             const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
                             int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
+/* hcspmm_forward_softmax_typed: the aggregation on fp16 / bf16 features (dtype = HCSPMM_DTYPE_F16 / _BF16; X_d and Z_d of that
+ * type, kernels of their own: spmm_softmax16.hip).  With x_e = widen(X[column_index[e]][d]) (exact), s_e = fl32(beta[d] * x_e) and
+ * the online state (m, l, a, q) of hcspmm_forward_softmax, arithmetic unchanged:
+ *   Z[r][d]   = zf = a / l in fp32, rounded ONCE to dtype (nearest even)
+ *   LSE[r][d] = fl32(m + ln l): the log-sum-exp of the row's s_e -- the ONE statistic the backward needs
+ *   Var[r][d] = fl32(fl32(q / l) - fl32(zf zf)): the softmax-weighted variance, from the unrounded zf.  The gradient of beta is
+ *               sum_i grad_Z[i][d] Var[i][d]; Q - Z^2 with a 16-bit Z cancels badly.
+ * Rows without entries get Z = +0, LSE = -inf, Var = +0.  LSE_d / Var_d (fp32, row stride ld_stat) may each be NULL and are then
+ * not written; without Var_d the kernels keep no q state.  Where the summation order is hcspmm_forward_softmax's, Z is its Z on a
+ * widened copy of X rounded once.  ldx / ldz count elements.  Every EVEN embedding_dim >= 4 with even ldx / ldz and 4-byte aligned
+ * X_d / Z_d is served (rows on the dword grid); an odd width or stride, embedding_dim == 2, a misaligned base, ld_stat <
+ * embedding_dim with a statistic set, a dtype other than F16 / BF16 (fp32 is refused: its outputs differ) and every argument, plan
+ * and workspace error of hcspmm_forward_softmax are HCSPMM_EINVAL (or that call's code) before any device call -- pad to an even
+ * width.  workspace_d >= hcspmm_softmax_workspace_bytes() (the partial slots stay four fp32 areas).  num_nodes == 0 returns
+ * HCSPMM_OK without a launch.  Asynchronous on `stream`, allocates nothing, capturable.
+ *
+ * hcspmm_softmax_backward_typed: the gradient with respect to X (fp32 grad_X_d) on the graph the backward walks, from 16-bit
+ * grad_Z_d and Z_d ([src_rows] rows of stride ld_in elements), the fp32 LSE_d (stride ld_stat) and the 16-bit X_d (stride ldx):
+ *   grad_X[j][d] = sum over the entries (j, i) of row j of
+ *                  exp(fl32(beta[d] x_j) - LSE[i][d]) * g_i * (1 + beta[d] (x_j - z_i))
+ * x_j, g_i, z_i the widened elements of X, grad_Z, Z (one dtype for all three).  8 gathered bytes per column against the fp32
+ * call's 16 (softmax_aggr_grad16.hip).  The exponent is <= 0 on a true transpose.  A plain fp32 sum in hcspmm_forward_weighted's
+ * order; workspace_d >= hcspmm_workspace_bytes().  Shape rules and refusals as above, for every 16-bit operand.
+ * hcspmm_forward_softmax and hcspmm_softmax_backward keep refusing the 16-bit types. */
+int hcspmm_forward_softmax_typed(const void* X_d, int64_t x_rows, int64_t ldx, int dtype, const float* beta_d, void* Z_d, int64_t ldz,
+                                 float* LSE_d, float* Var_d, int64_t ld_stat, const int32_t* row_pointers_d,
+                                 const int32_t* column_index_d, const int32_t* blockPartition_d, const int32_t* edgeToColumn_d,
+                                 const int32_t* edgeToRow_d, const int32_t* hybrid_type_d, const int32_t* plan_d,
+                                 const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                                 void* workspace_d, size_t workspace_bytes, void* stream);
+int hcspmm_softmax_backward_typed(const void* grad_Z_d, const void* Z_d, int64_t ld_in, const float* LSE_d, int64_t ld_stat,
+                                  int64_t src_rows, const void* X_d, int64_t ldx, int dtype, const float* beta_d, float* grad_X_d,
+                                  int64_t ldgx, const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                  const int32_t* blockPartition_d, const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d,
+                                  const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
+                                  int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Gated neighbour aggregation (residual gated graph convolution, Bresson & Laurent; PyG ResGatedGraphConv): a message that
