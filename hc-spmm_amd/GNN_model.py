@@ -998,37 +998,71 @@ class MultiAggregate(torch.autograd.Function):
         return z_sum, z_sumsq, z_max, z_min
 
     @staticmethod
-    def backward(ctx, g_sum, g_sumsq, g_max, g_min):
+    def backward(ctx, *grads):
         X, arg_max, arg_min, *rest = ctx.saved_tensors
-        graph_b, index = rest[:N_GRAPH], rest[N_GRAPH]
         if not ctx.needs_input_grad[0]:
             return (None,) * (2 * N_GRAPH + 2)
-        D = X.size(1)
-        d_x = None
-        if g_sum is not None and g_sumsq is not None:
-            t = HCSPMM.forward(torch.cat((g_sum, g_sumsq), 1), *graph_b)[0]
-            d_x = t[:, :D] + 2.0 * X * t[:, D:]
-        elif g_sum is not None:
-            d_x = HCSPMM.forward(g_sum.contiguous(), *graph_b)[0]
-        elif g_sumsq is not None:
-            d_x = 2.0 * X * HCSPMM.forward(g_sumsq.contiguous(), *graph_b)[0]
-        for g, arg in ((g_max, arg_max), (g_min, arg_min)):
-            if g is not None:
-                d = HCSPMM.forward_extremum_backward(g.contiguous(), arg, index, *graph_b)
-                d_x = d if d_x is None else d_x + d
-        if d_x is None:
-            d_x = torch.zeros_like(X)
-        return (d_x,) + (None,) * (2 * N_GRAPH + 1)
+        return (_multi_backward(X, grads, arg_max, arg_min, rest[:N_GRAPH], rest[N_GRAPH]),) + (None,) * (2 * N_GRAPH + 1)
 
 
-def multi_aggregate(X, graph, directed=False):
+def _multi_backward(X, grads, arg_max, arg_min, graph_b, index):
+    """dX of MultiAggregate from float32 X and the four output gradients (None: that output was not used, and costs no launch)"""
+    g_sum, g_sumsq, g_max, g_min = grads
+    D = X.size(1)
+    d_x = None
+    if g_sum is not None and g_sumsq is not None:
+        t = HCSPMM.forward(torch.cat((g_sum, g_sumsq), 1), *graph_b)[0]
+        d_x = t[:, :D] + 2.0 * X * t[:, D:]
+    elif g_sum is not None:
+        d_x = HCSPMM.forward(g_sum.contiguous(), *graph_b)[0]
+    elif g_sumsq is not None:
+        d_x = 2.0 * X * HCSPMM.forward(g_sumsq.contiguous(), *graph_b)[0]
+    for g, arg in ((g_max, arg_max), (g_min, arg_min)):
+        if g is not None:
+            d = HCSPMM.forward_extremum_backward(g.contiguous(), arg, index, *graph_b)
+            d_x = d if d_x is None else d_x + d
+    return torch.zeros_like(X) if d_x is None else d_x
+
+
+class MultiAggregate16(torch.autograd.Function):
+    """MultiAggregate on a float16 / bfloat16 X (HCSPMM.forward_multi16: half the gathered bytes): Z_sum and Z_sumsq float32,
+    Z_max and Z_min in X's dtype.  What is saved is X16 and the two args.  The backward is MultiAggregate's composition on the
+    fp32 launches, over the output gradients and X widened exactly, and its total is rounded once to X's dtype; an output the
+    layer does not use costs no launch.  tail as for MultiAggregate."""
+
+    @staticmethod
+    def forward(ctx, X, *tail):
+        X = X.contiguous()
+        z_sum, z_sumsq, z_max, z_min, arg_max, arg_min = HCSPMM.forward_multi16(X, *tail[:N_GRAPH])
+        ctx.save_for_backward(X, arg_max, arg_min, *tail[N_GRAPH:])
+        ctx.set_materialize_grads(False)
+        return z_sum, z_sumsq, z_max, z_min
+
+    @staticmethod
+    def backward(ctx, *grads):
+        X, arg_max, arg_min, *rest = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * (2 * N_GRAPH + 2)
+        grads = [None if g is None else g.float() for g in grads]
+        d_x = _multi_backward(X.float(), grads, arg_max, arg_min, rest[:N_GRAPH], rest[N_GRAPH])
+        return (d_x.to(X.dtype),) + (None,) * (2 * N_GRAPH + 1)
+
+
+def multi_aggregate(X, graph, directed=False, activation_dtype=None):
     """(sum, sum of squares, max, min) over each row's neighbours from one gather pass, with autograd for X (float32 [N, D]);
     graph = the eight graph tensors, whose pattern must be symmetric (checked before any launch: the backward walks A^T)
-    unless directed=True: the backward then runs on transposed_graph(graph).  Rows without entries give 0 in all four."""
+    unless directed=True: the backward then runs on transposed_graph(graph).  Rows without entries give 0 in all four.
+    activation_dtype = torch.bfloat16 / torch.float16: X is taken in that dtype (an fp32 X is rounded once) and the 16-bit
+    kernels run (MultiAggregate16): float32 sums, max / min in that dtype; even D >= 4.  A 16-bit X selects them as well."""
+    if activation_dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+    if activation_dtype is not None:
+        X = X.to(activation_dtype)
+    fn = MultiAggregate16 if X.dtype in (torch.bfloat16, torch.float16) else MultiAggregate
     if directed:
-        return MultiAggregate.apply(X, *graph, *transposed_graph(graph))
+        return fn.apply(X, *graph, *transposed_graph(graph))
     perm32 = transpose_permutation_i32(graph[0], graph[1])
-    return MultiAggregate.apply(X, *graph, *graph, perm32)
+    return fn.apply(X, *graph, *graph, perm32)
 
 
 class PNAConv(torch.nn.Module):
@@ -1039,25 +1073,37 @@ class PNAConv(torch.nn.Module):
     avg_log_deg or, when that is None, the mean of log(deg + 1) over the graph, computed once per row_pointers tensor and kept
     on the device (no host synchronisation, so the layer captures into a HIP graph without a warm-up).  Both products run on
     _Update.  _Conv's call signature, so that Net builds it; edge_weight is refused.  The pattern must be
-    symmetric unless directed=True (the backward then runs on transposed_graph)."""
+    symmetric unless directed=True (the backward then runs on transposed_graph).
+    activation_dtype = torch.bfloat16 / torch.float16 (_Conv's convention): X is taken in that dtype (an fp32 X is rounded once
+    on entry) and aggregated by the 16-bit one-pass kernels (MultiAggregate16); mean, std and the scalers are computed in fp32
+    from the fp32 sums, S is rounded once to that dtype, both products run on _Update16 and the layer returns that dtype; the
+    parameters and their gradients stay fp32.  Even widths."""
 
     AGGREGATORS = ("mean", "min", "max", "std")
     SCALERS = ("identity", "amplification", "attenuation")
 
     def __init__(self, input_dim, output_dim, aggregators=("mean", "min", "max", "std"),
-                 scalers=("identity", "amplification", "attenuation"), avg_log_deg=None, directed=False):
+                 scalers=("identity", "amplification", "attenuation"), avg_log_deg=None, directed=False, activation_dtype=None):
         super().__init__()
         aggregators, scalers = tuple(aggregators), tuple(scalers)
         for names, known, what in ((aggregators, self.AGGREGATORS, "aggregators"), (scalers, self.SCALERS, "scalers")):
             if not names or any(n not in known for n in names):
                 raise ValueError("PNAConv %s must be among %s, got %r" % (what, ", ".join(repr(k) for k in known), names))
-        self.directed = bool(directed)
+        self.directed, self.activation_dtype = bool(directed), activation_dtype
         self.aggregators, self.scalers = aggregators, scalers
         self.avg_log_deg = None if avg_log_deg is None else float(avg_log_deg)
         self.weights_root = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self.weights_neigh = torch.nn.Parameter(torch.empty(len(scalers) * len(aggregators) * input_dim, output_dim))
         self._degrees = None  # (row_pointers, deg [N, 1], log(deg + 1) [N, 1], delta) of the last graph
+        self._check_activation_dtype()
         self.reset_parameters()
+
+    def _check_activation_dtype(self):
+        if self.activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (self.activation_dtype,))
+        if self.activation_dtype is not None and (self.weights_root.size(0) % 2 or self.weights_root.size(1) % 2):
+            raise ValueError("activation_dtype needs even widths (16-bit rows on the dword grid), got %d -> %d"
+                             % tuple(self.weights_root.shape))
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.weights_root.size(1))
@@ -1103,6 +1149,12 @@ class PNAConv(torch.nn.Module):
         if edge_weight is not None:
             raise ValueError("PNAConv aggregates with its own aggregators: edge_weight is not accepted")
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
+        if self.activation_dtype is not None:
+            self._check_activation_dtype()  # (the attribute may have been set after construction)
+            X = X.to(self.activation_dtype)
+            z_sum, z_sumsq, z_max, z_min = multi_aggregate(X, graph, self.directed)
+            S = self.scaled_aggregates(z_sum, z_sumsq, z_max.float(), z_min.float(), row_pointers).to(self.activation_dtype)
+            return _Update16.apply(X, self.weights_root) + _Update16.apply(S, self.weights_neigh)
         S = self.scaled_aggregates(*multi_aggregate(X, graph, self.directed), row_pointers)
         return _Update.apply(X, self.weights_root) + _Update.apply(S, self.weights_neigh)
 

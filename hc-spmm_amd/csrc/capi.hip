@@ -663,6 +663,51 @@ extern "C" int hcspmm_forward_multi(const void* X, int64_t x_rows, int64_t ldx, 
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// The same pass with `dtype` honoured (fp32: the call above; fp16 / bf16: spmm_multi16.hip, rows on the dword grid, fp32 sums with
+// their own stride, extrema of X's type, the fp32 unit's six partial areas, 64-column panels).
+extern "C" int hcspmm_forward_multi_typed(const void* X, int64_t x_rows, int64_t ldx, int dtype, float* Z_sum, float* Z_sumsq,
+                                          int64_t ld_sum, void* Z_max, void* Z_min, int64_t ldz, int32_t* arg_max, int32_t* arg_min,
+                                          int64_t ldarg, const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                          const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                          const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                          void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32) {
+    if (ld_sum != ldz) return HCSPMM_EINVAL;
+    return hcspmm_forward_multi(X, x_rows, ldx, dtype, Z_sum, Z_sumsq, reinterpret_cast<float*>(Z_max), reinterpret_cast<float*>(Z_min),
+                                ldz, arg_max, arg_min, ldarg, rowptr, col, blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d,
+                                ph, N, E, D, workspace, workspace_bytes, stream_v);
+  }
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D || ld_sum < D) return HCSPMM_EINVAL;
+  if (!Z_sum && !Z_sumsq && !Z_max && !Z_min) return HCSPMM_EINVAL;
+  if ((arg_max || arg_min) && ldarg < D) return HCSPMM_EINVAL;
+  // rows on the dword grid: an even width of at least 4 columns, even 16-bit strides, 4-byte aligned 16-bit bases
+  if (D < 4 || ((D | ldx | ldz) & 1) != 0 || !aligned(X, 4) || !aligned(Z_max, 4) || !aligned(Z_min, 4)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::M16Args m{};
+  // workspace: the fp32 unit's six areas; the features' type decides the panel width
+  const int rc = bind_graph(m.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 6, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (m.p.plan) {
+    m.area = hcspmm_workspace_bytes(ph, D) / sizeof(float);
+    m.segment_len = ph->segment_len;
+  }
+  set_operands(m.p, X, nullptr, ldx, ldz);
+  m.rowptr = rowptr;
+  m.zsum = Z_sum;
+  m.zsumsq = Z_sumsq;
+  m.ldsum = (size_t)ld_sum;
+  m.zmax = Z_max;
+  m.zmin = Z_min;
+  m.amax = arg_max;
+  m.amin = arg_min;
+  m.ldarg = (size_t)ldarg;
+  const hipError_t e = hcspmm::launch_multi16(m, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" size_t hcspmm_softmax_workspace_bytes(const hcspmm_plan_header* ph, int D) { return 4 * hcspmm_workspace_bytes(ph, D); }
 
 // Per-channel softmax aggregation (spmm_softmax.hip): the plan and checks of hcspmm_forward_multi, Z required, three nullable

@@ -330,6 +330,23 @@ struct MArgs {
 };
 // vec: 4 (D >= 4), 2 or 1, as pick_vec gives for fp32
 hipError_t launch_multi_f32(const MArgs& a, int vec, hipStream_t stream);
+// The same pass over fp16 / bf16 features (spmm_multi16.hip; the 16-bit dtypes of hcspmm_forward_multi_typed): p.X holds 16-bit
+// elements on the dword grid (even D >= 4, even ldx, 4-byte aligned base), p.Z is unused.  zsum / zsumsq are fp32 with row stride
+// ldsum; zmax / zmin hold X's 16-bit type with row stride p.ldz (even, 4-byte aligned bases); the args, the six partial areas and
+// every other field are launch_multi_f32's.  The unit picks its own lanes: 8 elements from 32 columns per panel on, 4 below.
+struct M16Args {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  float *zsum, *zsumsq;
+  size_t ldsum;
+  void *zmax, *zmin;
+  int *amax, *amin;
+  size_t ldarg;
+  size_t area;        // floats per workspace area
+};
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_multi16(const M16Args& a, int dtype, hipStream_t stream);
 
 // Per-channel softmax aggregation (spmm_softmax.hip; include/hcspmm.h hcspmm_forward_softmax), fp32.  p as for launch_multi_f32
 // with p.Z unused: the outputs below share the row stride p.ldz, z is required and a null m / l / q is not written.

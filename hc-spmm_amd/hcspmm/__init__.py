@@ -29,7 +29,7 @@ __all__ = [
     "gatv2_scores", "gatv2_scores_backward",
     "transpose_graph", "transpose_graph_device", "sample_row_pointers", "sample_neighbors", "plan_free_graph",
     "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
-    "forward_max", "forward_min", "forward_extremum_backward", "forward_multi",
+    "forward_max", "forward_min", "forward_extremum_backward", "forward_multi", "forward_multi16",
     "forward_softmax", "softmax_backward", "forward_softmax16", "softmax_backward16", "forward_gated",
     "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
@@ -783,6 +783,38 @@ def forward_multi(X, row_pointers, column_index, blockPartition, edgeToColumn, e
     with c:
         check(lib().hcspmm_forward_multi(_ptr(X), X.size(0), X.stride(0), 0, *(_ptr(z) if z is not None else null for z in Z), D,
                                          *(_ptr(a) if a is not None else null for a in args), D, *c.graph, *c.ws))
+    return Z + args
+
+
+def forward_multi16(X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                    aggregates=MULTI_AGGREGATES, return_arg=True):
+    """forward_multi on a float16 / bfloat16 X in one gather pass at half the gathered bytes -> [Z_sum, Z_sumsq, Z_max, Z_min,
+    arg_max, arg_min] (hcspmm.h hcspmm_forward_multi_typed): the sums are float32 (sums of the exactly widened values and of their
+    exact squares), Z_max / Z_min have X's dtype and hold the winner's own 16 bits, the args are forward_max's / forward_min's on
+    the same X.  None rules as forward_multi.  Serves even widths of at least 4 with an even row stride and a 4-byte aligned
+    view: pad anything else to an even width."""
+    want = _multi_wanted(aggregates)
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    if not X.is_cuda:
+        raise RuntimeError("input must be a CUDA tensor")
+    if X.dtype not in (torch.float16, torch.bfloat16) or X.dim() != 2 or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise RuntimeError("16-bit multi aggregation takes a 2-D float16 / bfloat16 view with unit inner stride "
+                           "(float32 features: forward_multi)")
+    N, D = row_pointers.size(0) - 1, X.size(1)
+    if D < 4 or D % 2 or X.stride(0) % 2 or X.data_ptr() % 4:
+        raise RuntimeError("16-bit multi aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: "
+                           "pad the input to an even width")
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, X.size(0),
+                      X.device, ws_fn=_ws_bytes_multi)
+    Z = [torch.empty((N, D), dtype=torch.float32 if k < 2 else X.dtype, device=X.device) if w else None for k, w in enumerate(want)]
+    args = [torch.empty((N, D), dtype=torch.int32, device=X.device) if (w and return_arg) else None for w in want[2:]]
+    if N == 0:
+        return Z + args
+    null = ctypes.c_void_p(0)
+    p = [_ptr(t) if t is not None else null for t in Z + args]
+    with c:
+        check(lib().hcspmm_forward_multi_typed(_ptr(X), X.size(0), X.stride(0), _DTYPES[X.dtype], p[0], p[1], D, p[2], p[3], D, p[4],
+                                               p[5], D, *c.graph, *c.ws))
     return Z + args
 
 

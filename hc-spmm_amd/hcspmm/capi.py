@@ -110,6 +110,8 @@ SYMBOLS = {
     "hcspmm_multi_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_multi": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _hp, _i64, _i64, _int, _vp, _sz, _vp]),
+    "hcspmm_forward_multi_typed": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_softmax_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_softmax": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64,
                                       _i64, _int, _vp, _sz, _vp]),

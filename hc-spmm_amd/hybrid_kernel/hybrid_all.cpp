@@ -498,6 +498,57 @@ std::vector<c10::optional<torch::Tensor>> spmm_forward_multi(torch::Tensor input
   return out;
 }
 
+// The same pass on float16 / bfloat16 X (hcspmm_forward_multi_typed): float32 sums, extrema of X's type, forward_max's 16-bit
+// input contract
+std::vector<c10::optional<torch::Tensor>> spmm_forward_multi16(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                               torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                                               torch::Tensor edgeToRow, torch::Tensor hybrid_type,
+                                                               torch::Tensor row_nzr, torch::Tensor col_nzr,
+                                                               const std::vector<std::string>& aggregates, bool return_arg) {
+  static const char* const kNames[4] = {"sum", "sumsq", "max", "min"};
+  bool want[4] = {false, false, false, false};
+  for (const std::string& a : aggregates) {
+    int k = 0;
+    while (k < 4 && a != kNames[k]) ++k;
+    if (k == 4) throw pybind11::value_error("aggregates must be among 'sum', 'sumsq', 'max', 'min', got '" + a + "'");
+    want[k] = true;
+  }
+  if (aggregates.empty()) throw pybind11::value_error("aggregates must name at least one of 'sum', 'sumsq', 'max', 'min'");
+  CHECK_CUDA(input);
+  const int dtype = feature_dtype(input);
+  TORCH_CHECK((dtype == HCSPMM_DTYPE_F16 || dtype == HCSPMM_DTYPE_BF16) && input.dim() == 2 && input.stride(1) == 1 &&
+                  input.stride(0) >= input.size(1),
+              "16-bit multi aggregation takes a 2-D float16 / bfloat16 view with unit inner stride (float32 features: forward_multi)");
+  TORCH_CHECK(input.size(1) >= 4 && rows16(input),
+              "16-bit multi aggregation serves even widths >= 4 with even row strides and 4-byte aligned views: pad the input to an "
+              "even width");
+  CallOptions o(CallOptions::kTyped);
+  o.rect = o.strided = true;
+  o.workspace_bytes = hcspmm_multi_workspace_bytes;  // the fp32 unit's six arrays per partial slot of a split row
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  std::vector<c10::optional<torch::Tensor>> out(6);
+  void* z[4] = {nullptr, nullptr, nullptr, nullptr};
+  int* arg[2] = {nullptr, nullptr};
+  for (int k = 0; k < 4; ++k) {
+    if (!want[k]) continue;
+    auto t = torch::empty({c.N, (int64_t)c.D}, k < 2 ? input.options().dtype(torch::kFloat) : input.options());
+    z[k] = c.N > 0 ? t.data_ptr() : nullptr;
+    out[k] = t;
+    if (k >= 2 && return_arg) {
+      auto a = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(torch::kInt));
+      arg[k - 2] = mptr(a);
+      out[k + 2] = a;
+    }
+  }
+  if (c.N == 0) return out;
+  const int rc = invoke(hcspmm_forward_multi_typed,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), dtype, static_cast<float*>(z[0]),
+                                        static_cast<float*>(z[1]), c.D, z[2], z[3], c.D, arg[0], arg[1], c.D),
+                        c.graph(), c.ws());
+  check_rc(rc, "forward_multi16");
+  return out;
+}
+
 // beta of the softmax aggregation as a float32 [D] vector on the input's device: a Python number, or a float32 tensor of 1 or D
 // elements on that device, broadcast there (no host synchronisation: the call captures into a HIP graph)
 torch::Tensor beta_vector(const pybind11::object& beta, int64_t D, const torch::Tensor& input) {
@@ -1593,6 +1644,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward_multi", &spmm_forward_multi,
         "sum, sum of squares, max and min over each row's neighbours in one gather pass -> [Z_sum, Z_sumsq, Z_max, Z_min, arg_max, "
         "arg_min], None for what `aggregates` / return_arg leave out; max / min / args as forward_max (gfx950)",
+        pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
+        pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
+        pybind11::arg("col_nzr"), pybind11::arg("aggregates") = std::vector<std::string>{"sum", "sumsq", "max", "min"},
+        pybind11::arg("return_arg") = true);
+  m.def("forward_multi16", &spmm_forward_multi16,
+        "forward_multi on float16 / bfloat16 features at half the gathered bytes -> [Z_sum f32, Z_sumsq f32, Z_max, Z_min (X's "
+        "dtype), arg_max, arg_min], None for what `aggregates` / return_arg leave out (gfx950)",
         pybind11::arg("input"), pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("blockPartition"),
         pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"), pybind11::arg("row_nzr"),
         pybind11::arg("col_nzr"), pybind11::arg("aggregates") = std::vector<std::string>{"sum", "sumsq", "max", "min"},

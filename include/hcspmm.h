@@ -37,7 +37,8 @@ extern "C" {
  * hcspmm_softmax_backward (round 17); hcspmm_sample_workspace_bytes, hcspmm_sample_row_pointers_device,
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
  * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
- * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26).
+ * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26);
+ * hcspmm_forward_multi_typed (round 27).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -530,6 +531,25 @@ int hcspmm_forward_multi(const void* X_d, int64_t x_rows, int64_t ldx, int dtype
                          const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d, const int32_t* hybrid_type_d,
                          const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges,
                          int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream);
+/* hcspmm_forward_multi_typed: the same pass with `dtype` honoured.
+ *   HCSPMM_DTYPE_F32           forwards to hcspmm_forward_multi (Z_max_d / Z_min_d are float*; ld_sum == ldz required)
+ *   HCSPMM_DTYPE_F16 / _BF16   every guarantee above on the elements widened to fp32 (exact).  Z_sum_d / Z_sumsq_d stay FP32 with
+ *                              their own row stride ld_sum (an fp16 sum of squares overflows on any hub, and sumsq / deg - mean^2
+ *                              cancels on a 16-bit mean); the square of a 16-bit value is exact in fp32 wherever it is
+ *                              representable.  Z_max_d / Z_min_d have X_d's type with row stride ldz and hold the winning entry's
+ *                              own 16 bits, the args are hcspmm_forward_extremum_typed's.  Half the gathered bytes (kernels of their
+ *                              own, spmm_multi16.hip); the column panels of a planned call are 64 columns wide.
+ * The 16-bit dtypes need an even embedding_dim >= 4, even ldx / ldz and 4-byte aligned X_d / Z_max_d / Z_min_d; an odd width or
+ * stride, embedding_dim == 2, a misaligned base, a stride below embedding_dim, all four Z_* NULL or ldarg < embedding_dim with
+ * an arg set is HCSPMM_EINVAL before any device call.  workspace_d >= hcspmm_multi_workspace_bytes() (the partial slots are fp32 /
+ * int32 whatever the features are).  num_nodes == 0 returns HCSPMM_OK without a launch.  Asynchronous on `stream`. */
+int hcspmm_forward_multi_typed(const void* X_d, int64_t x_rows, int64_t ldx, int dtype, float* Z_sum_d, float* Z_sumsq_d,
+                               int64_t ld_sum, void* Z_max_d, void* Z_min_d, int64_t ldz, int32_t* arg_max_d, int32_t* arg_min_d,
+                               int64_t ldarg, const int32_t* row_pointers_d, const int32_t* column_index_d,
+                               const int32_t* blockPartition_d, const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d,
+                               const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
+                               int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-channel softmax aggregation of each row's neighbours in ONE gather pass (DeeperGCN / GENConv, PyG SoftmaxAggregation).
