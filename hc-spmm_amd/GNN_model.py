@@ -1472,32 +1472,93 @@ class EdgeMessageAggregate(torch.autograd.Function):
         return (d_x, d_f, None) + (None,) * len(tail)
 
 
-def edge_message_aggregate(X, F, graph, op="add_relu", directed=False):
+class EdgeMessageAggregate16(torch.autograd.Function):
+    """EdgeMessageAggregate with X and F read in float16 / bfloat16 (HCSPMM.forward_edge_messages / edge_messages_grad on 16-bit
+    views: half the bytes of the gathered rows and of both [E, D] streams, float32 sums): Z = f(r(X), r(F)) with r the rounding to
+    `dtype`, and the gradients of f at the rounded operands, straight through the casts.  The forward casts what is not 16-bit
+    already and saves the 16-bit operands; the backward casts dZ once:
+      "mul":      dF = grad(r(dZ), r(X)),   dX = forward("mul", X := r(dZ), r(F), index)
+      "add_relu": dF = grad(r(dZ), r(X), r(F)) -- r(dZ)'s own bits or 0 --,   dX = forward("copy", F := dF, index)
+    dX comes back float32 (a sum: not rounded), dF in `dtype`; both are cast to their operand's dtype where that differs."""
+
+    @staticmethod
+    def forward(ctx, X, F, op, dtype, *tail):
+        X16 = None if X is None else X.to(dtype).contiguous()
+        F16 = F.to(dtype).contiguous()
+        ctx.op, ctx.x_dtype, ctx.f_dtype = op, None if X is None else X.dtype, F.dtype
+        ctx.save_for_backward(X16, F16, *tail)
+        return HCSPMM.forward_edge_messages(X16, F16, *tail[:N_GRAPH], op)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        X16, F16, *tail = ctx.saved_tensors
+        graph, graph_b, index = tail[:N_GRAPH], tail[N_GRAPH:2 * N_GRAPH], tail[2 * N_GRAPH]
+        need_x, need_f = ctx.needs_input_grad[0] and ctx.op != "copy", ctx.needs_input_grad[1]
+        d_x = d_f = None
+        if need_x or need_f:
+            d16 = d_out.to(F16.dtype).contiguous()
+            if ctx.op == "mul":
+                if need_f:
+                    d_f = HCSPMM.edge_messages_grad(d16, X16, None, graph[0], graph[1], "mul")
+                if need_x:
+                    d_x = HCSPMM.forward_edge_messages(d16, F16, *graph_b, "mul", index)[0]
+            else:  # one pass serves both: dX sums dF over A^T's rows
+                d_f = HCSPMM.edge_messages_grad(d16, X16, F16, graph[0], graph[1], ctx.op)
+                if need_x:
+                    d_x = HCSPMM.forward_edge_messages(None, d_f, *graph_b, "copy", index)[0]
+                if not need_f:
+                    d_f = None
+        if d_x is not None:
+            d_x = d_x.to(ctx.x_dtype)
+        if d_f is not None:
+            d_f = d_f.to(ctx.f_dtype)
+        return (d_x, d_f, None, None) + (None,) * len(tail)
+
+
+def edge_message_aggregate(X, F, graph, op="add_relu", directed=False, gather_dtype=None):
     """Sum over each row's entries of a message of the neighbour's row and the entry's own feature vector, with autograd for
-    X [N, D] and F [E, D] (float32; F aligned with column_index): op "mul" X[j] * F[e] (continuous-filter convolutions),
+    X [N, D] and F [E, D] (F aligned with column_index): op "mul" X[j] * F[e] (continuous-filter convolutions),
     "add_relu" relu(X[j] + F[e]) (GINE), "copy" F[e] (X may be None).  graph = the eight graph tensors, whose pattern must be
     symmetric (checked before any launch: the backward walks A^T) unless directed=True: the backward then runs on
-    transposed_graph(graph).  Rows without entries give 0."""
+    transposed_graph(graph).  Rows without entries give 0.
+    gather_dtype=torch.bfloat16 / torch.float16 (or a 16-bit X / F): the operands (and, in the backward, dZ) are rounded to that
+    type once and read in it -- half the bytes of X's gathered rows, of F and of dF; the sums, Z and dX stay float32, and the
+    gradients are those of the function of the rounded operands (EdgeMessageAggregate16).  Even widths of at least 4."""
     if op not in ("mul", "add_relu", "copy"):
         raise ValueError("op must be 'mul', 'add_relu' or 'copy', got %r" % (op,))
+    if gather_dtype not in GATHER_DTYPES:
+        raise ValueError("gather_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (gather_dtype,))
     if F.dim() != 2 or F.size(0) != graph[1].numel():
         raise ValueError("F must hold one row per stored entry: [%d, D], got %s" % (graph[1].numel(), tuple(F.shape)))
+    if gather_dtype is None:
+        held = {t.dtype for t in (X, F) if t is not None and t.dtype in GATHER_DTYPES}
+        if len(held) > 1:
+            raise ValueError("X and F hold different 16-bit types: pass gather_dtype")
+        gather_dtype = held.pop() if held else None
+    if gather_dtype is not None and (F.size(1) % 2 or F.size(1) < 4):
+        raise ValueError("gather_dtype needs an even width of at least 4 (16-bit rows sit on a 4-byte grid), got %d" % F.size(1))
+    fn = EdgeMessageAggregate.apply if gather_dtype is None else (lambda *a: EdgeMessageAggregate16.apply(*a[:3], gather_dtype, *a[3:]))
     if directed:
         gt = transposed_graph(graph)
-        return EdgeMessageAggregate.apply(X, F, op, *graph, *gt)
+        return fn(X, F, op, *graph, *gt)
     perm32 = transpose_permutation_i32(graph[0], graph[1])
-    return EdgeMessageAggregate.apply(X, F, op, *graph, *graph, perm32)
+    return fn(X, F, op, *graph, *graph, perm32)
 
 
 class GINEConv(torch.nn.Module):
     """GIN with edge attributes (GINE):  out = ((1 + eps) X + sum_j relu(X_j + edge_attr W_e)) W, the sum one
     edge_message_aggregate over the projected edge attributes, both products on _Update.  edge_attr is float32 [E, edge_dim],
     aligned with column_index; W_e [edge_dim, input_dim]; eps is learnt with train_eps=True.  _Conv's call signature with
-    edge_attr in the place of edge_weight.  The pattern must be symmetric unless directed=True."""
+    edge_attr in the place of edge_weight.  The pattern must be symmetric unless directed=True.
+    activation_dtype = torch.bfloat16 / torch.float16 (_Conv's convention): X is taken in that dtype (an fp32 X is rounded once),
+    edge_attr is cast, F = edge_attr W_e comes out of _Update16 in 16 bits -- no float32 [E, input_dim] tensor exists, forward or
+    backward --, the sum runs on the 16-bit edge-message kernels (float32 Z), (1 + eps) X + Z is formed in float32 and rounded once,
+    and the output product runs on _Update16: the layer returns activation_dtype.  input_dim must then be even and at least 4."""
 
-    def __init__(self, input_dim, output_dim, edge_dim, eps=0.0, train_eps=False, fixed=0, directed=False):
+    def __init__(self, input_dim, output_dim, edge_dim, eps=0.0, train_eps=False, fixed=0, directed=False, activation_dtype=None):
         super().__init__()
-        self.fixed, self.directed = fixed, bool(directed)
+        self.fixed, self.directed, self.activation_dtype = fixed, bool(directed), activation_dtype
         self.weights = torch.nn.Parameter(torch.empty(input_dim, output_dim))
         self.weights_edge = torch.nn.Parameter(torch.empty(edge_dim, input_dim))
         self.initial_eps = float(eps)
@@ -1505,7 +1566,15 @@ class GINEConv(torch.nn.Module):
             self.eps = torch.nn.Parameter(torch.empty(()))
         else:
             self.register_buffer("eps", torch.empty(()))
+        self._check_activation_dtype()
         self.reset_parameters()
+
+    def _check_activation_dtype(self):
+        if self.activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (self.activation_dtype,))
+        if self.activation_dtype is not None and (self.weights.size(0) % 2 or self.weights.size(0) < 4):
+            raise ValueError("activation_dtype needs an even input_dim of at least 4 (16-bit rows sit on a 4-byte grid), got %d"
+                             % self.weights.size(0))
 
     def reset_parameters(self):
         for p in (self.weights, self.weights_edge):
@@ -1520,5 +1589,11 @@ class GINEConv(torch.nn.Module):
         graph = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr)
         if not self.directed:
             transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
+        if self.activation_dtype is not None:
+            self._check_activation_dtype()  # (the attribute may have been set after construction, as the driver does for _Conv)
+            X = X.to(self.activation_dtype)
+            F = _Update16.apply(edge_attr.to(self.activation_dtype), self.weights_edge)
+            agg = edge_message_aggregate(X, F, graph, "add_relu", self.directed, self.activation_dtype)
+            return _Update16.apply(((1.0 + self.eps) * X.float() + agg).to(self.activation_dtype), self.weights)
         agg = edge_message_aggregate(X, _Update.apply(edge_attr, self.weights_edge), graph, "add_relu", self.directed)
         return _Update.apply((1.0 + self.eps) * X + agg, self.weights)

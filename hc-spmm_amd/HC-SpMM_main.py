@@ -68,7 +68,7 @@ def parse_args(argv=None):
     # addition: 16-bit activations end to end (GNN_model._Conv activation_dtype: 16-bit aggregation and the 16-bit update / weight
     # gradient kernels; parameters, their gradients and the loss stay fp32)
     p.add_argument("--activation-dtype", type=str, default="fp32", choices=["fp32", "bf16", "fp16"],
-                   help="--model gcn / gin with --norm sym|mean, or --model sage / pna / gen: run the layers on activations of this type")
+                   help="--model gcn / gin with --norm sym|mean, or --model sage / pna / gen / gine: run the layers on activations of this type")
     # addition: message passing over a directed graph (GNN_model.transposed_graph: the backward aggregates with A^T)
     p.add_argument("--directed", action="store_true",
                    help="the graph's pattern need not be symmetric: the layers' backward runs on the transposed graph")
@@ -287,13 +287,15 @@ def main(argv=None):
         edge_attr = torch.rand(num_edges, args.edge_dim, generator=gen).to(device)
 
         def conv_cls(input_dim, output_dim, fixed):
-            return GINEConv(input_dim, output_dim, args.edge_dim, fixed=fixed, directed=directed)
+            # 16-bit rows sit on a 4-byte grid: a layer of odd input width (raw features) keeps fp32 operands
+            return GINEConv(input_dim, output_dim, args.edge_dim, fixed=fixed, directed=directed,
+                            activation_dtype=activation_dtype if input_dim % 2 == 0 and input_dim >= 4 else None)
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight, edge_attr).to(device)
     if args.fp8:
         set_feature_storage(model, "fp8")
-    if args.activation_dtype != "fp32" and args.model not in ("sage", "pna", "gen"):  # (SAGEConv, PNAConv and GENConv took it where they were built)
+    if args.activation_dtype != "fp32" and args.model not in ("sage", "pna", "gen", "gine"):  # (those layers took it where they were built)
         if args.model not in ("gcn", "gin") or edge_weight is None:
-            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean, or --model sage, pna or gen")
+            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean, or --model sage, pna, gen or gine")
         for m in model.modules():
             if isinstance(m, (GCNConv, GINConv)):
                 m.activation_dtype = activation_dtype

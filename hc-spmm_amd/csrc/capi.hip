@@ -976,6 +976,85 @@ extern "C" int hcspmm_edge_messages_grad(const float* grad_Z, int64_t ldg, const
   return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
+// The messages on operands of one element type (fp32: the call above; fp16 / bf16: spmm_edgevec16.hip, rows on the dword grid, fp32
+// Z and partial slots, 64-column panels).
+extern "C" int hcspmm_forward_edge_messages_typed(const void* X, int64_t x_rows, int64_t ldx, const void* F, int64_t f_rows,
+                                                  int64_t ldf, int dtype, const int32_t* f_index, int op, float* Z, int64_t ldz,
+                                                  const int32_t* rowptr, const int32_t* col, const int32_t* blockPartition,
+                                                  const int32_t* edgeToColumn, const int32_t* edgeToRow, const int32_t* hybrid_type,
+                                                  const int32_t* plan_d, const hcspmm_plan_header* ph, int64_t N, int64_t E, int D,
+                                                  void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_forward_edge_messages(X, x_rows, ldx, static_cast<const float*>(F), f_rows, ldf, f_index, op, Z, ldz, rowptr, col,
+                                        blockPartition, edgeToColumn, edgeToRow, hybrid_type, plan_d, ph, N, E, D, workspace,
+                                        workspace_bytes, stream_v);
+  if (op != HCSPMM_EDGE_OP_MUL && op != HCSPMM_EDGE_OP_ADD_RELU && op != HCSPMM_EDGE_OP_COPY) return HCSPMM_EINVAL;
+  const bool reads_x = op != HCSPMM_EDGE_OP_COPY;
+  if (N < 0 || E < 0 || D <= 0 || f_rows < 0 || ldf < D || ldz < D || (reads_x && ldx < D)) return HCSPMM_EINVAL;
+  // rows on the dword grid: an even width of at least 4 columns, even strides, 4-byte aligned bases of what the op reads
+  if (D < 4 || ((D | ldf) & 1) != 0 || !aligned(F, 4) || (reads_x && ((ldx & 1) != 0 || !aligned(X, 4)))) return HCSPMM_EINVAL;
+  if (E > 0 && (!F || f_rows == 0 || (!f_index && f_rows < E))) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if ((reads_x && !X) || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || f_rows > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::EVec16Args a{};
+  // workspace: hcspmm_workspace_bytes (fp32 partial slots); the operands' type decides the panel width
+  const int rc = bind_graph(a.p, GRAPH_IN, D, reads_x ? x_rows : kNoSource, workspace, workspace_bytes, 1, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.plan) a.segment_len = ph->segment_len;
+  set_operands(a.p, reads_x ? X : nullptr, Z, ldx, ldz);
+  a.rowptr = rowptr;
+  a.op = op;
+  a.F = static_cast<const unsigned short*>(F);
+  a.ldf = (size_t)ldf;
+  a.findex = f_index;
+  const hipError_t e = hcspmm::launch_edgevec16(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+// Their gradient with respect to F on operands of one element type (fp32: the call above; fp16 / bf16: edgevec16_grad.hip, grad_F in
+// the operands' type).
+extern "C" int hcspmm_edge_messages_grad_typed(const void* grad_Z, int64_t ldg, const void* X, int64_t x_rows, int64_t ldx,
+                                               const void* F, int64_t ldf, int dtype, void* grad_F, int64_t ldgf, int op,
+                                               const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int D,
+                                               void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_edge_messages_grad(static_cast<const float*>(grad_Z), ldg, static_cast<const float*>(X), x_rows, ldx,
+                                     static_cast<const float*>(F), ldf, static_cast<float*>(grad_F), ldgf, op, rowptr, col, N, E, D,
+                                     stream_v);
+  if (op != HCSPMM_EDGE_OP_MUL && op != HCSPMM_EDGE_OP_ADD_RELU && op != HCSPMM_EDGE_OP_COPY) return HCSPMM_EINVAL;
+  const bool reads_x = op != HCSPMM_EDGE_OP_COPY, reads_f = op == HCSPMM_EDGE_OP_ADD_RELU;
+  if (N < 0 || E < 0 || D <= 0 || ldg < D || ldgf < D || (reads_x && (ldx < D || x_rows < 0)) || (reads_f && ldf < D))
+    return HCSPMM_EINVAL;
+  // every operand the op touches on the dword grid
+  if (D < 4 || ((D | ldg | ldgf) & 1) != 0 || !aligned(grad_Z, 4) || !aligned(grad_F, 4) ||
+      (reads_x && ((ldx & 1) != 0 || !aligned(X, 4))) || (reads_f && ((ldf & 1) != 0 || !aligned(F, 4))))
+    return HCSPMM_EINVAL;
+  if (!rowptr || (E > 0 && (!grad_Z || !grad_F || !col || N == 0 || (reads_x && (!X || x_rows == 0)) || (reads_f && !F))))
+    return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::EVec16GradArgs a{};
+  a.gZ = static_cast<const unsigned short*>(grad_Z);
+  a.X = static_cast<const unsigned short*>(X);
+  a.F = static_cast<const unsigned short*>(F);
+  a.gF = static_cast<unsigned short*>(grad_F);
+  a.ldg = (size_t)ldg;
+  a.ldx = (size_t)ldx;
+  a.ldf = (size_t)ldf;
+  a.ldgf = (size_t)ldgf;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.N = (int)N;
+  a.D = D;
+  a.op = op;
+  a.E = (long long)E;
+  const hipError_t e = hcspmm::launch_edgevec16_grad(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_edge_norm_device(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E, int kind,
                                        float* values_out, void* stream_v) {
   if (N < 0 || E < 0 || (kind != HCSPMM_NORM_SYM && kind != HCSPMM_NORM_MEAN)) return HCSPMM_EINVAL;

@@ -463,4 +463,34 @@ struct Gate16Args {
 // dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16; vec: 8 (D >= 32) or 4 (4 <= D < 32) elements per lane
 hipError_t launch_gate16(const Gate16Args& a, int dtype, int vec, hipStream_t stream);
 
+// The edge-feature messages on fp16 / bf16 operands (spmm_edgevec16.hip; the 16-bit dtypes of hcspmm_forward_edge_messages_typed):
+// p.X (null for the copy op) and F hold 16-bit elements on the dword grid (even D >= 4, even ldx / ldf, 4-byte aligned bases),
+// widened exactly in registers; p.Z, the partial slots and every other field are EdgeMsgArgs' -- fp32.  The unit picks its own
+// lanes: 8 elements from 32 columns on, 4 below.
+struct EVec16Args {
+  PlanArgs p;
+  const int* rowptr;  // [N + 1]
+  int segment_len;    // plan header: entries per segment of a split row
+  int op;             // HCSPMM_EDGE_OP_*
+  const unsigned short* F;  // [f_rows][ldf]
+  size_t ldf;         // in elements
+  const int* findex;  // [E], or nullptr for the direct form
+};
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_edgevec16(const EVec16Args& a, int dtype, hipStream_t stream);
+// its gradient with respect to F (edgevec16_grad.hip, hcspmm_edge_messages_grad_typed): gZ, X, F and gF all of the 16-bit type, on
+// the dword grid; mul rounds the exact fp32 product once, add_relu and copy pass gZ's own bits
+struct EVec16GradArgs {
+  const unsigned short* gZ;  // [N][ldg]
+  const unsigned short* X;   // [x_rows][ldx] (copy: unused)
+  const unsigned short* F;   // [E][ldf] (add_relu only)
+  unsigned short* gF;        // [E][ldgf]
+  size_t ldg, ldx, ldf, ldgf;
+  const int* rowptr;  // [N + 1]
+  const int* col;     // [E]
+  int N, D, op;
+  long long E;
+};
+hipError_t launch_edgevec16_grad(const EVec16GradArgs& a, int dtype, hipStream_t stream);
+
 }  // namespace hcspmm

@@ -1059,11 +1059,19 @@ def _edge_op(op):
     return EDGE_OPS[op]
 
 
-def _check_f32_view(t, name):
+def _check_edge_view(t, name, like=None):
+    """A 2-D view with unit inner stride of float32, float16 or bfloat16 -- of `like`'s dtype when one is given; the 16-bit types
+    need rows on the dword grid"""
     if not t.is_cuda:
         raise RuntimeError("%s must be a CUDA tensor" % name)
-    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
-        raise RuntimeError("%s must be a 2-D float32 view with unit inner stride" % name)
+    if t.dtype not in _DTYPES or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+        raise RuntimeError("%s must be a 2-D float32 / float16 / bfloat16 view with unit inner stride" % name)
+    if like is not None and t.dtype != like.dtype:
+        raise RuntimeError("%s must have the dtype of the other operands (all float32, all float16 or all bfloat16), got %s and %s"
+                           % (name, t.dtype, like.dtype))
+    if t.dtype != torch.float32 and (t.size(1) < 4 or t.size(1) % 2 or t.stride(0) % 2 or t.data_ptr() % 4):
+        raise RuntimeError("16-bit edge messages serve even widths >= 4 with even row strides and 4-byte aligned views: pad %s to "
+                           "an even width" % name)
 
 
 def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
@@ -1072,15 +1080,18 @@ def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edge
     [E]) or e.  op: "mul" x * f, "add_relu" relu(x + f), "copy" f (X may be None).  X [rows, D] and F [f_rows, D] are float32
     views with unit inner stride; F is read on every call.  Deterministic, no atomics (hcspmm.h hcspmm_forward_edge_messages).
     The gradient with respect to X is this call on A^T's graph with index = entry_index_t (or, on a pattern-symmetric graph,
-    the int32 transpose permutation): "mul" with X := dZ, "add_relu" as "copy" of edge_messages_grad's result."""
+    the int32 transpose permutation): "mul" with X := dZ, "add_relu" as "copy" of edge_messages_grad's result.
+    X and F may instead BOTH be float16 or both bfloat16 (hcspmm_forward_edge_messages_typed): they are widened exactly, the sums
+    are the float32 call's and Z stays float32, at half the bytes of both streams.  That form serves even widths of at least 4 with
+    even row strides and 4-byte aligned views."""
     code = _edge_op(op)
     _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
-    _check_f32_view(F, "F")
+    _check_edge_view(F, "F")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), F.size(1)
     if X is None and op != "copy":
         raise RuntimeError("input may be None for op='copy' only")
     if X is not None:
-        _check_f32_view(X, "input")
+        _check_edge_view(X, "input", F)
         if X.size(1) != D or X.device != F.device:
             raise RuntimeError("input and F must have the same width and device, got %s and %s" % (tuple(X.shape), tuple(F.shape)))
     if index is not None:
@@ -1096,44 +1107,47 @@ def forward_edge_messages(X, F, row_pointers, column_index, blockPartition, edge
                       row_nzr, D, X.size(0) if X is not None else 1 << 62, F.device)  # (copy: no gathered rows)
     Z = torch.empty((N, D), dtype=torch.float32, device=F.device)
     with c:
-        check(lib().hcspmm_forward_edge_messages(_ptr(X), X.size(0) if X is not None else 0,
-                                                 X.stride(0) if X is not None else D, _ptr(F), F.size(0), F.stride(0),
-                                                 _ptr(index), code, _ptr(Z), D, *c.graph, *c.ws))
+        check(lib().hcspmm_forward_edge_messages_typed(_ptr(X), X.size(0) if X is not None else 0,
+                                                       X.stride(0) if X is not None else D, _ptr(F), F.size(0), F.stride(0),
+                                                       _DTYPES[F.dtype], _ptr(index), code, _ptr(Z), D, *c.graph, *c.ws))
     return [Z]
 
 
 def edge_messages_grad(dZ, X, F, row_pointers, column_index, op="add_relu"):
-    """Gradient of forward_edge_messages (direct form) with respect to F -> float32 [E, D]: "mul" dZ[row(e)] * X[col(e)],
+    """Gradient of forward_edge_messages (direct form) with respect to F -> [E, D] of dZ's dtype: "mul" dZ[row(e)] * X[col(e)],
     "add_relu" dZ[row(e)] where X[col(e)] + F[e] > 0 and +0 elsewhere, "copy" dZ[row(e)] (X and F may be None).  Edge-parallel,
-    every element written once (hcspmm.h hcspmm_edge_messages_grad)."""
+    every element written once (hcspmm.h hcspmm_edge_messages_grad).  dZ, X and F are all float32, or all float16 / all bfloat16
+    (hcspmm_edge_messages_grad_typed: "mul" rounds the exact product once, the other ops pass dZ's own bits; even widths of at
+    least 4, even row strides, 4-byte aligned views)."""
     code = _edge_op(op)
     _check_graph(row_pointers, column_index)
-    _check_f32_view(dZ, "dZ")
+    _check_edge_view(dZ, "dZ")
     N, E, D = row_pointers.size(0) - 1, column_index.size(0), dZ.size(1)
     if dZ.size(0) != N:
         raise RuntimeError("dZ has %d rows but the graph has %d nodes" % (dZ.size(0), N))
     if op != "copy":
         if X is None:
             raise RuntimeError("input may be None for op='copy' only")
-        _check_f32_view(X, "input")
+        _check_edge_view(X, "input", dZ)
         if X.size(1) != D or X.device != dZ.device:
             raise RuntimeError("input must have the width and device of dZ")
     if op == "add_relu":
         if F is None:
             raise RuntimeError("F is required for op='add_relu'")
-        _check_f32_view(F, "F")
+        _check_edge_view(F, "F", dZ)
         if F.size(1) != D or F.size(0) < E or F.device != dZ.device:
             raise RuntimeError("F must be [E, D] with E = %d, D = %d on the device of dZ, got %s" % (E, D, tuple(F.shape)))
     reads_x, reads_f = op != "copy", op == "add_relu"
-    out = torch.empty((E, D), dtype=torch.float32, device=dZ.device)
+    out = torch.empty((E, D), dtype=dZ.dtype, device=dZ.device)
     if D == 0:
         return out
     stream = ctypes.c_void_p(torch.cuda.current_stream(dZ.device).cuda_stream)
     with _on_device(dZ.device):
-        check(lib().hcspmm_edge_messages_grad(_ptr(dZ), dZ.stride(0), _ptr(X) if reads_x else ctypes.c_void_p(0),
-                                              X.size(0) if reads_x else 0, X.stride(0) if reads_x else D,
-                                              _ptr(F) if reads_f else ctypes.c_void_p(0), F.stride(0) if reads_f else D, _ptr(out), D,
-                                              code, _ptr(row_pointers), _ptr(column_index), N, E, D, stream))
+        check(lib().hcspmm_edge_messages_grad_typed(_ptr(dZ), dZ.stride(0), _ptr(X) if reads_x else ctypes.c_void_p(0),
+                                                    X.size(0) if reads_x else 0, X.stride(0) if reads_x else D,
+                                                    _ptr(F) if reads_f else ctypes.c_void_p(0), F.stride(0) if reads_f else D,
+                                                    _DTYPES[dZ.dtype], _ptr(out), D, code, _ptr(row_pointers), _ptr(column_index),
+                                                    N, E, D, stream))
     return out
 
 

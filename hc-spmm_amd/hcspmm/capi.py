@@ -129,6 +129,10 @@ SYMBOLS = {
     "hcspmm_forward_edge_messages": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_edge_messages_grad": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _i64, _i64, _int, _vp]),
+    "hcspmm_forward_edge_messages_typed": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
+    "hcspmm_edge_messages_grad_typed": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _int, _vp, _vp, _i64, _i64, _int,
+                                               _vp]),
     "hcspmm_edge_norm_device": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp]),
     "hcspmm_transpose_permutation": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "hcspmm_transpose_graph": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),

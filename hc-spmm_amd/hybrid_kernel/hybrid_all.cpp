@@ -826,34 +826,43 @@ torch::Tensor spmm_forward_extremum_backward(torch::Tensor grad_Z, torch::Tensor
   return grad_X;
 }
 
-// Edge-feature messages (hcspmm_forward_edge_messages / hcspmm_edge_messages_grad): float32 views with unit inner stride
+// Edge-feature messages (hcspmm_forward_edge_messages_typed / hcspmm_edge_messages_grad_typed): views with unit inner stride
 int edge_op_code(const std::string& op) {
   if (op == "mul") return HCSPMM_EDGE_OP_MUL;
   if (op == "add_relu") return HCSPMM_EDGE_OP_ADD_RELU;
   TORCH_CHECK(op == "copy", "op must be one of 'mul', 'add_relu', 'copy', got '", op, "'");
   return HCSPMM_EDGE_OP_COPY;
 }
-void check_f32_view(const torch::Tensor& t, const char* name) {
+// an operand of the two calls: float32, or float16 / bfloat16 with rows on the dword grid; `like`: the operand whose dtype it shares
+void check_edge_view(const torch::Tensor& t, const char* name, const torch::Tensor* like = nullptr) {
   CHECK_CUDA(t);
-  TORCH_CHECK(t.scalar_type() == torch::kFloat && t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1), name,
-              " must be a 2-D float32 view with unit inner stride");
+  TORCH_CHECK(feature_dtype(t) >= 0 && t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1), name,
+              " must be a 2-D float32 / float16 / bfloat16 view with unit inner stride");
+  TORCH_CHECK(!like || t.scalar_type() == like->scalar_type(), name,
+              " must have the dtype of the other operands (all float32, all float16 or all bfloat16), got ", t.scalar_type(), " and ",
+              like ? like->scalar_type() : t.scalar_type());
+  TORCH_CHECK(t.scalar_type() == torch::kFloat || (t.size(1) >= 4 && t.size(1) % 2 == 0 && t.stride(0) % 2 == 0 &&
+                                                   reinterpret_cast<uintptr_t>(t.data_ptr()) % 4 == 0),
+              "16-bit edge messages serve even widths >= 4 with even row strides and 4-byte aligned views: pad ", name,
+              " to an even width");
 }
 
+// input and F float32, or both float16 / both bfloat16 (hcspmm_forward_edge_messages_typed): widened exactly, float32 output
 std::vector<torch::Tensor> spmm_forward_edge_messages(c10::optional<torch::Tensor> input, torch::Tensor F, torch::Tensor nodePointer,
                                                       torch::Tensor edgeList, torch::Tensor blockPartition,
                                                       torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type,
                                                       torch::Tensor row_nzr, torch::Tensor col_nzr, const std::string& op,
                                                       c10::optional<torch::Tensor> index) {
   const int code = edge_op_code(op);
-  check_f32_view(F, "F");
+  check_edge_view(F, "F");
   TORCH_CHECK(input.has_value() || code == HCSPMM_EDGE_OP_COPY, "input may be None for op='copy' only");
   TORCH_CHECK(F.size(1) > 0, "F must have at least one column");
   if (input.has_value()) {
-    check_f32_view(*input, "input");
+    check_edge_view(*input, "input", &F);
     TORCH_CHECK(input->size(1) == F.size(1) && input->device() == F.device(), "input and F must have the same width and device, got ",
                 input->sizes(), " and ", F.sizes());
   }
-  CallOptions o;
+  CallOptions o(CallOptions::kTyped);
   o.rect = o.strided = true;
   // (no input: no rows are gathered, and the plan is checked against the graph alone)
   PlannedCall c(input.has_value() ? &*input : nullptr, F, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
@@ -866,46 +875,48 @@ std::vector<torch::Tensor> spmm_forward_edge_messages(c10::optional<torch::Tenso
   } else {
     TORCH_CHECK(F.size(0) >= c.E, "F has ", F.size(0), " rows but the graph has ", c.E, " entries");
   }
-  auto output = torch::empty({c.N, (int64_t)c.D}, F.options());
-  const int rc = invoke(hcspmm_forward_edge_messages,
+  auto output = torch::empty({c.N, (int64_t)c.D}, F.options().dtype(torch::kFloat));
+  const int rc = invoke(hcspmm_forward_edge_messages_typed,
                         std::make_tuple(input.has_value() && input->numel() > 0 ? input->data_ptr() : nullptr,
                                         input.has_value() ? input->size(0) : 0, input.has_value() ? input->stride(0) : c.D,
-                                        F.numel() > 0 ? F.data_ptr<float>() : nullptr, F.size(0), F.stride(0),
-                                        index.has_value() ? iptr(*index) : nullptr, code, c.N > 0 ? output.data_ptr() : nullptr, c.D),
+                                        F.numel() > 0 ? F.data_ptr() : nullptr, F.size(0), F.stride(0), feature_dtype(F),
+                                        index.has_value() ? iptr(*index) : nullptr, code,
+                                        c.N > 0 ? output.data_ptr<float>() : nullptr, c.D),
                         c.graph(), c.ws());
   check_rc(rc, "forward_edge_messages");
   return {output};
 }
 
+// dZ, input and F float32, or all float16 / all bfloat16 (hcspmm_edge_messages_grad_typed): the result has their dtype
 torch::Tensor spmm_edge_messages_grad(torch::Tensor dZ, c10::optional<torch::Tensor> input, c10::optional<torch::Tensor> F,
                                       torch::Tensor nodePointer, torch::Tensor edgeList, const std::string& op) {
   const int code = edge_op_code(op);
   CHECK_INPUT(nodePointer);
   CHECK_INPUT(edgeList);
   check_i32_graph(nodePointer, edgeList);
-  check_f32_view(dZ, "dZ");
+  check_edge_view(dZ, "dZ");
   const int64_t N = nodePointer.size(0) - 1, E = edgeList.size(0), D = dZ.size(1);
   TORCH_CHECK(dZ.size(0) == N, "dZ has ", dZ.size(0), " rows but the graph has ", N, " nodes");
   const bool reads_x = code != HCSPMM_EDGE_OP_COPY, reads_f = code == HCSPMM_EDGE_OP_ADD_RELU;
   if (reads_x) {
     TORCH_CHECK(input.has_value(), "input may be None for op='copy' only");
-    check_f32_view(*input, "input");
+    check_edge_view(*input, "input", &dZ);
     TORCH_CHECK(input->size(1) == D && input->device() == dZ.device(), "input must have the width and device of dZ");
   }
   if (reads_f) {
     TORCH_CHECK(F.has_value(), "F is required for op='add_relu'");
-    check_f32_view(*F, "F");
+    check_edge_view(*F, "F", &dZ);
     TORCH_CHECK(F->size(1) == D && F->size(0) >= E && F->device() == dZ.device(), "F must be [E, D] with E = ", E, ", D = ", D,
                 " on the device of dZ, got ", F->sizes());
   }
   auto out = torch::empty({E, D}, dZ.options());
   if (D == 0) return out;
   const c10::DeviceGuard guard(dZ.device());
-  const int rc = hcspmm_edge_messages_grad(
-      dZ.numel() > 0 ? dZ.data_ptr<float>() : nullptr, dZ.stride(0), reads_x && input->numel() > 0 ? input->data_ptr<float>() : nullptr,
-      reads_x ? input->size(0) : 0, reads_x ? input->stride(0) : D, reads_f && F->numel() > 0 ? F->data_ptr<float>() : nullptr,
-      reads_f ? F->stride(0) : D, E > 0 ? out.data_ptr<float>() : nullptr, D, code, iptr(nodePointer), iptr(edgeList), N, E, (int)D,
-      current_stream(dZ));
+  const int rc = hcspmm_edge_messages_grad_typed(
+      dZ.numel() > 0 ? dZ.data_ptr() : nullptr, dZ.stride(0), reads_x && input->numel() > 0 ? input->data_ptr() : nullptr,
+      reads_x ? input->size(0) : 0, reads_x ? input->stride(0) : D, reads_f && F->numel() > 0 ? F->data_ptr() : nullptr,
+      reads_f ? F->stride(0) : D, feature_dtype(dZ), E > 0 ? out.data_ptr() : nullptr, D, code, iptr(nodePointer), iptr(edgeList), N,
+      E, (int)D, current_stream(dZ));
   check_rc(rc, "edge_messages_grad");
   return out;
 }

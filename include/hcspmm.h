@@ -38,7 +38,7 @@ extern "C" {
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
  * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
  * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26);
- * hcspmm_forward_multi_typed (round 27).
+ * hcspmm_forward_multi_typed (round 27); hcspmm_forward_edge_messages_typed, hcspmm_edge_messages_grad_typed (round 28).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -740,6 +740,35 @@ int hcspmm_edge_messages_grad(const float* grad_Z_d, int64_t ldg, const float* X
                               int64_t ldf, float* grad_F_out_d, int64_t ldgf, int op, const int32_t* row_pointers_d,
                               const int32_t* column_index_d, int64_t num_nodes, int64_t num_edges, int embedding_dim,
                               void* stream);
+
+/* hcspmm_forward_edge_messages_typed / hcspmm_edge_messages_grad_typed: the two calls above with X_d and F_d (and grad_Z_d, and the
+ * output grad_F_out_d) ALL of element type `dtype`.
+ *   HCSPMM_DTYPE_F32           forwards to the fp32 call, which changes in no way
+ *   HCSPMM_DTYPE_F16 / _BF16   x, f = the elements widened to fp32 (exact), then the op's arithmetic, the summation orders and every
+ *                              guarantee above on the widened values.  Z_d, the partial slots and the fix-up pass stay FP32 (the
+ *                              X-gradient is such a sum and is not rounded); wherever the fp32 launch's order does not depend on the
+ *                              lane count -- plan-free rows of at most 64 entries -- Z has the bits of the fp32 call on the widened
+ *                              operands.  Half the bytes of the gathered X rows and of the F stream (kernels of their own,
+ *                              spmm_edgevec16.hip); the column panels of a planned call are 64 columns wide.
+ *                              The gradient writes grad_F in the operands' type: MUL rounds the exact fp32 product once (nearest
+ *                              even, NaN stays NaN), ADD_RELU and COPY pass grad_Z's own 16 bits or +0 (edgevec16_grad.hip).
+ * Strides count elements.  The 16-bit types serve every EVEN embedding_dim >= 4 with even strides and 4-byte aligned bases of the
+ * operands the op reads or writes (rows on the dword grid); an odd width or stride, embedding_dim == 2 or a misaligned base is
+ * HCSPMM_EINVAL before any device call -- pad to an even width.  A dtype outside F32 ... BF16 is HCSPMM_EINVAL; every other
+ * argument, plan and workspace error is the fp32 call's.  workspace_d >= hcspmm_workspace_bytes().  num_nodes == 0 (forward) and
+ * num_edges == 0 (gradient) return HCSPMM_OK without a launch.  The gradient recipe above holds with 16-bit copies of grad_Z
+ * (MUL) and with the 16-bit grad_F (ADD_RELU -> COPY) in the places of X and F: dX comes back fp32. */
+int hcspmm_forward_edge_messages_typed(const void* X_d, int64_t x_rows, int64_t ldx, const void* F_d, int64_t f_rows, int64_t ldf,
+                                       int dtype, const int32_t* f_index_d /* [E] or NULL */, int op, float* Z_d, int64_t ldz,
+                                       const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                       const int32_t* blockPartition_d, const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d,
+                                       const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
+                                       int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d,
+                                       size_t workspace_bytes, void* stream);
+int hcspmm_edge_messages_grad_typed(const void* grad_Z_d, int64_t ldg, const void* X_d, int64_t x_rows, int64_t ldx, const void* F_d,
+                                    int64_t ldf, int dtype, void* grad_F_out_d, int64_t ldgf, int op, const int32_t* row_pointers_d,
+                                    const int32_t* column_index_d, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                                    void* stream);
 
 /* Edge normalisations of a square graph, on the device (asynchronous on `stream`); deg(r) = stored entries of row r, so
  * self-loops count only when the graph stores them.  Rows of degree 0 own no entries.
