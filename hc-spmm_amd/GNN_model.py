@@ -239,6 +239,33 @@ class _Update16(torch.autograd.Function):
         return d_x, d_w
 
 
+class _Scores16(torch.autograd.Function):
+    """The attention score product s = h16 A for a 16-bit h [N, D] and the fp32 parameter block A [D, 2 heads], s float32: A is
+    rounded once to h's dtype and the product runs on the 16-bit update kernel with fp32 accumulation and an fp32 output.  In the
+    backward ds is rounded once to h's dtype; d_h = ds16 A16^T (16-bit) and d_A = h16^T ds16 through the 16-bit weight gradient
+    (fp32).  Below 4096 rows, or for a shape the kernels do not serve, torch.mm on the same operands (as _Update16)."""
+
+    @staticmethod
+    def forward(ctx, h, A):
+        h = h.contiguous()
+        A16 = A.detach().to(h.dtype)
+        ctx.save_for_backward(h, A16)
+        s = HCSPMM.update(h, A16, torch.float32) if h.size(0) >= 4096 else None
+        return s if s is not None else torch.mm(h.float(), A16.float())
+
+    @staticmethod
+    def backward(ctx, d_s):
+        h, A16 = ctx.saved_tensors
+        d_s = d_s.to(h.dtype).contiguous()
+        d_h = _Update16._mm16(d_s, A16.transpose(0, 1)) if ctx.needs_input_grad[0] else None
+        d_a = None
+        if ctx.needs_input_grad[1]:
+            d_a = HCSPMM.weight_grad(h, d_s) if h.size(0) >= 4096 else None
+            if d_a is None:
+                d_a = torch.mm(h.transpose(0, 1).float(), d_s.float())
+        return d_h, d_a
+
+
 _TRANSPOSED = {}  # (row_pointers, column_index) pointers and sizes -> (weak refs, perm): the host pass runs once per graph
 
 
@@ -504,10 +531,47 @@ class EdgeWeightedAggregateHeads(torch.autograd.Function):
         return (d_x, d_w, None) + (None,) * N_GRAPH
 
 
-def edge_weighted_aggregate_heads(X, edge_weight, graph, directed=False):
+class EdgeWeightedAggregateHeads16(torch.autograd.Function):
+    """EdgeWeightedAggregateHeads on a float16 / bfloat16 X [N, heads*Dh] (HCSPMM.forward_weighted_heads16: half the gathered
+    bytes, fp32 sums, Z in X's dtype), symmetric and directed.  dX = A_w^T dY = forward_weighted_heads16(dY16, w, value_index=index)
+    on the backward graph -- the graph itself with transpose_permutation's perm, or transposed_graph's tensors with entry_index_t --
+    so the values are read in place and no w[:, perm] copy is written; dX has X's dtype.  dw = HCSPMM.sddmm_heads16(dY16, X16),
+    float32.  tail = the eight graph tensors, the backward's eight, the index."""
+
+    @staticmethod
+    def forward(ctx, X, edge_weight, *tail):
+        X = X.contiguous()
+        edge_weight = edge_weight.contiguous()
+        ctx.save_for_backward(X, edge_weight, *tail)
+        return HCSPMM.forward_weighted_heads16(X, edge_weight, *tail[:N_GRAPH])[0]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        X, edge_weight, *tail = ctx.saved_tensors
+        graph, graph_b, index = tail[:N_GRAPH], tail[N_GRAPH:2 * N_GRAPH], tail[2 * N_GRAPH]
+        d_out = d_out.to(X.dtype).contiguous()
+        d_x = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_x = HCSPMM.forward_weighted_heads16(d_out, edge_weight, *graph_b, value_index=index)[0]
+        if ctx.needs_input_grad[1]:
+            d_w = HCSPMM.sddmm_heads16(d_out, X, *graph, edge_weight.size(0))
+        return (d_x, d_w) + (None,) * len(tail)
+
+
+def edge_weighted_aggregate_heads(X, edge_weight, graph, directed=False, activation_dtype=None):
     """Multi-head A_w X with autograd for X [N, heads*Dh] and edge_weight [heads, E] (float32, Dh % 4 == 0); graph = the
     eight graph tensors, whose pattern must be symmetric (the backward's A_w^T) unless directed=True: the backward then
-    runs on transposed_graph(graph)."""
+    runs on transposed_graph(graph).
+    activation_dtype = torch.bfloat16 / torch.float16: X is taken in that dtype (an fp32 X is rounded once) and the 16-bit
+    kernels run (EdgeWeightedAggregateHeads16): fp32 sums, the result and dX in that dtype.  A 16-bit X selects them as well."""
+    if activation_dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+    if activation_dtype is not None:
+        X = X.to(activation_dtype)
+    if X.dtype in (torch.bfloat16, torch.float16):
+        if directed:
+            return EdgeWeightedAggregateHeads16.apply(X, edge_weight, *graph, *transposed_graph(graph))
+        return EdgeWeightedAggregateHeads16.apply(X, edge_weight, *graph, *graph, transpose_permutation_i32(graph[0], graph[1]))
     if directed:
         return EdgeWeightedAggregateDirected.apply(X, edge_weight, *graph, *transposed_graph(graph))
     perm = transpose_permutation(graph[0], graph[1])
@@ -823,15 +887,28 @@ class GATConv(torch.nn.Module):
     update X W_cat for all heads, both scores as one product H A_blk (A_blk block-diagonal [heads * output_dim, 2 heads]
     from a_dst / a_src; both products run on the library's update and weight-gradient kernels in both passes),
     gat_attention, and one multi-head aggregation (edge_weighted_aggregate_heads).  The kernels need output_dim % 4 == 0.
-    The parameters are the same in both modes, so a state dict loads into either."""
+    The parameters are the same in both modes, so a state dict loads into either.
 
-    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, directed=False):
+    activation_dtype = torch.bfloat16 / torch.float16 (concat=True only, _Conv's convention): X is taken in that dtype (an fp32 X
+    is rounded once), h = X W_cat runs on _Update16, the score product h A_blk on the 16-bit update with an fp32 [N, 2 heads]
+    output (_Scores16), gat_attention stays fp32, and the aggregation is EdgeWeightedAggregateHeads16: the layer returns
+    activation_dtype.  input_dim must be even."""
+
+    def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, directed=False,
+                 activation_dtype=None):
         super().__init__()
         self.fixed, self.heads, self.negative_slope, self.concat = fixed, int(heads), float(negative_slope), bool(concat)
-        self.directed = bool(directed)
+        self.directed, self.activation_dtype = bool(directed), activation_dtype
         if self.concat and output_dim % 4 != 0:
             raise ValueError("GATConv(concat=True) needs output_dim (the width of one head) to be a multiple of 4, got %d"
                              % output_dim)
+        if activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+        if activation_dtype is not None and not self.concat:
+            raise ValueError("activation_dtype needs GATConv(concat=True): the mean-of-heads layer stays fp32")
+        if activation_dtype is not None and input_dim % 2:
+            raise ValueError("activation_dtype needs even widths (16-bit rows on the dword grid), got %d -> %d"
+                             % (input_dim, self.heads * output_dim))
         self.weights = torch.nn.Parameter(torch.empty(self.heads, input_dim, output_dim))  # W_k = weights[k], contiguous
         self.a_src = torch.nn.Parameter(torch.empty(self.heads, output_dim))
         self.a_dst = torch.nn.Parameter(torch.empty(self.heads, output_dim))
@@ -863,8 +940,13 @@ class GATConv(torch.nn.Module):
     def _forward_concat(self, X, graph):
         heads, din, dout = self.weights.shape
         w_cat = self.weights.permute(1, 0, 2).reshape(din, heads * dout)  # column block k = W_k
-        h = _Update.apply(X, w_cat)  # [N, heads * dout]
         a_blk = torch.cat([torch.block_diag(*self.a_dst.unsqueeze(2)), torch.block_diag(*self.a_src.unsqueeze(2))], 1)
+        if self.activation_dtype is not None:
+            h = _Update16.apply(X.to(self.activation_dtype), w_cat)  # [N, heads * dout], 16-bit
+            s = _Scores16.apply(h, a_blk)  # [N, 2 heads] fp32
+            alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope, self.directed)
+            return edge_weighted_aggregate_heads(h, alpha, graph, self.directed, self.activation_dtype)
+        h = _Update.apply(X, w_cat)  # [N, heads * dout]
         s = _Update.apply(h, a_blk)  # [N, 2 heads]: s_dst | s_src
         alpha = gat_attention(s[:, :heads], s[:, heads:], graph, self.negative_slope, self.directed)  # [heads, E]
         return edge_weighted_aggregate_heads(h, alpha, graph, self.directed)

@@ -27,6 +27,10 @@ from dataset import HCSPMM_dataset  # noqa: E402
 from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINEConv, PNAConv, ResGatedGraphConv, SAGEConv, sampled_graph, tqdm  # noqa: E402
 
 
+_ACTIVATION_DTYPE_MODELS = ("--activation-dtype needs --model gcn or gin with --norm sym or mean, --model sage, pna, gen or gine, or "
+                            "--model gat with --gat-concat (gatv2 and the mean-of-heads gat layers stay fp32)")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", type=str, default="DD_A_our_3", help="dataset")
@@ -139,6 +143,8 @@ def parse_args(argv=None):
         p.error("--norm does not apply to --model pna: its aggregators and degree scalers are the layer's own")
     if args.heads < 1:
         p.error("--heads must be at least 1")
+    if args.activation_dtype != "fp32" and (args.model == "gatv2" or (args.model == "gat" and not args.gat_concat)):
+        p.error(_ACTIVATION_DTYPE_MODELS)
     if args.gat_concat and args.model not in ("gat", "gatv2"):
         p.error("--gat-concat applies to --model gat / gatv2 only")
     if args.gat_concat and args.hidden % (4 * args.heads) != 0:
@@ -166,6 +172,17 @@ class _FirstColumns(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.conv(*args, **kwargs)[:, :self.keep]
+
+
+class _Fp32Input(nn.Module):
+    """conv on X.float(): the mean-of-heads GAT layer behind 16-bit concat layers stays fp32."""
+
+    def __init__(self, conv):
+        super().__init__()
+        self.conv = conv
+
+    def forward(self, X, *args, **kwargs):
+        return self.conv(X.float(), *args, **kwargs)
 
 
 class Net(nn.Module):
@@ -271,8 +288,11 @@ def main(argv=None):
     if args.model == "gat":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:  # first / hidden layers: heads x (hidden / heads) features, concatenated
-                return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True, directed=directed)
-            return GATConv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
+                # 16-bit rows sit on a 4-byte grid: a layer of odd input width (raw features) keeps fp32 operands
+                return GATConv(input_dim, output_dim // args.heads, fixed, heads=args.heads, concat=True, directed=directed,
+                               activation_dtype=activation_dtype if input_dim % 2 == 0 else None)
+            conv = GATConv(input_dim, output_dim, fixed, heads=args.heads, directed=directed)
+            return conv if activation_dtype is None else _Fp32Input(conv)  # the mean-of-heads layer stays fp32
     if args.model == "gatv2":
         def conv_cls(input_dim, output_dim, fixed):
             if args.gat_concat and fixed != 2:
@@ -293,9 +313,9 @@ def main(argv=None):
     model = Net(conv_cls, dataset, graph, output, args.hidden, args.num_layers, edge_weight, edge_attr).to(device)
     if args.fp8:
         set_feature_storage(model, "fp8")
-    if args.activation_dtype != "fp32" and args.model not in ("sage", "pna", "gen", "gine"):  # (those layers took it where they were built)
+    if args.activation_dtype != "fp32" and args.model not in ("sage", "pna", "gen", "gine", "gat"):  # (those layers took it where they were built)
         if args.model not in ("gcn", "gin") or edge_weight is None:
-            raise SystemExit("--activation-dtype needs --model gcn or gin with --norm sym or mean, or --model sage, pna, gen or gine")
+            raise SystemExit(_ACTIVATION_DTYPE_MODELS)
         for m in model.modules():
             if isinstance(m, (GCNConv, GINConv)):
                 m.activation_dtype = activation_dtype

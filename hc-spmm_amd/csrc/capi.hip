@@ -478,6 +478,52 @@ extern "C" int hcspmm_forward_weighted_indexed(const void* X, int64_t x_rows, in
                       value_index ? value_index : &no_entries, num_values);
 }
 
+// The multi-head weighted product on features of one element type (fp32: the calls above; fp16 / bf16: spmm_heads16.hip, every row
+// from CSR, fp32 partial slots, Z fp32 or the features' type).  A null value_index is the identity.
+extern "C" int hcspmm_forward_weighted_heads_typed(const void* X, int64_t x_rows, int64_t ldx, void* Z, int64_t ldz, int dtype,
+                                                   int z_dtype, const int32_t* rowptr, const int32_t* col,
+                                                   const int32_t* blockPartition, const int32_t* edgeToColumn,
+                                                   const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,
+                                                   const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* workspace,
+                                                   size_t workspace_bytes, void* stream_v, const float* values, int heads,
+                                                   const int32_t* value_index, int64_t num_values) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (z_dtype != HCSPMM_DTYPE_F32 && z_dtype != dtype) return HCSPMM_EINVAL;
+  if (!value_index && num_values != E) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32) {
+    if (value_index)
+      return hcspmm_forward_weighted_indexed(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
+                                             hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, values, heads,
+                                             value_index, num_values);
+    return hcspmm_forward_weighted_heads(X, x_rows, ldx, Z, ldz, dtype, rowptr, col, blockPartition, edgeToColumn, edgeToRow,
+                                         hybrid_type, plan_d, ph, N, E, D, workspace, workspace_bytes, stream_v, values, heads);
+  }
+  if (!values || heads <= 0 || num_values < 0 || (E > 0 && num_values == 0)) return HCSPMM_EINVAL;
+  if (num_values > INT32_MAX || num_values > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  if (N < 0 || E < 0 || D <= 0 || ldx < D || ldz < D || D % heads != 0 || (D / heads) % 4 != 0) return HCSPMM_EINVAL;
+  // rows on the dword grid
+  const bool z16 = z_dtype != HCSPMM_DTYPE_F32;
+  if ((ldx & 1) != 0 || !aligned(X, 4) || !aligned(Z, 4) || (z16 && (ldz & 1) != 0)) return HCSPMM_EINVAL;
+  if (N == 0) return HCSPMM_OK;
+  if (!X || !Z || !rowptr || (E > 0 && !col)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  hcspmm::Heads16Args a{};
+  // workspace: hcspmm_workspace_bytes (fp32 partial slots); the features' type decides the panel width
+  const int rc = bind_graph(a.p, GRAPH_IN, D, x_rows, workspace, workspace_bytes, 1, dtype);
+  if (rc != HCSPMM_OK) return rc;
+  if (a.p.partial && !aligned(a.p.partial, 4)) return HCSPMM_EINVAL;
+  if (a.p.plan) a.segment_len = ph->segment_len;
+  set_operands(a.p, X, Z, ldx, ldz);
+  a.rowptr = rowptr;
+  a.dh = D / heads;
+  a.z16 = z16 ? 1 : 0;
+  a.values = values;
+  a.num_values = (long long)num_values;
+  a.vindex = value_index;
+  const hipError_t e = hcspmm::launch_heads16(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 // 8-bit feature storage (quantize_fp8.hip, spmm_kernels_f8.hip, spmm_weighted_f8.hip): forward_impl's checks and launch
 // decisions for one-byte elements, fp32 Z, nullable values and per-row scales.
 extern "C" int hcspmm_quantize_fp8(const float* X, int64_t rows, int64_t ldx, int D, int format, const float* scale_in, void* Xq,
@@ -1108,6 +1154,30 @@ extern "C" int hcspmm_sddmm_heads(const void* A, int64_t lda, const void* B, int
                                   int64_t N, int64_t E, int D, void* stream_v, int heads) {
   if (heads <= 0) return HCSPMM_EINVAL;
   return sddmm_impl(A, lda, B, b_rows, ldb, dtype, out, rowptr, col, plan_d, ph, N, E, D, stream_v, heads);
+}
+
+// Multi-head SDDMM on operands of one element type (fp32: the call above; fp16 / bf16: sddmm_heads16.hip, one lane group per row).
+extern "C" int hcspmm_sddmm_heads_typed(const void* A, int64_t lda, const void* B, int64_t b_rows, int64_t ldb, int dtype, float* out,
+                                        const int32_t* rowptr, const int32_t* col, const int32_t* plan_d,
+                                        const hcspmm_plan_header* ph, int64_t N, int64_t E, int D, void* stream_v, int heads) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32) return hcspmm_sddmm_heads(A, lda, B, b_rows, ldb, dtype, out, rowptr, col, plan_d, ph, N, E, D, stream_v, heads);
+  if (heads <= 0 || D <= 0 || !hcspmm::sddmm_heads16_supported(D, heads)) return HCSPMM_EINVAL;
+  if ((long long)E * heads > INT64_MAX / 4) return HCSPMM_ERANGE;
+  if (N < 0 || E < 0 || b_rows < 0 || lda < D || ldb < D) return HCSPMM_EINVAL;
+  if (((lda | ldb) & 1) != 0 || !aligned(A, 4) || !aligned(B, 4)) return HCSPMM_EINVAL;  // rows on the dword grid
+  if (!rowptr || (E > 0 && (!A || !B || !out || !col || N == 0))) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX) return HCSPMM_ERANGE;
+  if ((plan_d == nullptr) != (ph == nullptr)) return HCSPMM_EINVAL;  // both or neither
+  if (ph) {
+    const int rc = hcspmm_plan_check(ph, N, E, 0);
+    if (rc != HCSPMM_OK) return rc;
+    if (b_rows < ph->num_columns) return HCSPMM_EINVAL;  // the graph gathers rows B does not have
+  }
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::SddmmArgs a{A, B, (size_t)lda, (size_t)ldb, rowptr, col, out, (int)N, D, (long long)E};
+  const hipError_t e = hcspmm::launch_sddmm_heads16(a, heads, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
 }
 
 namespace {

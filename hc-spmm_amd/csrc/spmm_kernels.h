@@ -493,4 +493,26 @@ struct EVec16GradArgs {
 };
 hipError_t launch_edgevec16_grad(const EVec16GradArgs& a, int dtype, hipStream_t stream);
 
+// The multi-head weighted aggregation on fp16 / bf16 rows (spmm_heads16.hip; the 16-bit dtypes of
+// hcspmm_forward_weighted_heads_typed): p.X holds 16-bit elements on the dword grid (even ldx, 4-byte aligned base), values are
+// fp32 head-major [heads][num_values], entry e of head h weighs values[h * num_values + (vindex ? vindex[e] : e)].  p.Z is fp32
+// (z16 = 0) or X's type (z16 = 1: even p.ldz, 4-byte aligned base); the partial slots are fp32.  dh % 4 == 0 and D % dh == 0.
+// The unit picks its own lanes: 8 elements when dh % 8 == 0 and the panel has 32 columns or more, 4 otherwise.
+struct Heads16Args {
+  PlanArgs p;
+  const int* rowptr;     // [N + 1]
+  int segment_len;       // plan header: entries per segment of a split row
+  int dh;                // columns per head
+  int z16;
+  const float* values;   // [heads][num_values]
+  long long num_values;
+  const int* vindex;     // [E], or nullptr: the identity (num_values = E)
+};
+// dtype: HCSPMM_DTYPE_F16 or HCSPMM_DTYPE_BF16
+hipError_t launch_heads16(const Heads16Args& a, int dtype, hipStream_t stream);
+// multi-head SDDMM on 16-bit rows (sddmm_heads16.hip, hcspmm_sddmm_heads_typed): a.D = heads * Dh, the whole row; A and B on the
+// dword grid; one lane group per row (sddmm_heads16_supported: Dh % 4 == 0 and D within 64 lanes of 8 or 4 columns)
+bool sddmm_heads16_supported(int D, int heads);
+hipError_t launch_sddmm_heads16(const SddmmArgs& a, int heads, int dtype, hipStream_t stream);
+
 }  // namespace hcspmm

@@ -31,7 +31,7 @@ __all__ = [
     "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi", "forward_multi16",
     "forward_softmax", "softmax_backward", "forward_softmax16", "softmax_backward16", "forward_gated",
-    "forward_edge_messages", "edge_messages_grad", "EDGE_OPS",
+    "forward_edge_messages", "edge_messages_grad", "EDGE_OPS", "forward_weighted_heads16", "sddmm_heads16",
     "quantize_fp8", "forward_fp8", "forward_weighted_fp8", "wide_threshold_fp8",
     "wide_threshold", "workspace_bytes", "fused_in_launch", "own_tiny_launch", "build_plan", "set_default_rule", "default_rule", "RULE_INTENDED", "RULE_INTENDED_GUARD",
     "RULE_AS_SHIPPED", "RULE_MI355X", "RULE_MI355X_WIDE", "mi355x_rule", "tune_plan",
@@ -668,6 +668,62 @@ def forward_weighted_indexed(X, values, value_index, row_pointers, column_index,
         check(lib().hcspmm_forward_weighted_indexed(_ptr(X), X.size(0), D, _ptr(Z), D, _DTYPES[X.dtype], *c.graph, *c.ws,
                                                     _ptr(values if V else torch.zeros(1, device=X.device)), heads,
                                                     _ptr(value_index), V))
+    return [Z]
+
+
+def _check_heads16(t, name, heads, like=None):
+    """a 16-bit operand of the multi-head kernels: float16 / bfloat16 rows on the dword grid, D = heads * Dh, Dh % 4 == 0"""
+    if not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+    if t.dtype not in (torch.float16, torch.bfloat16) or (like is not None and t.dtype != like.dtype) or t.dim() != 2 or \
+            t.stride(1) != 1 or t.stride(0) < t.size(1):
+        raise RuntimeError("%s must be a 2-D float16 / bfloat16 view with unit inner stride%s, got %s (float32 features: the fp32 "
+                           "entry points)" % (name, "" if like is None else ", of the dtype of A", t.dtype))
+    D = t.size(1)
+    if heads < 1 or D % heads != 0 or (D // heads) % 4 != 0:
+        raise RuntimeError("the multi-head kernels need heads >= 1 and D = heads * Dh with Dh a multiple of 4: D = %d, heads = %d"
+                           % (D, heads))
+    if t.stride(0) % 2 or t.data_ptr() % 4:
+        raise RuntimeError("the 16-bit multi-head kernels serve even row strides and 4-byte aligned views: %s is not" % name)
+
+
+def forward_weighted_heads16(X, values, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type,
+                             row_nzr, col_nzr, value_index=None, out_dtype=None):
+    """Multi-head edge-weighted aggregation of float16 / bfloat16 rows -> [Z] (hcspmm.h hcspmm_forward_weighted_heads_typed): X
+    [rows, D] a 16-bit view (unit inner stride, even row stride, 4-byte aligned; rows may exceed the graph's nodes), D = heads * Dh,
+    Dh % 4 == 0; values float32 [heads, V] (or [V]: one head); entry e of head h weighs values[h, value_index[e]] (int32 [E], every
+    index in [0, V)) or, without an index, values[h, e] (V = E).  Sums are fp32 fma chains; Z is out_dtype = float32, or X's dtype
+    (the default) rounded once.  Same plan, registry and workspace handling as forward_weighted_heads."""
+    _check_graph(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+    _check_input(values, "values")
+    if values.dtype != torch.float32:
+        raise RuntimeError("values must be a float32 tensor")
+    if values.dim() not in (1, 2) or (values.dim() == 2 and values.size(0) < 1):
+        raise RuntimeError("values must be [heads, V] or [V], got %s" % (tuple(values.shape),))
+    heads, V = (1, values.size(0)) if values.dim() == 1 else tuple(values.shape)
+    _check_heads16(X, "input", heads)
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), X.size(1)
+    if value_index is None:
+        if V != E:
+            raise RuntimeError("values must be [heads, E] with E = %d, got %s" % (E, tuple(values.shape)))
+    else:
+        _check_input(value_index, "value_index")
+        if value_index.dtype != torch.int32 or value_index.dim() != 1 or value_index.numel() != E:
+            raise RuntimeError("value_index must be an int32 [E] tensor with E = %d, got %s %s"
+                               % (E, value_index.dtype, tuple(value_index.shape)))
+    if values.device != X.device or (value_index is not None and value_index.device != X.device):
+        raise RuntimeError("values and value_index must be on the device of the input")
+    out_dtype = X.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, X.dtype):
+        raise RuntimeError("out_dtype must be float32 or the dtype of the input, got %s" % (out_dtype,))
+    c = _planned_call((row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type), row_nzr, D, X.size(0),
+                      X.device)
+    Z = torch.empty((N, D), dtype=out_dtype, device=X.device)
+    with c:
+        check(lib().hcspmm_forward_weighted_heads_typed(
+            _ptr(X), X.size(0), X.stride(0), _ptr(Z), D, _DTYPES[X.dtype], _DTYPES[out_dtype], *c.graph, *c.ws,
+            _ptr(values if V else torch.zeros(1, device=X.device)), heads,
+            _ptr(value_index) if value_index is not None and E else ctypes.c_void_p(0), V if value_index is not None and E else E))
     return [Z]
 
 
@@ -1353,6 +1409,33 @@ def sddmm_heads(A, B, row_pointers, column_index, blockPartition, edgeToColumn, 
     D = heads * Dh, Dh % 4 == 0.  Each head is bit for bit sddmm on the column slices.  The gradient of
     forward_weighted_heads with respect to its values is sddmm_heads(dZ, X)."""
     return _sddmm(A, B, row_pointers, column_index, row_nzr, int(heads))
+
+
+def sddmm_heads16(A, B, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, col_nzr,
+                  heads):
+    """Multi-head SDDMM of float16 / bfloat16 rows -> float32 [heads, E] (hcspmm.h hcspmm_sddmm_heads_typed): A [N, D] and B
+    [b_rows, D] 16-bit views of one dtype (unit inner stride, even row strides, 4-byte aligned), D = heads * Dh, Dh % 4 == 0,
+    D <= 512 (Dh % 8 == 0) or 256.  One lane group per row, each B row gathered once; fp32 fma sums, the same bits on every
+    call.  The gradient of forward_weighted_heads16 with respect to its values is sddmm_heads16(dZ16, X16)."""
+    heads = int(heads)
+    _check_graph(row_pointers, column_index)
+    _check_heads16(A, "A", heads)
+    _check_heads16(B, "B", heads, like=A)
+    N, E, D = row_pointers.size(0) - 1, column_index.size(0), A.size(1)
+    if A.size(0) != N:
+        raise RuntimeError("A has %d rows but the graph has %d nodes" % (A.size(0), N))
+    if B.size(1) != D:
+        raise RuntimeError("B has %d columns but A has %d" % (B.size(1), D))
+    if B.device != A.device:
+        raise RuntimeError("B must be on the device of A")
+    if D > (512 if (D // heads) % 8 == 0 else 256):
+        raise RuntimeError("the 16-bit multi-head SDDMM serves rows of up to 512 columns (Dh %% 8 == 0) or 256: D = %d" % D)
+    c = _planned_call((row_pointers, column_index), row_nzr, D, B.size(0), A.device, ws_fn=None)
+    out = torch.empty((heads, E), dtype=torch.float32, device=A.device)
+    with c:
+        check(lib().hcspmm_sddmm_heads_typed(_ptr(A), A.stride(0), _ptr(B), B.size(0), B.stride(0), _DTYPES[A.dtype], _ptr(out),
+                                             *c.graph, c.stream, heads))
+    return out
 
 
 def _softmax_operand(t, name, E, device):

@@ -100,6 +100,8 @@ SYMBOLS = {
                                              _int, _vp, _sz, _vp, _vp, _int]),
     "hcspmm_forward_weighted_indexed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64,
                                                _int, _vp, _sz, _vp, _vp, _int, _vp, _i64]),
+    "hcspmm_forward_weighted_heads_typed": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64,
+                                                   _i64, _int, _vp, _sz, _vp, _vp, _int, _vp, _i64]),
     "hcspmm_extremum_workspace_bytes": (_sz, [_hp, _int]),
     "hcspmm_forward_extremum": (_int, [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int,
                                        _vp, _sz, _vp, _int, _vp, _i64]),
@@ -143,6 +145,7 @@ SYMBOLS = {
     "hcspmm_sample_neighbors_device": (_int, [_vp, _vp, _vp, _i64, _i64, _int, ctypes.c_uint64, _vp, _vp, _vp]),
     "hcspmm_sddmm": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp]),
     "hcspmm_sddmm_heads": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _int]),
+    "hcspmm_sddmm_heads_typed": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _int]),
     "hcspmm_edge_softmax": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_edge_softmax_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
     "hcspmm_gat_attention": (_int, [_vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _vp]),

@@ -421,6 +421,66 @@ std::vector<torch::Tensor> spmm_forward_weighted_indexed(torch::Tensor input, to
   return {output};
 }
 
+// a 16-bit operand of the multi-head kernels: float16 / bfloat16 rows on the dword grid, D = heads * Dh, Dh % 4 == 0
+void check_heads16(const torch::Tensor& t, const char* name, int64_t heads, const torch::Tensor* like = nullptr) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+  const int dtype = feature_dtype(t);
+  TORCH_CHECK((dtype == HCSPMM_DTYPE_F16 || dtype == HCSPMM_DTYPE_BF16) && (!like || t.scalar_type() == like->scalar_type()) &&
+                  t.dim() == 2 && t.stride(1) == 1 && t.stride(0) >= t.size(1),
+              name, " must be a 2-D float16 / bfloat16 view with unit inner stride", like ? ", of the dtype of A" : "", ", got ",
+              t.scalar_type(), " (float32 features: the fp32 entry points)");
+  const int64_t D = t.size(1);
+  TORCH_CHECK(heads >= 1 && D % heads == 0 && (D / heads) % 4 == 0,
+              "the multi-head kernels need heads >= 1 and D = heads * Dh with Dh a multiple of 4: D = ", D, ", heads = ", heads);
+  TORCH_CHECK(rows16(t), "the 16-bit multi-head kernels serve even row strides and 4-byte aligned views: ", name, " is not");
+}
+
+// Multi-head edge-weighted aggregation of float16 / bfloat16 rows (hcspmm_forward_weighted_heads_typed): values [heads, V] (or
+// [V]), value_index int32 [E] or None (identity, V = E); Z float32 or the input's dtype
+std::vector<torch::Tensor> spmm_forward_weighted_heads16(torch::Tensor input, torch::Tensor values, torch::Tensor nodePointer,
+                                                         torch::Tensor edgeList, torch::Tensor blockPartition,
+                                                         torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                                         torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr,
+                                                         c10::optional<torch::Tensor> value_index,
+                                                         c10::optional<torch::ScalarType> out_dtype) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  CHECK_INPUT(blockPartition);
+  CHECK_INPUT(edgeToColumn);
+  CHECK_INPUT(edgeToRow);
+  check_i32_graph(nodePointer, edgeList);
+  CHECK_INPUT(values);
+  TORCH_CHECK(values.scalar_type() == torch::kFloat, "values must be a float32 tensor");
+  TORCH_CHECK((values.dim() == 1 || values.dim() == 2) && (values.dim() == 1 || values.size(0) >= 1),
+              "values must be [heads, V] or [V], got ", values.sizes());
+  const int64_t heads = values.dim() == 1 ? 1 : values.size(0), V = values.size(values.dim() - 1), E = edgeList.size(0);
+  check_heads16(input, "input", heads);
+  if (!value_index) {
+    TORCH_CHECK(V == E, "values must be [heads, E] with E = ", E, ", got ", values.sizes());
+  } else {
+    CHECK_INPUT((*value_index));
+    TORCH_CHECK(value_index->scalar_type() == torch::kInt && value_index->dim() == 1 && value_index->numel() == E,
+                "value_index must be an int32 [E] tensor with E = ", E, ", got ", value_index->scalar_type(), " ", value_index->sizes());
+  }
+  TORCH_CHECK(values.device() == input.device() && (!value_index || value_index->device() == input.device()),
+              "values and value_index must be on the device of the input");
+  const torch::ScalarType zt = out_dtype ? *out_dtype : input.scalar_type();
+  TORCH_CHECK(zt == torch::kFloat || zt == input.scalar_type(), "out_dtype must be float32 or the dtype of the input, got ", zt);
+  CallOptions o(CallOptions::kTyped);
+  o.rect = o.strided = true;
+  PlannedCall c(&input, input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, hybrid_type, row_nzr, o);
+  auto output = torch::empty({c.N, (int64_t)c.D}, input.options().dtype(zt));
+  auto vals = V > 0 ? values : torch::zeros({1}, values.options());  // (NULL values: EINVAL)
+  const bool indexed = value_index.has_value() && E > 0;
+  const int rc = invoke(hcspmm_forward_weighted_heads_typed,
+                        std::make_tuple(input.data_ptr(), input.size(0), input.stride(0), output.data_ptr(), c.D, feature_dtype(input),
+                                        feature_dtype(output)),
+                        c.graph(), c.ws(),
+                        std::make_tuple(vals.data_ptr<float>(), (int)heads, indexed ? iptr(*value_index) : nullptr, indexed ? V : E));
+  check_rc(rc, "forward_weighted_heads16");
+  return {output};
+}
+
 // Max / min aggregation (hcspmm_forward_extremum): float32 X, a strided view with unit inner stride whose rows the column ids
 // index -> {Z, arg} ({Z} without arg).  float16 / bfloat16 X (hcspmm_forward_extremum_typed): Z in X's type, the winner's own 16
 // bits; even widths of at least 4, an even row stride, a 4-byte aligned view
@@ -957,6 +1017,32 @@ torch::Tensor spmm_sddmm_heads(torch::Tensor A, torch::Tensor B, torch::Tensor n
                                torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
                                torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr, int64_t heads) {
   return run_sddmm(A, B, nodePointer, edgeList, row_nzr, heads);
+}
+
+// Multi-head SDDMM of float16 / bfloat16 rows (hcspmm_sddmm_heads_typed): float32 [heads, E], one lane group per row
+torch::Tensor spmm_sddmm_heads16(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                 torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
+                                 torch::Tensor hybrid_type, torch::Tensor row_nzr, torch::Tensor col_nzr, int64_t heads) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  check_i32_graph(nodePointer, edgeList);
+  check_heads16(A, "A", heads);
+  check_heads16(B, "B", heads, &A);
+  const int64_t N = nodePointer.size(0) - 1, D = A.size(1);
+  TORCH_CHECK(A.size(0) == N, "A has ", A.size(0), " rows but the graph has ", N, " nodes");
+  TORCH_CHECK(B.size(1) == D, "B has ", B.size(1), " columns but A has ", D);
+  TORCH_CHECK(B.device() == A.device(), "B must be on the device of A");
+  TORCH_CHECK(D <= ((D / heads) % 8 == 0 ? 512 : 256),
+              "the 16-bit multi-head SDDMM serves rows of up to 512 columns (Dh % 8 == 0) or 256: D = ", D);
+  CallOptions o;
+  o.workspace_bytes = nullptr;
+  PlannedCall c(B, "B", nodePointer, edgeList, row_nzr, o);
+  auto out = torch::empty({heads, c.E}, A.options().dtype(torch::kFloat));
+  const auto operands = std::tuple_cat(std::make_tuple(A.data_ptr(), A.stride(0), B.data_ptr(), B.size(0), B.stride(0), feature_dtype(A),
+                                                       c.E ? out.data_ptr<float>() : nullptr, iptr(nodePointer), iptr(edgeList)),
+                                       c.plan(), std::make_tuple(c.N, c.E, c.D, c.stream));
+  check_rc(invoke(hcspmm_sddmm_heads_typed, operands, std::make_tuple((int)heads)), "sddmm_heads16");
+  return out;
 }
 
 torch::Tensor spmm_sddmm(torch::Tensor A, torch::Tensor B, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -1634,6 +1720,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-head edge-weighted aggregation [Z]: values [heads, E], head h weights columns h*Dh ... (h+1)*Dh - 1 (gfx950)");
   m.def("sddmm_heads", &spmm_sddmm_heads,
         "multi-head sampled dense-dense product: float32 [heads, E], one Dh-column slice per head (gfx950)");
+  m.def("forward_weighted_heads16", &spmm_forward_weighted_heads16,
+        "multi-head edge-weighted aggregation of float16 / bfloat16 rows [Z]: values float32 [heads, V], entry e of head h weighs "
+        "values[h][value_index[e]] (None: values[h][e]); fp32 sums, Z float32 or the input's dtype rounded once (gfx950)",
+        pybind11::arg("input"), pybind11::arg("values"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("value_index") = pybind11::none(),
+        pybind11::arg("out_dtype") = pybind11::none());
+  m.def("sddmm_heads16", &spmm_sddmm_heads16,
+        "multi-head sampled dense-dense product of float16 / bfloat16 rows: float32 [heads, E], each B row gathered once (gfx950)",
+        pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("row_pointers"), pybind11::arg("column_index"),
+        pybind11::arg("blockPartition"), pybind11::arg("edgeToColumn"), pybind11::arg("edgeToRow"), pybind11::arg("hybrid_type"),
+        pybind11::arg("row_nzr"), pybind11::arg("col_nzr"), pybind11::arg("heads"));
   m.def("forward_max", [](torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor blockPartition,
                           torch::Tensor edgeToColumn, torch::Tensor edgeToRow, torch::Tensor hybrid_type, torch::Tensor row_nzr,
                           torch::Tensor col_nzr, bool return_arg) {

@@ -38,7 +38,8 @@ extern "C" {
  * hcspmm_sample_neighbors_device, hcspmm_transpose_graph_device_workspace_bytes, hcspmm_transpose_graph_device (round 19);
  * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
  * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26);
- * hcspmm_forward_multi_typed (round 27); hcspmm_forward_edge_messages_typed, hcspmm_edge_messages_grad_typed (round 28).
+ * hcspmm_forward_multi_typed (round 27); hcspmm_forward_edge_messages_typed, hcspmm_edge_messages_grad_typed (round 28);
+ * hcspmm_forward_weighted_heads_typed, hcspmm_sddmm_heads_typed (round 29).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -435,6 +436,25 @@ int hcspmm_forward_weighted_indexed(const void* X_d, int64_t x_rows, int64_t ldx
                                     const int32_t* plan_d, const hcspmm_plan_header* plan_header_h, int64_t num_nodes,
                                     int64_t num_edges, int embedding_dim, void* workspace_d, size_t workspace_bytes, void* stream,
                                     const float* values_d, int heads, const int32_t* value_index_d /* [E] */, int64_t num_values);
+
+/* hcspmm_forward_weighted_indexed on features of one element type, with a nullable index and a chosen output type.
+ * dtype = HCSPMM_DTYPE_F32 forwards to the fp32 entry points (value_index_d NULL: hcspmm_forward_weighted_heads, and num_values
+ * must then be num_edges; z_dtype must be F32).  HCSPMM_DTYPE_F16 / BF16 (spmm_heads16.hip): X_d holds 16-bit elements, values_d
+ * stays fp32 head-major [heads][num_values], every entry adds acc = fmaf(v, widen(x), acc) in fp32, and Z_d is fp32
+ * (z_dtype = HCSPMM_DTYPE_F32) or X's type (z_dtype = dtype) rounded once from the fp32 sum (nearest even, a NaN stays a NaN).
+ * Every row is served from CSR on the binary product's plan (dense-tile windows as CSR rows, split rows through fp32 partial
+ * slots: workspace hcspmm_workspace_bytes(header, embedding_dim)); ordinary, tiny and window rows sum in CSR order, wide tasks
+ * by a fixed xor-shuffle tree; no atomics, so two calls give the same bits.  value_index_d NULL means vi(e) = e with
+ * num_values = num_edges.  For the 16-bit types an odd ldx, an odd ldz of a 16-bit Z, bases off the 4-byte grid, Dh % 4 != 0
+ * (one head included), a z_dtype other than F32 or dtype, and every argument error of the fp32 call are HCSPMM_EINVAL before
+ * any device call.  Plan and plan-free, rectangular x_rows, asynchronous and capturable as the fp32 call. */
+int hcspmm_forward_weighted_heads_typed(const void* X_d, int64_t x_rows, int64_t ldx, void* Z_d, int64_t ldz, int dtype, int z_dtype,
+                                        const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                        const int32_t* blockPartition_d, const int32_t* edgeToColumn_d, const int32_t* edgeToRow_d,
+                                        const int32_t* hybrid_type_d, const int32_t* plan_d, const hcspmm_plan_header* plan_header_h,
+                                        int64_t num_nodes, int64_t num_edges, int embedding_dim, void* workspace_d,
+                                        size_t workspace_bytes, void* stream, const float* values_d, int heads,
+                                        const int32_t* value_index_d /* [E] or NULL */, int64_t num_values);
 
 /* ------------------------------------------------------------------------------------------
  * Max / min neighbour aggregation with its argmax (GraphSAGE-pool, GIN-max, PNA; PyG aggr = "max" / "min"):
@@ -869,6 +889,17 @@ int hcspmm_sddmm_heads(const void* A_d, int64_t lda, const void* B_d, int64_t b_
                        const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* plan_d,
                        const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
                        void* stream, int heads);
+
+/* hcspmm_sddmm_heads with dtype honoured.  HCSPMM_DTYPE_F32 forwards to it.  HCSPMM_DTYPE_F16 / BF16 (sddmm_heads16.hip): A_d and
+ * B_d hold 16-bit elements, out_d is fp32 head-major.  One lane group spans the whole row of heads * Dh columns, a lane owns 8
+ * (Dh % 8 == 0) or 4 columns of one head and sums its products with fmaf in column order, and the Dh / 8 (or Dh / 4) lane sums
+ * of a head are added by an xor butterfly (a power of two of them) or in lane order: within (Dh + 1) * 2^-24 * sum |a_k b_k| of
+ * the exact product, the same bits on every call.  The 16-bit types need even lda / ldb, 4-byte aligned bases, Dh % 4 == 0 and
+ * embedding_dim <= 512 (Dh % 8 == 0) or 256, else HCSPMM_EINVAL; the other checks are hcspmm_sddmm_heads'. */
+int hcspmm_sddmm_heads_typed(const void* A_d, int64_t lda, const void* B_d, int64_t b_rows, int64_t ldb, int dtype, float* out_d,
+                             const int32_t* row_pointers_d, const int32_t* column_index_d, const int32_t* plan_d,
+                             const hcspmm_plan_header* plan_header_h, int64_t num_nodes, int64_t num_edges, int embedding_dim,
+                             void* stream, int heads);
 
 /* Edge softmax over each row's stored entries, per head, on head-major fp32 arrays [heads][E] (head h is the contiguous
  * slice [h * E, (h + 1) * E), which hcspmm_forward_weighted takes as its values as is):
