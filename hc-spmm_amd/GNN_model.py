@@ -707,10 +707,69 @@ class GATv2ScoresDirected(torch.autograd.Function):
         return (d_dst, d_src, d_att) + (None,) * 6
 
 
-def gatv2_attention(H_dst, H_src, att, graph, negative_slope=0.2, directed=False):
+class GATv2Scores16(torch.autograd.Function):
+    """GATv2Scores on float16 / bfloat16 H_dst, H_src (views of one dtype on the dword grid: the halves of one 16-bit projection
+    need no copy) and the fp32 att (HCSPMM.gatv2_scores16: half the gathered bytes, fp32 logits): the node gradients come back in
+    the operands' dtype, each the fp32 sum rounded once, grad_att in fp32 (HCSPMM.gatv2_scores_backward16)."""
+
+    @staticmethod
+    def forward(ctx, H_dst, H_src, att, negative_slope, perm32, row_pointers, column_index):
+        att = att.contiguous()
+        logits = HCSPMM.gatv2_scores16(H_dst, H_src, att, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(H_dst, H_src, att, perm32, row_pointers, column_index)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        H_dst, H_src, att, perm32, row_pointers, column_index = ctx.saved_tensors
+        d_dst, d_src, d_att = HCSPMM.gatv2_scores_backward16(d_logits.contiguous(), H_dst, H_src, att, row_pointers, column_index,
+                                                             perm32, ctx.negative_slope)
+        return d_dst, d_src, d_att, None, None, None, None
+
+
+class GATv2ScoresDirected16(torch.autograd.Function):
+    """GATv2Scores16 on any square graph: the backward's grad_H_src walks A^T (HCSPMM.gatv2_scores_backward_directed16)."""
+
+    @staticmethod
+    def forward(ctx, H_dst, H_src, att, negative_slope, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t):
+        att = att.contiguous()
+        logits = HCSPMM.gatv2_scores16(H_dst, H_src, att, row_pointers, column_index, negative_slope)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t)
+        return logits
+
+    @staticmethod
+    def backward(ctx, d_logits):
+        H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, entry_index_t = ctx.saved_tensors
+        d_dst, d_src, d_att = HCSPMM.gatv2_scores_backward_directed16(d_logits.contiguous(), H_dst, H_src, att, row_pointers,
+                                                                      column_index, row_pointers_t, column_index_t, entry_index_t,
+                                                                      ctx.negative_slope)
+        return (d_dst, d_src, d_att) + (None,) * 6
+
+
+def gatv2_attention(H_dst, H_src, att, graph, negative_slope=0.2, directed=False, activation_dtype=None):
     """GATv2 attention weights alpha [heads, E] = edge softmax of GATv2Scores' logits, with autograd for H_dst, H_src and att;
     graph = the eight graph tensors, whose pattern must be symmetric (checked before any launch: the backward sums over
-    A^T) unless directed=True: the backward then walks transposed_graph(graph)."""
+    A^T) unless directed=True: the backward then walks transposed_graph(graph).
+    activation_dtype = torch.bfloat16 / torch.float16: H_dst and H_src are taken in that dtype (fp32 ones are rounded once) and the
+    16-bit score kernels run (GATv2Scores16): fp32 logits and softmax, node gradients in that dtype.  16-bit operands select them
+    as well."""
+    if activation_dtype not in (None, torch.bfloat16, torch.float16):
+        raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+    if activation_dtype is not None:
+        shared = H_dst is H_src
+        H_src = H_src.to(activation_dtype)
+        H_dst = H_src if shared else H_dst.to(activation_dtype)
+    if H_dst.dtype in (torch.bfloat16, torch.float16):
+        if directed:
+            gt = transposed_graph(graph)
+            logits = GATv2ScoresDirected16.apply(H_dst, H_src, att, float(negative_slope), graph[0], graph[1], gt[0], gt[1],
+                                                 gt[N_GRAPH])
+        else:
+            perm32 = transpose_permutation_i32(graph[0], graph[1])
+            logits = GATv2Scores16.apply(H_dst, H_src, att, float(negative_slope), perm32, graph[0], graph[1])
+        return EdgeSoftmax.apply(logits, graph[0])
     if directed:
         gt = transposed_graph(graph)
         logits = GATv2ScoresDirected.apply(H_dst, H_src, att, float(negative_slope), graph[0], graph[1], gt[0], gt[1], gt[N_GRAPH])
@@ -962,19 +1021,31 @@ class GATv2Conv(torch.nn.Module):
     mean [N, output_dim].  share_weights=True uses one projection for both roles (H_dst = H_src, [N, heads * output_dim]).
     No per-entry torch op and no [E, D] tensor in either pass.  The kernels need output_dim % 4 == 0.  _Conv's call
     signature, so that Net builds it; the attention weights are the edge values, so edge_weight is refused.  The pattern must
-    be symmetric unless directed=True (the backward then runs on transposed_graph)."""
+    be symmetric unless directed=True (the backward then runs on transposed_graph).
+
+    activation_dtype = torch.bfloat16 / torch.float16 (_Conv's convention): X is taken in that dtype (an fp32 X is rounded once),
+    the projection runs on _Update16, the attention on the 16-bit score kernels through gatv2_attention (fp32 logits and softmax)
+    and the aggregation on EdgeWeightedAggregateHeads16; the mean of heads is taken in fp32 and rounded once.  The layer returns
+    activation_dtype; the parameters and their gradients stay fp32, so an fp32 layer's state dict loads.  input_dim must be even
+    and heads * output_dim at most 512 (256 when output_dim % 8 != 0): one lane group per row."""
 
     def __init__(self, input_dim, output_dim, fixed=0, heads=1, negative_slope=0.2, concat=False, share_weights=False,
-                 directed=False):
+                 directed=False, activation_dtype=None):
         super().__init__()
         self.fixed, self.heads, self.negative_slope = fixed, int(heads), float(negative_slope)
-        self.directed = bool(directed)
+        self.directed, self.activation_dtype = bool(directed), activation_dtype
         self.concat, self.share_weights, self.output_dim = bool(concat), bool(share_weights), int(output_dim)
         if self.heads < 1:
             raise ValueError("GATv2Conv needs heads >= 1, got %d" % self.heads)
         if output_dim < 4 or output_dim % 4 != 0:
             raise ValueError("GATv2Conv needs output_dim (the width of one head) to be a multiple of 4, got %d" % output_dim)
         width = self.heads * self.output_dim
+        if activation_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("activation_dtype must be None, torch.bfloat16 or torch.float16, got %r" % (activation_dtype,))
+        if activation_dtype is not None and input_dim % 2:
+            raise ValueError("activation_dtype needs an even input_dim (16-bit rows on the dword grid), got %d" % input_dim)
+        if activation_dtype is not None and width > (512 if output_dim % 8 == 0 else 256):
+            raise ValueError("activation_dtype serves heads * output_dim up to 512 (output_dim %% 8 == 0) or 256, got %d" % width)
         # column block 0 = W_src, block 1 = W_dst (absent with share_weights); within a block, head k's columns are contiguous
         self.weights = torch.nn.Parameter(torch.empty(input_dim, width if self.share_weights else 2 * width))
         self.att = torch.nn.Parameter(torch.empty(self.heads, self.output_dim))
@@ -993,13 +1064,16 @@ class GATv2Conv(torch.nn.Module):
         if not self.directed:
             transpose_permutation_i32(row_pointers, column_index)  # an asymmetric pattern is refused before any launch (cached)
         width = self.heads * self.output_dim
-        h = _Update.apply(X, self.weights)
+        lo = self.activation_dtype
+        h = _Update.apply(X, self.weights) if lo is None else _Update16.apply(X.to(lo), self.weights)
         h_src = h[:, :width]
         h_dst = h_src if self.share_weights else h[:, width:]
-        alpha = gatv2_attention(h_dst, h_src, self.att, graph, self.negative_slope, self.directed)  # [heads, E]
-        out = edge_weighted_aggregate_heads(h_src, alpha, graph, self.directed)  # [N, heads * output_dim]
+        alpha = gatv2_attention(h_dst, h_src, self.att, graph, self.negative_slope, self.directed, lo)  # [heads, E]
+        out = edge_weighted_aggregate_heads(h_src, alpha, graph, self.directed, lo)  # [N, heads * output_dim]
         if self.concat or self.heads == 1:
             return out
+        if lo is not None:  # the mean of heads in fp32, rounded once
+            return out.float().view(out.size(0), self.heads, self.output_dim).mean(1).to(lo)
         return out.view(out.size(0), self.heads, self.output_dim).mean(1)
 
 

@@ -28,7 +28,8 @@ from GNN_model import SAG, GATConv, GATv2Conv, GCNConv, GENConv, GINConv, GINECo
 
 
 _ACTIVATION_DTYPE_MODELS = ("--activation-dtype needs --model gcn or gin with --norm sym or mean, --model sage, pna, gen or gine, or "
-                            "--model gat with --gat-concat (gatv2 and the mean-of-heads gat layers stay fp32)")
+                            "--model gat with --gat-concat (the mean-of-heads gat layer stays fp32; gatv2 runs in 16 bits through "
+                            "GATv2Conv(activation_dtype=), not through this driver)")
 
 
 def parse_args(argv=None):

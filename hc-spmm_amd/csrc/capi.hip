@@ -1332,6 +1332,67 @@ extern "C" int hcspmm_gatv2_scores_backward_directed(const float* grad_logits, c
                              E, D, heads, grad_dst, ld_gdst, grad_src, ld_gsrc, grad_att, workspace, workspace_bytes, stream_v);
 }
 
+// GATv2 attention on node rows of one element type (fp32: the calls above; fp16 / bf16: gatv2_attention16.hip, one lane group per
+// row).  Every refusal comes before any device call.
+extern "C" int hcspmm_gatv2_scores_typed(const void* H_dst, int64_t ld_dst, const void* H_src, int64_t src_rows, int64_t ld_src,
+                                         int dtype, const float* att, float slope, float* logits, const int32_t* rowptr,
+                                         const int32_t* col, int64_t N, int64_t E, int D, int heads, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_gatv2_scores(static_cast<const float*>(H_dst), ld_dst, static_cast<const float*>(H_src), src_rows, ld_src, att, slope,
+                               logits, rowptr, col, N, E, D, heads, stream_v);
+  if (N < 0 || E < 0 || src_rows < 0 || !gatv2_shape_ok(D, heads) || !hcspmm::gatv2_16_supported(D, heads) || ld_dst < D ||
+      ld_src < D || !rowptr || !att || !__builtin_isfinite(slope))
+    return HCSPMM_EINVAL;
+  if (((ld_dst | ld_src) & 1) != 0 || !aligned(H_dst, 4) || !aligned(H_src, 4)) return HCSPMM_EINVAL;  // rows on the dword grid
+  if ((N > 0 && !H_dst) || (src_rows > 0 && !H_src)) return HCSPMM_EINVAL;
+  if (E > 0 && (!logits || !col || N == 0 || src_rows == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 16 || E > INT32_MAX || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  if (E == 0) return HCSPMM_OK;
+  hcspmm::Gatv2Args16 a{};
+  a.H_dst = H_dst, a.H_src = H_src, a.att = att, a.rowptr = rowptr, a.col = col, a.out = logits;
+  a.ld_dst = (size_t)ld_dst, a.ld_src = (size_t)ld_src;
+  a.slope = slope, a.N = (int)N, a.D = D, a.heads = heads, a.E = (long long)E;
+  const hipError_t e = hcspmm::launch_gatv2_scores16(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
+extern "C" int hcspmm_gatv2_scores_backward_typed(const float* grad_logits, const void* H_dst, int64_t ld_dst, const void* H_src,
+                                                  int64_t ld_src, int dtype, const float* att, float slope, const int32_t* rowptr,
+                                                  const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t,
+                                                  const int32_t* entry_t, int64_t src_rows, int64_t N, int64_t E, int D, int heads,
+                                                  void* grad_dst, int64_t ld_gdst, void* grad_src, int64_t ld_gsrc, int grad_dtype,
+                                                  float* grad_att, void* workspace, size_t workspace_bytes, void* stream_v) {
+  if (dtype < HCSPMM_DTYPE_F32 || dtype > HCSPMM_DTYPE_BF16) return HCSPMM_EINVAL;
+  if (grad_dtype != HCSPMM_DTYPE_F32 && grad_dtype != dtype) return HCSPMM_EINVAL;
+  if (dtype == HCSPMM_DTYPE_F32)
+    return hcspmm_gatv2_scores_backward_directed(grad_logits, static_cast<const float*>(H_dst), ld_dst, static_cast<const float*>(H_src),
+                                                 ld_src, att, slope, rowptr, col, rowptr_t, col_t, entry_t, src_rows, N, E, D, heads,
+                                                 static_cast<float*>(grad_dst), ld_gdst, static_cast<float*>(grad_src), ld_gsrc, grad_att,
+                                                 workspace, workspace_bytes, stream_v);
+  const int64_t n_t = src_rows;
+  const bool g16 = grad_dtype != HCSPMM_DTYPE_F32;
+  if (N < 0 || E < 0 || n_t < 0 || !gatv2_shape_ok(D, heads) || !hcspmm::gatv2_16_supported(D, heads) || ld_dst < D || ld_src < D ||
+      ld_gdst < D || ld_gsrc < D || !rowptr || !rowptr_t || !att || !grad_att || !__builtin_isfinite(slope))
+    return HCSPMM_EINVAL;
+  if (((ld_dst | ld_src) & 1) != 0 || !aligned(H_dst, 4) || !aligned(H_src, 4)) return HCSPMM_EINVAL;  // rows on the dword grid
+  if (g16 && (((ld_gdst | ld_gsrc) & 1) != 0 || !aligned(grad_dst, 4) || !aligned(grad_src, 4))) return HCSPMM_EINVAL;
+  if ((N > 0 && (!H_dst || !grad_dst)) || (n_t > 0 && (!H_src || !grad_src))) return HCSPMM_EINVAL;
+  if (E > 0 && (!grad_logits || !col || !col_t || !entry_t || N == 0 || n_t == 0)) return HCSPMM_EINVAL;
+  if (N > INT32_MAX - 2048 || n_t > INT32_MAX - 2048 || E > INT32_MAX - 4096 || E > INT64_MAX / 4 / heads) return HCSPMM_ERANGE;
+  const size_t need = hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads);
+  if (workspace_bytes < need) return HCSPMM_EWORKSPACE;
+  if (need > 0 && !workspace) return HCSPMM_EINVAL;
+  hcspmm::Gatv2Args16 a{};
+  a.H_dst = H_dst, a.H_src = H_src, a.att = att, a.g = grad_logits, a.rowptr = rowptr, a.col = col, a.perm = entry_t;
+  a.rowptr_t = rowptr_t, a.col_t = col_t, a.n_t = (int)n_t;
+  a.grad_dst = grad_dst, a.grad_src = grad_src, a.grad_att = grad_att, a.partial = static_cast<float*>(workspace);
+  a.ld_dst = (size_t)ld_dst, a.ld_src = (size_t)ld_src, a.ld_gdst = (size_t)ld_gdst, a.ld_gsrc = (size_t)ld_gsrc;
+  a.slope = slope, a.N = (int)N, a.D = D, a.heads = heads, a.grad16 = g16 ? 1 : 0, a.E = (long long)E;
+  const hipError_t e = hcspmm::launch_gatv2_backward16(a, dtype, reinterpret_cast<hipStream_t>(stream_v));
+  return e == hipSuccess ? HCSPMM_OK : fail_hip(e);
+}
+
 extern "C" int hcspmm_forward_strided(const float* X, int64_t x_rows, int64_t ldx, float* Z, int64_t ldz, const int32_t* rowptr,
                                       const int32_t* col, const int32_t* blockPartition, const int32_t* edgeToColumn,
                                       const int32_t* edgeToRow, const int32_t* hybrid_type, const int32_t* plan_d,

@@ -515,4 +515,35 @@ hipError_t launch_heads16(const Heads16Args& a, int dtype, hipStream_t stream);
 bool sddmm_heads16_supported(int D, int heads);
 hipError_t launch_sddmm_heads16(const SddmmArgs& a, int heads, int dtype, hipStream_t stream);
 
+// GATv2 attention logits and their backward on fp16 / bf16 rows (gatv2_attention16.hip; the 16-bit dtypes of
+// hcspmm_gatv2_scores_typed / hcspmm_gatv2_scores_backward_typed): Gatv2Args with H_dst / H_src holding 16-bit elements on the dword
+// grid (even strides, 4-byte aligned bases); att, g, the logits, grad_att and the partials stay fp32.  grad16 = 1: grad_dst /
+// grad_src hold the operands' 16-bit type (even ld_gdst / ld_gsrc, 4-byte aligned bases), each element rounded once from its fp32
+// sum; 0: fp32.  One lane group per row (gatv2_16_supported = sddmm_heads16_supported).  The backward's grid never exceeds
+// gatv2_grad_blocks(N, D): partial is sized by the fp32 query.
+struct Gatv2Args16 {
+  const void* H_dst;  // [N][ld_dst]
+  const void* H_src;  // [src_rows][ld_src] (backward: src_rows = n_t)
+  const float* att;   // [heads][Dh]
+  const float* g;     // backward: [heads][E]
+  const int* rowptr;  // [N + 1]
+  const int* col;     // [E]
+  const int* perm;    // backward: [E]
+  float* out;         // forward: [heads][E]
+  void* grad_dst;     // backward: [N][ld_gdst]
+  void* grad_src;     // backward: [n_t][ld_gsrc]
+  float* grad_att;    // backward: [heads][Dh]
+  float* partial;     // backward: the workgroups' [D] partials of grad_att
+  size_t ld_dst, ld_src, ld_gdst, ld_gsrc;
+  float slope;
+  int N, D, heads, grad16;
+  long long E;
+  const int* rowptr_t;  // [n_t + 1]
+  const int* col_t;     // [E]
+  int n_t;
+};
+bool gatv2_16_supported(int D, int heads);
+hipError_t launch_gatv2_scores16(const Gatv2Args16& a, int dtype, hipStream_t stream);
+hipError_t launch_gatv2_backward16(const Gatv2Args16& a, int dtype, hipStream_t stream);
+
 }  // namespace hcspmm

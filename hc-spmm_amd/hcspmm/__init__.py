@@ -26,7 +26,7 @@ __all__ = [
     "backward_fixed64_fused", "backward_final_fused_64", "backward_GIN_final_fused", "loi_reorder",
     "apply_permutation", "weight_grad", "update", "plan_header", "forward_rect", "forward_into", "sddmm", "edge_softmax", "edge_softmax_backward",
     "gat_attention", "gat_attention_backward", "forward_weighted_heads", "sddmm_heads",
-    "gatv2_scores", "gatv2_scores_backward",
+    "gatv2_scores", "gatv2_scores_backward", "gatv2_scores16", "gatv2_scores_backward16", "gatv2_scores_backward_directed16",
     "transpose_graph", "transpose_graph_device", "sample_row_pointers", "sample_neighbors", "plan_free_graph",
     "SAMPLE_WAVE_ROW_MAX", "forward_weighted_indexed", "gat_attention_backward_directed", "gatv2_scores_backward_directed",
     "forward_max", "forward_min", "forward_extremum_backward", "forward_multi", "forward_multi16",
@@ -1677,6 +1677,104 @@ def gatv2_scores_backward_directed(grad_logits, H_dst, H_src, att, row_pointers,
     int32) of a pattern-symmetric graph it returns gatv2_scores_backward's bits."""
     return _gatv2_scores_backward(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
                                   entry_index_t, negative_slope)
+
+
+def _gatv2_operands16(H_dst, H_src, att, row_pointers, column_index):
+    """-> (N, E, D, heads) of a 16-bit GATv2 call: H_dst [N, D] and H_src [src_rows, D] float16 / bfloat16 views of one dtype on the
+    dword grid (unit inner stride, even row strides, 4-byte aligned), att float32 [heads, Dh] (or [Dh]) contiguous, D = heads * Dh,
+    Dh % 4 == 0, D <= 512 (Dh % 8 == 0) or 256"""
+    _check_graph(row_pointers, column_index)
+    _check_input(att, "att")
+    if att.dtype != torch.float32 or att.dim() not in (1, 2) or att.numel() == 0:
+        raise RuntimeError("att must be a float32 [Dh] or [heads, Dh] tensor, got %s %s" % (att.dtype, tuple(att.shape)))
+    heads = 1 if att.dim() == 1 else att.size(0)
+    _check_heads16(H_dst, "H_dst", heads)
+    _check_heads16(H_src, "H_src", heads, like=H_dst)
+    N, E, D = row_pointers.numel() - 1, column_index.numel(), H_dst.size(1)
+    if H_dst.size(0) != N:
+        raise RuntimeError("H_dst has %d rows but the graph has %d nodes" % (H_dst.size(0), N))
+    if H_src.size(1) != D:
+        raise RuntimeError("H_src has %d columns but H_dst has %d" % (H_src.size(1), D))
+    if att.numel() != D:
+        raise RuntimeError("att has %d elements but H_dst has %d columns" % (att.numel(), D))
+    if H_src.device != H_dst.device or att.device != H_dst.device or row_pointers.device != H_dst.device:
+        raise RuntimeError("H_src, att and the graph must be on the device of H_dst")
+    if D > (512 if (D // heads) % 8 == 0 else 256):
+        raise RuntimeError("the 16-bit GATv2 kernels serve rows of up to 512 columns (Dh %% 8 == 0) or 256: D = %d" % D)
+    return N, E, D, heads
+
+
+def gatv2_scores16(H_dst, H_src, att, row_pointers, column_index, negative_slope=0.2):
+    """gatv2_scores on float16 / bfloat16 node rows -> float32 [heads, E] ([E] for a 1-D att) (hcspmm.h
+    hcspmm_gatv2_scores_typed): H_dst [N, D] and H_src [src_rows, D] are 16-bit views of one dtype (unit inner stride, even row
+    strides, 4-byte aligned: the halves of one [N, 2 D] projection need no copy), att float32, D = heads * Dh, Dh % 4 == 0,
+    D <= 512 (Dh % 8 == 0) or 256.  One lane group per row, each H_src row gathered once at half the fp32 call's bytes; z, l and
+    the sums are fp32, the same bits on every call."""
+    N, E, D, heads = _gatv2_operands16(H_dst, H_src, att, row_pointers, column_index)
+    out = torch.empty((E,) if att.dim() == 1 else (heads, E), dtype=torch.float32, device=H_dst.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)
+    with _on_device(H_dst.device):
+        check(lib().hcspmm_gatv2_scores_typed(_ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.size(0), H_src.stride(0),
+                                              _DTYPES[H_dst.dtype], _ptr(att), float(negative_slope), _ptr(out), _ptr(row_pointers),
+                                              _ptr(column_index), N, E, D, heads, stream))
+    return out
+
+
+def _gatv2_scores_backward16(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t, perm,
+                             negative_slope, grad_dtype):
+    """row_pointers_t None: the pattern-symmetric form (the graph's own arrays and transpose_permutation's perm as the transposed
+    arguments); else the directed form (A^T's arrays, perm = entry_index_t)"""
+    N, E, D, heads = _gatv2_operands16(H_dst, H_src, att, row_pointers, column_index)
+    if H_src.size(0) != N:
+        raise RuntimeError("H_src has %d rows but the backward needs one per node (%d)" % (H_src.size(0), N))
+    grad_dtype = H_dst.dtype if grad_dtype is None else grad_dtype
+    if grad_dtype not in (torch.float32, H_dst.dtype):
+        raise RuntimeError("grad_dtype must be float32 or the dtype of H_dst (%s), got %s" % (H_dst.dtype, grad_dtype))
+    shape = (E,) if att.dim() == 1 else (heads, E)
+    _check_input(grad_logits, "grad_logits")
+    if grad_logits.dtype != torch.float32 or tuple(grad_logits.shape) != shape:
+        raise RuntimeError("grad_logits must be float32 of shape %s, got %s %s" % (shape, grad_logits.dtype, tuple(grad_logits.shape)))
+    if grad_logits.device != H_dst.device:
+        raise RuntimeError("grad_logits must be on the device of H_dst")
+    if row_pointers_t is None:
+        perm = _perm_i32(perm, E, row_pointers.device)
+        row_pointers_t, column_index_t = row_pointers, column_index
+    else:
+        _transposed_i32(row_pointers_t, "row_pointers_t", N + 1, row_pointers.device)
+        _transposed_i32(column_index_t, "column_index_t", E, row_pointers.device)
+        _transposed_i32(perm, "entry_index_t", E, row_pointers.device)
+    L = lib()
+    grad_dst = torch.empty((N, D), dtype=grad_dtype, device=H_dst.device)
+    grad_src = torch.empty((N, D), dtype=grad_dtype, device=H_dst.device)
+    grad_att = torch.empty_like(att)
+    ws_bytes = int(L.hcspmm_gatv2_backward_workspace_bytes(N, E, D, heads))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=H_dst.device)
+    with _on_device(H_dst.device):
+        check(L.hcspmm_gatv2_scores_backward_typed(
+            _ptr(grad_logits), _ptr(H_dst), H_dst.stride(0), _ptr(H_src), H_src.stride(0), _DTYPES[H_dst.dtype], _ptr(att),
+            float(negative_slope), _ptr(row_pointers), _ptr(column_index), _ptr(row_pointers_t), _ptr(column_index_t), _ptr(perm), N, N,
+            E, D, heads, _ptr(grad_dst), D, _ptr(grad_src), D, _DTYPES[grad_dtype], _ptr(grad_att), _ptr(ws), ws_bytes,
+            ctypes.c_void_p(torch.cuda.current_stream(H_dst.device).cuda_stream)))
+    return grad_dst, grad_src, grad_att
+
+
+def gatv2_scores_backward16(grad_logits, H_dst, H_src, att, row_pointers, column_index, perm, negative_slope=0.2, grad_dtype=None):
+    """Backward of gatv2_scores16 on a square, pattern-symmetric graph -> (grad_H_dst, grad_H_src, grad_att): the node gradients
+    [N, D] contiguous in grad_dtype = the operands' dtype (the default; each element the fp32 sum rounded once) or float32,
+    grad_att float32 shaped as att.  grad_logits float32 of gatv2_scores16's shape; perm is transpose_permutation's (int64 or
+    int32).  Three launches, no atomics: two calls give the same bits (hcspmm_gatv2_scores_backward_typed; the workspace is
+    allocated here, sized by hcspmm_gatv2_backward_workspace_bytes)."""
+    return _gatv2_scores_backward16(grad_logits, H_dst, H_src, att, row_pointers, column_index, None, None, perm, negative_slope,
+                                    grad_dtype)
+
+
+def gatv2_scores_backward_directed16(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
+                                     entry_index_t, negative_slope=0.2, grad_dtype=None):
+    """gatv2_scores_backward16 on any square graph: (row_pointers_t, column_index_t, entry_index_t) are transpose_graph's, and
+    grad_H_src walks the rows of A^T.  With (row_pointers, column_index, perm as int32) of a pattern-symmetric graph it returns
+    gatv2_scores_backward16's bits."""
+    return _gatv2_scores_backward16(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t, column_index_t,
+                                    entry_index_t, negative_slope, grad_dtype)
 
 
 _DTYPE16 = {torch.float16: 1, torch.bfloat16: 2}  # HCSPMM_DTYPE_F16 / _BF16

@@ -159,6 +159,10 @@ SYMBOLS = {
                                             _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "hcspmm_gatv2_scores_backward_directed": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64,
                                                      _i64, _i64, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "hcspmm_gatv2_scores_typed": (_int, [_vp, _i64, _vp, _i64, _i64, _int, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _int, _int,
+                                         _vp]),
+    "hcspmm_gatv2_scores_backward_typed": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                  _i64, _i64, _int, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _sz, _vp]),
     "hcspmm_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz, _vp]),
     "hcspmm_forward_strided": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _hp, _i64, _i64, _int, _vp, _sz,
                                       _vp]),

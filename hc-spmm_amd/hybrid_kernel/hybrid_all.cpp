@@ -1270,6 +1270,89 @@ std::vector<torch::Tensor> gatv2_scores_backward(torch::Tensor grad_logits, torc
                                    negative_slope);
 }
 
+// 16-bit GATv2 operands: H_dst [N, D] and H_src [src_rows, D] float16 / bfloat16 views of one dtype on the dword grid, att float32
+// [heads, Dh] (or [Dh]) contiguous with D elements, D <= 512 (Dh % 8 == 0) or 256 -> heads
+int64_t gatv2_operands16(const torch::Tensor& H_dst, const torch::Tensor& H_src, const torch::Tensor& att,
+                         const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  CHECK_INPUT(nodePointer);
+  CHECK_INPUT(edgeList);
+  check_i32_graph(nodePointer, edgeList);
+  CHECK_INPUT(att);
+  TORCH_CHECK(att.scalar_type() == torch::kFloat && (att.dim() == 1 || att.dim() == 2) && att.numel() > 0,
+              "att must be a float32 [Dh] or [heads, Dh] tensor, got ", att.scalar_type(), " ", att.sizes());
+  const int64_t heads = att.dim() == 1 ? 1 : att.size(0);
+  check_heads16(H_dst, "H_dst", heads);
+  check_heads16(H_src, "H_src", heads, &H_dst);
+  const int64_t N = nodePointer.numel() - 1, D = H_dst.size(1);
+  TORCH_CHECK(H_dst.size(0) == N, "H_dst has ", H_dst.size(0), " rows but the graph has ", N, " nodes");
+  TORCH_CHECK(H_src.size(1) == D, "H_src has ", H_src.size(1), " columns but H_dst has ", D);
+  TORCH_CHECK(att.numel() == D, "att has ", att.numel(), " elements but H_dst has ", D, " columns");
+  TORCH_CHECK(H_src.device() == H_dst.device() && att.device() == H_dst.device() && nodePointer.device() == H_dst.device(),
+              "H_src, att and the graph must be on the device of H_dst");
+  TORCH_CHECK(D <= ((D / heads) % 8 == 0 ? 512 : 256),
+              "the 16-bit GATv2 kernels serve rows of up to 512 columns (Dh % 8 == 0) or 256: D = ", D);
+  return heads;
+}
+
+// GATv2 attention logits of float16 / bfloat16 node rows (hcspmm_gatv2_scores_typed): float32 [heads, E] ([E] for a 1-D att)
+torch::Tensor gatv2_scores16(torch::Tensor H_dst, torch::Tensor H_src, torch::Tensor att, torch::Tensor nodePointer,
+                             torch::Tensor edgeList, double negative_slope) {
+  const int64_t heads = gatv2_operands16(H_dst, H_src, att, nodePointer, edgeList);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), D = H_dst.size(1);
+  auto out = att.dim() == 1 ? torch::empty({E}, att.options()) : torch::empty({heads, E}, att.options());
+  const c10::DeviceGuard guard(H_dst.device());
+  check_rc(hcspmm_gatv2_scores_typed(H_dst.data_ptr(), H_dst.stride(0), H_src.data_ptr(), H_src.size(0), H_src.stride(0),
+                                     feature_dtype(H_dst), fptr(att), (float)negative_slope, mfptr(out), iptr(nodePointer),
+                                     iptr(edgeList), N, E, (int)D, (int)heads, current_stream(H_dst)),
+           "gatv2_scores16");
+  return out;
+}
+
+// Backward of gatv2_scores16 (hcspmm_gatv2_scores_backward_typed; the workspace is allocated here) -> [grad_H_dst, grad_H_src,
+// grad_att], the node gradients in grad_dtype (None: the operands' dtype) or float32.  rp_t / col_t undefined: the
+// pattern-symmetric form (the graph's own arrays with perm = transpose_permutation); defined: A^T's, perm = entry_index_t
+std::vector<torch::Tensor> gatv2_scores_backward16_any(torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src,
+                                                       torch::Tensor att, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                       torch::Tensor rp_t, torch::Tensor col_t, torch::Tensor perm,
+                                                       double negative_slope, c10::optional<torch::ScalarType> grad_dtype) {
+  const int64_t heads = gatv2_operands16(H_dst, H_src, att, nodePointer, edgeList);
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), D = H_dst.size(1);
+  TORCH_CHECK(H_src.size(0) == N, "H_src has ", H_src.size(0), " rows but the backward needs one per node (", N, ")");
+  const torch::ScalarType gt = grad_dtype ? *grad_dtype : H_dst.scalar_type();
+  TORCH_CHECK(gt == torch::kFloat || gt == H_dst.scalar_type(), "grad_dtype must be float32 or the dtype of H_dst (",
+              H_dst.scalar_type(), "), got ", gt);
+  const std::vector<int64_t> shape = att.dim() == 1 ? std::vector<int64_t>{E} : std::vector<int64_t>{heads, E};
+  CHECK_INPUT(grad_logits);
+  TORCH_CHECK(grad_logits.scalar_type() == torch::kFloat && grad_logits.sizes() == c10::IntArrayRef(shape),
+              "grad_logits must be float32 of shape ", c10::IntArrayRef(shape), ", got ", grad_logits.scalar_type(), " ",
+              grad_logits.sizes());
+  TORCH_CHECK(grad_logits.device() == H_dst.device(), "grad_logits must be on the device of H_dst");
+  CHECK_INPUT(perm);
+  TORCH_CHECK((perm.scalar_type() == torch::kInt || perm.scalar_type() == torch::kLong) && perm.dim() == 1 && perm.numel() == E,
+              "perm must be an int32 / int64 [E] tensor with E = ", E, ", got ", perm.scalar_type(), " ", perm.sizes());
+  TORCH_CHECK(perm.device() == nodePointer.device(), "perm must be on the device of row_pointers");
+  auto perm32 = perm.scalar_type() == torch::kInt ? perm : perm.to(torch::kInt);
+  if (rp_t.defined()) {
+    check_transposed(rp_t, "row_pointers_t", N + 1, nodePointer);
+    check_transposed(col_t, "column_index_t", E, nodePointer);
+  } else {
+    rp_t = nodePointer;
+    col_t = edgeList;
+  }
+  auto grad_dst = torch::empty({N, D}, H_dst.options().dtype(gt)), grad_src = torch::empty({N, D}, H_dst.options().dtype(gt));
+  auto grad_att = torch::empty_like(att);
+  const size_t ws_bytes = hcspmm_gatv2_backward_workspace_bytes(N, E, (int)D, (int)heads);
+  auto ws = torch::empty({(int64_t)(ws_bytes / 4)}, att.options());
+  const c10::DeviceGuard guard(H_dst.device());
+  check_rc(hcspmm_gatv2_scores_backward_typed(fptr(grad_logits), H_dst.data_ptr(), H_dst.stride(0), H_src.data_ptr(), H_src.stride(0),
+                                              feature_dtype(H_dst), fptr(att), (float)negative_slope, iptr(nodePointer),
+                                              iptr(edgeList), iptr(rp_t), iptr(col_t), iptr(perm32), N, N, E, (int)D, (int)heads,
+                                              grad_dst.data_ptr(), D, grad_src.data_ptr(), D, feature_dtype(grad_dst),
+                                              mfptr(grad_att), (void*)mfptr(ws), ws_bytes, current_stream(H_dst)),
+           "gatv2_scores_backward16");
+  return {grad_dst, grad_src, grad_att};
+}
+
 std::vector<torch::Tensor> run_fused(const torch::Tensor& input, const torch::Tensor& nodePointer,
                                      const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow,
@@ -1827,6 +1910,35 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grad_att] (gfx950)",
         pybind11::arg("grad_logits"), pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"),
         pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("perm"), pybind11::arg("negative_slope") = 0.2);
+  m.def("gatv2_scores16", &gatv2_scores16,
+        "GATv2 attention logits of float16 / bfloat16 node rows: float32 [heads, E], half the gathered bytes of gatv2_scores (gfx950)",
+        pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"), pybind11::arg("row_pointers"),
+        pybind11::arg("column_index"), pybind11::arg("negative_slope") = 0.2);
+  m.def("gatv2_scores_backward16",
+        [](torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src, torch::Tensor att, torch::Tensor row_pointers,
+           torch::Tensor column_index, torch::Tensor perm, double negative_slope, c10::optional<torch::ScalarType> grad_dtype) {
+          return gatv2_scores_backward16_any(grad_logits, H_dst, H_src, att, row_pointers, column_index, torch::Tensor(),
+                                             torch::Tensor(), perm, negative_slope, grad_dtype);
+        },
+        "backward of gatv2_scores16 (square, pattern-symmetric graph; perm = transpose_permutation) -> [grad_H_dst, grad_H_src, "
+        "grad_att]; the node gradients in grad_dtype = the operands' dtype (None) or float32 (gfx950)",
+        pybind11::arg("grad_logits"), pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("perm"), pybind11::arg("negative_slope") = 0.2,
+        pybind11::arg("grad_dtype") = pybind11::none());
+  m.def("gatv2_scores_backward_directed16",
+        [](torch::Tensor grad_logits, torch::Tensor H_dst, torch::Tensor H_src, torch::Tensor att, torch::Tensor row_pointers,
+           torch::Tensor column_index, torch::Tensor row_pointers_t, torch::Tensor column_index_t, torch::Tensor entry_index_t,
+           double negative_slope, c10::optional<torch::ScalarType> grad_dtype) {
+          TORCH_CHECK(row_pointers_t.defined() && column_index_t.defined(), "row_pointers_t and column_index_t are required");
+          return gatv2_scores_backward16_any(grad_logits, H_dst, H_src, att, row_pointers, column_index, row_pointers_t,
+                                             column_index_t, entry_index_t, negative_slope, grad_dtype);
+        },
+        "backward of gatv2_scores16 on any square graph; (row_pointers_t, column_index_t, entry_index_t) from transpose_graph -> "
+        "[grad_H_dst, grad_H_src, grad_att] (gfx950)",
+        pybind11::arg("grad_logits"), pybind11::arg("H_dst"), pybind11::arg("H_src"), pybind11::arg("att"),
+        pybind11::arg("row_pointers"), pybind11::arg("column_index"), pybind11::arg("row_pointers_t"),
+        pybind11::arg("column_index_t"), pybind11::arg("entry_index_t"), pybind11::arg("negative_slope") = 0.2,
+        pybind11::arg("grad_dtype") = pybind11::none());
   m.def("abi_version", []() { return hcspmm_abi_version(); });
   // LOI layout reorder on the host (the reference ships it as a separate file-to-file program, LOI.cpp)
   m.def("loi_reorder", [](torch::Tensor row_pointers, torch::Tensor column_index, int variant) {

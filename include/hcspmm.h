@@ -39,7 +39,8 @@ extern "C" {
  * hcspmm_gated_workspace_bytes, hcspmm_forward_gated (round 22); hcspmm_forward_gated_typed (round 23);
  * hcspmm_forward_extremum_typed (round 25); hcspmm_forward_softmax_typed, hcspmm_softmax_backward_typed (round 26);
  * hcspmm_forward_multi_typed (round 27); hcspmm_forward_edge_messages_typed, hcspmm_edge_messages_grad_typed (round 28);
- * hcspmm_forward_weighted_heads_typed, hcspmm_sddmm_heads_typed (round 29).
+ * hcspmm_forward_weighted_heads_typed, hcspmm_sddmm_heads_typed (round 29); hcspmm_gatv2_scores_typed,
+ * hcspmm_gatv2_scores_backward_typed (round 30).
  * HCSPMM_RULE_MI355X as the front-ends' default classifier is a front-end
  * matter: every C entry point that classifies takes its rule as an argument. */
 #define HCSPMM_ABI_VERSION 3
@@ -1016,6 +1017,45 @@ int hcspmm_gatv2_scores_backward_directed(const float* grad_logits_d, const floa
                                           int embedding_dim, int heads, float* grad_H_dst_out_d, int64_t ld_gdst,
                                           float* grad_H_src_out_d, int64_t ld_gsrc, float* grad_att_out_d /* [heads][Dh] */,
                                           void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* hcspmm_gatv2_scores with dtype honoured.  HCSPMM_DTYPE_F32 forwards to it: its bits and its codes.  HCSPMM_DTYPE_F16 / BF16
+ * (gatv2_attention16.hip): H_dst_d and H_src_d hold 16-bit elements, att_d and logits_out_d stay fp32.  One lane group spans the
+ * entry's whole row of heads * Dh columns and a lane owns VEC columns of one head: VEC = 8 (one 16-byte load) when Dh % 8 == 0,
+ * else 4 (one 8-byte load).  The loads are dword-aligned vectors, so Dh alone selects VEC; bases and strides need the dword grid
+ * only (below), and a 16-byte (8-byte) aligned base with strides that are multiples of 8 (4) elements keeps every lane's load
+ * inside one naturally aligned vector, which is the fast case and never a different result.  The widened values are exact, z and
+ * l are each rounded once in fp32 as in the fp32 call, a lane sums fmaf(att, l, acc) in column order, and the Dh / VEC lane sums
+ * of a head are added by an xor butterfly (a power of two of them) or by the head's first lane in lane order: within
+ * (Dh + 2) * 2^-24 * sum_k |att_k l_k| of the exact logit, the same bits on every call; every (head, entry) is written exactly
+ * once, no atomics.  The 16-bit types need even ld_dst / ld_src, 4-byte aligned bases, Dh % 4 == 0 and embedding_dim <= 512
+ * (Dh % 8 == 0) or 256 -- one lane group per row, the range of hcspmm_sddmm_heads_typed -- else HCSPMM_EINVAL, as is a dtype
+ * outside HCSPMM_DTYPE_*; the other checks are hcspmm_gatv2_scores', all before any device call.  N = 0 or E = 0 launches
+ * nothing.  Asynchronous on `stream`, capturable into a HIP graph. */
+int hcspmm_gatv2_scores_typed(const void* H_dst_d, int64_t ld_dst, const void* H_src_d, int64_t src_rows, int64_t ld_src, int dtype,
+                              const float* att_d /* [heads][Dh] */, float negative_slope, float* logits_out_d /* [heads][E] */,
+                              const int32_t* row_pointers_d, const int32_t* column_index_d, int64_t num_nodes, int64_t num_edges,
+                              int embedding_dim, int heads, void* stream);
+
+/* hcspmm_gatv2_scores_backward_directed with dtype honoured (passing a pattern-symmetric graph's own arrays, its int32
+ * permutation and num_nodes as the transposed arguments serves the undirected case, as documented there).  HCSPMM_DTYPE_F32 with
+ * grad_dtype = HCSPMM_DTYPE_F32 forwards to it.  HCSPMM_DTYPE_F16 / BF16: H_dst_d / H_src_d hold 16-bit elements; grad_logits_d,
+ * att_d and grad_att_out_d stay fp32; grad_H_dst_out_d / grad_H_src_out_d hold grad_dtype, which is HCSPMM_DTYPE_F32 or dtype
+ * itself -- then each element is the fp32 value rounded once.  The three formulas, the row tiers (one lane group up to 32 entries,
+ * one wave up to 256, the workgroup beyond), the fold orders and the determinism contract are the fp32 call's, on D / VEC lanes
+ * per row (VEC as in hcspmm_gatv2_scores_typed), so the row launches' grids never exceed the fp32 call's and
+ * hcspmm_gatv2_backward_workspace_bytes is the workspace bound here too (a shorter one is HCSPMM_EWORKSPACE).  Refusals
+ * (HCSPMM_EINVAL, before any device call): those of hcspmm_gatv2_scores_typed; a grad_dtype that is neither F32 nor dtype; for
+ * 16-bit gradients odd ld_gdst / ld_gsrc or bases off the 4-byte grid; everything the fp32 call refuses.  Rows without entries
+ * get zeros; with E = 0 all three gradients are zeroed.  Asynchronous on `stream`, capturable into a HIP graph. */
+int hcspmm_gatv2_scores_backward_typed(const float* grad_logits_d, const void* H_dst_d, int64_t ld_dst, const void* H_src_d,
+                                       int64_t ld_src, int dtype, const float* att_d, float negative_slope,
+                                       const int32_t* row_pointers_d, const int32_t* column_index_d,
+                                       const int32_t* row_pointers_t_d, const int32_t* column_index_t_d,
+                                       const int32_t* entry_index_t_d, int64_t src_rows, int64_t num_nodes, int64_t num_edges,
+                                       int embedding_dim, int heads, void* grad_H_dst_out_d, int64_t ld_gdst,
+                                       void* grad_H_src_out_d, int64_t ld_gsrc, int grad_dtype,
+                                       float* grad_att_out_d /* [heads][Dh] */, void* workspace_d, size_t workspace_bytes,
+                                       void* stream);
 
 /* hcspmm_wide_threshold for a feature type (lanes per row, hence the threshold, depend on the element size). */
 int32_t hcspmm_wide_threshold_typed(const hcspmm_plan_header* header_h, int embedding_dim, int dtype);
